@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the LM constraint-solve hot path on MI355X.
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0).  For N > 1 it is either
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0).  A plain run does only what that
+line's headline needs: set-up, warm-up, the K timed steps, the statuses of the last step (`iters_to_converge`,
+`results_ok`) and the HBM roof of the timed kernel time.  `--full` adds everything else below that is marked (--full): the
+oracle check, the extras, the legs over the other configurations, the PMC passes and the CPU baseline.  `--dump-outputs
+DIR` writes what the last timed step computed (module function dump_outputs).  For N > 1 it is either
 launched by torch.distributed.run (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE in the environment) or started
 plainly, in which case it starts the N rank processes itself -- before anything in this process touches the GPU -- and
 exits non-zero when the node has fewer than N devices.  It never reports fewer GPUs than it was asked for.
@@ -13,11 +17,11 @@ exits non-zero when the node has fewer than N devices.  It never reports fewer G
            passed): the first ~30 launches of a process run slower (clocks, first touch), and the timed region must not
            depend on how many the caller asked for.  `warmup_launches_run` says how many ran in all.
   value    whole-job solves/s = N * batch * K / max-over-ranks wall time of the K timed steps, device-resident
-           guesses in, device-resident results out (`config.value_is`).  `value_host_to_host` is the same batch
-           through the host-pointer entry point (SURVEY.md 8d's "results back on host": H2D + kernel + D2H).
+           guesses in, device-resident results out (`config.value_is`).  `value_host_to_host` (--full) is the same
+           batch through the host-pointer entry point (SURVEY.md 8d's "results back on host": H2D + kernel + D2H).
   scaling  weak: every rank owns its own shard of `--batch` systems; the path has no data-path collective
            (systems are independent), so none is issued inside the timed region
-  configs  after the headline, short legs (a few launches each, outside `value`) over the other BASELINE.json
+  configs  (--full) after the headline, short legs (a few launches each, outside `value`) over the other BASELINE.json
            configurations -- `square` x 65 536, the 1 M mixed batch, the 200 000-variable ladder, and a batch of one
            connected 300-variable sketch -- each with its rate, iterations, an oracle check and its roofs
   roofline three roofs, the highest fraction is `bound`:
@@ -28,9 +32,9 @@ exits non-zero when the node has fewer than N devices.  It never reports fewer G
              issue  vector-ALU busy cycles (SQ_ACTIVE_INST_VALU, quad-cycles) against SIMDs x kernel cycles
            plus `algorithmic_equiv`: SURVEY.md 8(d)'s BYTES formula, which charges the solver state to HBM although
            the fused kernel keeps it on chip (so it can exceed the HBM peak and is not a bound).
-           The kernel time is measured live with HIP events on the launch stream; the counters come from rocprofv3
-           child passes of this same script (one --pmc set per pass, never with a trace).
-  cpu_baseline  the CPU oracle (a C port of the reference algorithm, sparse Cholesky, per-call setup like the
+           The kernel time is measured live with HIP events on the launch stream; the counters (--full) come from
+           rocprofv3 child passes of this same script (one --pmc set per pass, never with a trace).
+  cpu_baseline  (--full) the CPU oracle (a C port of the reference algorithm, sparse Cholesky, per-call setup like the
            reference) timed on 1 host core with the CLI protocol on a bounded sample -- a reported baseline only
 """
 import argparse
@@ -72,6 +76,9 @@ SOLVE_KERNELS = ("lm_solve_kernel", "comp_solve_kernel", "ezpz_jit_solve", "ezpz
 # a tree of dense fronts on several workgroups): a launch is one solve, its roofs are over the CUs it uses.
 LEGS = [("square", 65536, 0), ("mixed", 1 << 20, 0), ("massive50000", 64, 0), ("sketch150", 262144, 0), ("sketch150", 32768, 0),
         ("sketch1000", 1, 0xFFFFFFFF)]
+# --dump-outputs writes at most this many bytes (under 64 MB with the .npy headers); a larger batch is sampled
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 0x64756D70
 
 
 def algorithmic_bytes(info: dict, k: int) -> int:
@@ -118,14 +125,24 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="massive500", help="massive<lines>[o] (o = over-constrained variant), sketch<points> (one connected sketch), a test_cases/ directory name, or mixed")
     ap.add_argument("--team", type=lambda v: int(v, 0), default=0, help="override lanes per system (0 = auto; 0xFFFFFFFF = the automatic shape for one solve)")
     ap.add_argument("--max-iterations", type=int, default=0, help="Config.max_iterations (0 = the reference's default, 35)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--check", type=int, default=1, help="verify the results of the last step against the oracle")
-    ap.add_argument("--extras", type=int, default=1, help="also report the host-to-host rate, single-solve latency (and, "
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else this script measures or checks: "
+                    "the defaults of --cpu-seconds, --check, --extras, --pmc and --legs become 12, 1, 1, 1 and 1 (else 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "to DIR/<name>.npy (float64; a fixed sample of the systems when the whole batch exceeds DUMP_BYTES; rank 0's shard)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--check", type=int, default=None, help="verify the results of the last step against the oracle")
+    ap.add_argument("--extras", type=int, default=None, help="also report the host-to-host rate, single-solve latency (and, "
                     "for N>1, the rate with the RCCL scatter/gather of the batch) -- never part of `value`")
     ap.add_argument("--specialize", type=int, default=1, help="use the run-time compiled class-specialised kernel where the topology has one")
-    ap.add_argument("--pmc", type=int, default=1, help="N=1: collect the roofline's PMC counters with rocprofv3 child passes of this script")
-    ap.add_argument("--legs", type=int, default=1, help="after the headline, short legs over the other BASELINE.json configurations (`configs` in the line)")
-    return ap.parse_args(argv)
+    ap.add_argument("--pmc", type=int, default=None, help="N=1: collect the roofline's PMC counters with rocprofv3 child passes of this script")
+    ap.add_argument("--legs", type=int, default=None, help="after the headline, short legs over the other BASELINE.json configurations (`configs` in the line)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    for name, full_default in (("cpu_seconds", 12.0), ("check", 1), ("extras", 1), ("pmc", 1), ("legs", 1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -496,6 +513,35 @@ class Workload:
         return total
 
 
+def dump_outputs(w, out_dir):
+    """What a caller of the timed path receives from the last step, as float64 .npy files: `x` (the solved values; systems x
+    variables, or for the mixed batch the caller's ragged array restricted to the sampled systems, in order), one
+    `status_<field>` per status field, and `systems` (which of the batch they are).  When the whole batch exceeds DUMP_BYTES
+    the systems are a fixed sample drawn with DUMP_SEED, the same for the same arguments from run to run."""
+    import numpy as np
+
+    torch, E = w.torch, w.E
+    torch.cuda.synchronize(w.dev)
+    fields = E.STATUS_DTYPE.names
+    k = min(w.batch, DUMP_BYTES // (8 * (max(p["n"] for p in w.parts) + len(fields) + 1)))
+    systems = np.arange(w.batch) if k == w.batch else np.sort(np.random.default_rng(DUMP_SEED).choice(w.batch, k, replace=False))
+    idx = torch.from_numpy(systems).to(w.dev)
+    if w.mixed is None:
+        x, status = w.parts[0]["x_out"][idx], w.parts[0]["status"][idx]
+    else:
+        starts = w.mixed.offsets[systems].astype(np.int64)
+        n_of = w.mixed.offsets[systems + 1].astype(np.int64) - starts
+        # the values of system i are ragged[starts[i] : starts[i] + n_of[i]]: every position of the sampled systems, in order
+        pos = np.repeat(starts - (np.cumsum(n_of) - n_of), n_of) + np.arange(int(n_of.sum()))
+        x, status = w.x_ragged[torch.from_numpy(pos).to(w.dev)], w.status_all[idx]
+    st = status.cpu().numpy().view(E.STATUS_DTYPE).reshape(-1)
+    arrays = {"x": x.cpu().numpy(), "systems": systems}
+    arrays.update({"status_" + f: st[f] for f in fields})
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run_leg(E, torch, dist, args, name, batch, world, rank, device_index, dev, backend, n_cus, team=0):
     """One short leg over another BASELINE configuration: steady-state warm-up, a few timed launches bracketed like the
     headline's (barrier + synchronize, max over ranks), iterations, oracle check, roofs (hbm always; issue from one PMC
@@ -684,6 +730,12 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
     if os.environ.get("EZPZ_BENCH_DRY") == "1":
         sys.exit(dry_run(args, world, rank))
+    # what is measured is the library build() made, loaded as it is: the build step (and its lock file in the tree) runs only for a
+    # library older than its sources -- the tree may be read-only to this user, and may be another commit's build of the project
+    from ezpz_amd import build as B
+
+    if not B.stale():
+        os.environ.setdefault("EZPZ_AMD_NO_BUILD", "1")
 
     import numpy as np
     import torch
@@ -745,6 +797,8 @@ def main():
         dist.all_reduce(t[:2], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[2:], op=dist.ReduceOp.SUM)
         elapsed, kernel_ms, world_seen = float(t[0]), float(t[1]), int(round(float(t[2])))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)
 
     extras = {}
     value_h2h = None

@@ -65,6 +65,21 @@ def test_gpus_must_match_world_size():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
 
 
+def test_plain_run_leaves_everything_beyond_the_headline_to_full():
+    """A plain run sets up, warms up, times its steps and prints the line; --full turns on the oracle check, the extras, the PMC
+    passes, the legs and the CPU baseline, and an explicit value of any of them wins either way."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    plain, full = bench.parse_args(["--steps", "7"]), bench.parse_args(["--full"])
+    assert plain.steps == 7 and not plain.full and plain.dump_outputs is None
+    assert (plain.cpu_seconds, plain.check, plain.extras, plain.pmc, plain.legs) == (0, 0, 0, 0, 0)
+    assert (full.cpu_seconds, full.check, full.extras, full.pmc, full.legs) == (12.0, 1, 1, 1, 1)
+    mixed = bench.parse_args(["--full", "--legs", "0", "--dump-outputs", "out"])
+    assert mixed.legs == 0 and mixed.check == 1 and mixed.dump_outputs == "out"
+    assert bench.parse_args(["--check", "1"]).check == 1
+
+
 def test_workload_builders_match_the_oracle_loader():
     """bench.py builds its workloads with the product's front end; same records / guesses as the oracle's loader."""
     sys.path.insert(0, ROOT)

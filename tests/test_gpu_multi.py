@@ -256,7 +256,7 @@ def test_bench_takes_its_multi_gpu_branches_with_rccl_at_world_size_one(E):
     env = dict(os.environ, EZPZ_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29900 + os.getpid() % 90), HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "2048",
-                        "--cpu-seconds", "0", "--pmc", "0", "--legs", "0"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-seconds", "0", "--pmc", "0", "--legs", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -1,6 +1,6 @@
 # A/B runs of the class-specialised kernels' switches on the GPU box (bench.py lines, no PMC): usage bash tools/ab_fastdiv.sh
 # (parity of every variant is checked by the bench line itself: results_ok + bitwise_equal against the oracle)
-B="--extras 0 --cpu-seconds 0 --pmc 0 --steps 200 --warmup 30"
+B="--full --extras 0 --cpu-seconds 0 --pmc 0 --steps 200 --warmup 30"
 run() { # name, env..., args
   name=$1; shift
   env "$@" > gpurun_out/ab_$name.json 2> gpurun_out/ab_$name.err

@@ -1,5 +1,5 @@
 # A/B runs of the lanes-across-the-batch kernel's launch parameters (bench.py lines, no PMC): bash tools/ab_lanes.sh
-B="--extras 0 --cpu-seconds 0 --pmc 0 --legs 0 --workload sketch150 --warmup 1"
+B="--full --extras 0 --cpu-seconds 0 --pmc 0 --legs 0 --workload sketch150 --warmup 1"
 run() { name=$1; shift
   env "$@" > gpurun_out/abl_$name.json 2> gpurun_out/abl_$name.err
   python - <<PY

@@ -5,36 +5,36 @@
 out=$1; mkdir -p $out
 # (the interpreter itself after `--`: a python3 shim that exec()s the real one would be an exec hop under the profiler)
 PY=$(python -c 'import os,sys;print(os.path.realpath(sys.executable))')
-python bench.py --steps 20 --warmup 5 > $out/bench_massive.json 2>/dev/null   # the driver's invocation: headline + legs over every BASELINE config
-EZPZ_JIT=0 python bench.py --specialize 0 --legs 0 > $out/bench_massive_interpreter.json 2>/dev/null   # (EZPZ_JIT=0: with the on-disk cache a kernel compiled earlier would be picked up)
-EZPZ_JIT=0 EZPZ_COMP=0 python bench.py --specialize 0 --legs 0 > $out/bench_massive_listwalk.json 2>/dev/null
-EZPZ_JIT_FASTDIV=0 python bench.py --legs 0 --cpu-seconds 0 --extras 0 > $out/bench_massive_plain_divisions.json 2>/dev/null
-python bench.py --batch 4096 --pmc 0 --cpu-seconds 0 --extras 0 --legs 0 > $out/bench_massive_b4096.json 2>/dev/null
-python bench.py --batch 16384 --pmc 0 --cpu-seconds 0 --extras 0 --legs 0 > $out/bench_massive_b16384.json 2>/dev/null   # (rounds 2-3 quoted this batch)
-python bench.py --workload massive600 --legs 0 > $out/bench_massive600.json 2>/dev/null   # (round 5: with the PMC roofs)
-python bench.py --workload massive200 > $out/bench_massive200.json 2>/dev/null
-python bench.py --workload massive500o --legs 0 > $out/bench_massive500_overconstrained.json 2>/dev/null
-python bench.py --workload square --batch 65536 > $out/bench_square.json 2>/dev/null
-python bench.py --workload mixed --batch 1000000 --steps 20 > $out/bench_mixed_1M.json 2>/dev/null
-python bench.py --workload massive50000 --batch 64 --steps 20 > $out/bench_ladder200k.json 2>/dev/null
-python bench.py --workload sketch150 --batch 262144 --steps 10 --warmup 2 > $out/bench_sketch_300vars_b262144.json 2>/dev/null
-python bench.py --workload sketch150 --batch 32768 --steps 10 --warmup 2 > $out/bench_sketch_300vars_b32768.json 2>/dev/null   # (below the lanes' batch: the teams' record walk)
+python bench.py --full --steps 20 --warmup 5 > $out/bench_massive.json 2>/dev/null   # the driver's invocation: headline + legs over every BASELINE config
+EZPZ_JIT=0 python bench.py --full --specialize 0 --legs 0 > $out/bench_massive_interpreter.json 2>/dev/null   # (EZPZ_JIT=0: with the on-disk cache a kernel compiled earlier would be picked up)
+EZPZ_JIT=0 EZPZ_COMP=0 python bench.py --full --specialize 0 --legs 0 > $out/bench_massive_listwalk.json 2>/dev/null
+EZPZ_JIT_FASTDIV=0 python bench.py --full --legs 0 --cpu-seconds 0 --extras 0 > $out/bench_massive_plain_divisions.json 2>/dev/null
+python bench.py --full --batch 4096 --pmc 0 --cpu-seconds 0 --extras 0 --legs 0 > $out/bench_massive_b4096.json 2>/dev/null
+python bench.py --full --batch 16384 --pmc 0 --cpu-seconds 0 --extras 0 --legs 0 > $out/bench_massive_b16384.json 2>/dev/null   # (rounds 2-3 quoted this batch)
+python bench.py --full --workload massive600 --legs 0 > $out/bench_massive600.json 2>/dev/null   # (round 5: with the PMC roofs)
+python bench.py --full --workload massive200 > $out/bench_massive200.json 2>/dev/null
+python bench.py --full --workload massive500o --legs 0 > $out/bench_massive500_overconstrained.json 2>/dev/null
+python bench.py --full --workload square --batch 65536 > $out/bench_square.json 2>/dev/null
+python bench.py --full --workload mixed --batch 1000000 --steps 20 > $out/bench_mixed_1M.json 2>/dev/null
+python bench.py --full --workload massive50000 --batch 64 --steps 20 > $out/bench_ladder200k.json 2>/dev/null
+python bench.py --full --workload sketch150 --batch 262144 --steps 10 --warmup 2 > $out/bench_sketch_300vars_b262144.json 2>/dev/null
+python bench.py --full --workload sketch150 --batch 32768 --steps 10 --warmup 2 > $out/bench_sketch_300vars_b32768.json 2>/dev/null   # (below the lanes' batch: the teams' record walk)
 # round 5: ONE solve of a large connected sketch (2000 / 5000 variables) on the frontal shape (0xFFFFFFFF = the automatic latency shape),
 # with the PMC roofs of the CUs it runs on, and the same solve on round 4's record walk (0xFFFFFFF9)
-python bench.py --workload sketch1000 --batch 1 --team 0xFFFFFFFF --max-iterations 60 --legs 0 --steps 50 --warmup 5 --cpu-seconds 6 > $out/bench_sketch2000_one_solve.json 2>/dev/null
-python bench.py --workload sketch2500 --batch 1 --team 0xFFFFFFFF --max-iterations 60 --legs 0 --steps 20 --warmup 3 --cpu-seconds 6 > $out/bench_sketch5000_one_solve.json 2>/dev/null
-python bench.py --workload sketch1000 --batch 1 --team 0xFFFFFFF9 --max-iterations 60 --legs 0 --steps 20 --warmup 3 --cpu-seconds 0 > $out/bench_sketch2000_one_solve_records.json 2>/dev/null
-python bench.py --workload sketch2500 --batch 1 --team 0xFFFFFFF9 --max-iterations 60 --legs 0 --steps 5 --warmup 2 --cpu-seconds 0 > $out/bench_sketch5000_one_solve_records.json 2>/dev/null
+python bench.py --full --workload sketch1000 --batch 1 --team 0xFFFFFFFF --max-iterations 60 --legs 0 --steps 50 --warmup 5 --cpu-seconds 6 > $out/bench_sketch2000_one_solve.json 2>/dev/null
+python bench.py --full --workload sketch2500 --batch 1 --team 0xFFFFFFFF --max-iterations 60 --legs 0 --steps 20 --warmup 3 --cpu-seconds 6 > $out/bench_sketch5000_one_solve.json 2>/dev/null
+python bench.py --full --workload sketch1000 --batch 1 --team 0xFFFFFFF9 --max-iterations 60 --legs 0 --steps 20 --warmup 3 --cpu-seconds 0 > $out/bench_sketch2000_one_solve_records.json 2>/dev/null
+python bench.py --full --workload sketch2500 --batch 1 --team 0xFFFFFFF9 --max-iterations 60 --legs 0 --steps 5 --warmup 2 --cpu-seconds 0 > $out/bench_sketch5000_one_solve_records.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_m -- $PY bench.py --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_m -- $PY bench.py --full --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 > /dev/null 2>&1
 find $out/stats_m -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/massive_b65536_kernel_stats.csv; rm -rf $out/stats_m
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_s -- $PY bench.py --workload square --batch 65536 --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_s -- $PY bench.py --full --workload square --batch 65536 --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 > /dev/null 2>&1
 find $out/stats_s -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/square_b65536_kernel_stats.csv; rm -rf $out/stats_s
 for w in "mixed 1048576 mixed_1M" "massive50000 64 ladder200k" "sketch150 262144 sketch_300vars_b262144" "sketch150 32768 sketch_300vars_b32768"; do set -- $w
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_x -- $PY bench.py --workload $1 --batch $2 --steps 10 --warmup 2 --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_x -- $PY bench.py --full --workload $1 --batch $2 --steps 10 --warmup 2 --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 > /dev/null 2>&1
 find $out/stats_x -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/$3_kernel_stats.csv; rm -rf $out/stats_x; done
 for w in "sketch1000 sketch2000_one_solve" "sketch2500 sketch5000_one_solve"; do set -- $w
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_x -- $PY bench.py --workload $1 --batch 1 --team 0xFFFFFFFF --max-iterations 60 --steps 20 --warmup 3 --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 --check 0 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_x -- $PY bench.py --full --workload $1 --batch 1 --team 0xFFFFFFFF --max-iterations 60 --steps 20 --warmup 3 --cpu-seconds 0 --extras 0 --pmc 0 --legs 0 --check 0 > /dev/null 2>&1
 find $out/stats_x -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/$2_kernel_stats.csv; rm -rf $out/stats_x; done
 # (twice: the first process of a box compiles the small systems' kernels in the background while it times them; the second finds them in the on-disk cache)
 python tools/reference_benches.py > $out/reference_benches_first_process.txt 2>/dev/null
@@ -67,7 +67,7 @@ hipcc --offload-arch=gfx950 -O2 -o tools/pcie_duplex.bin tools/pcie_duplex.hip 2
 (echo "# python tools/freedom_wide.py 150 400 850 1000  (FreedomAnalysis of one large connected component: null-space probes on the frontal factorisation -- round 5, no QR --, then EZPZ_FREEDOM_PROBES=0: the pivoted QR with the matrix resident in registers, then on top EZPZ_FREEDOM_CHAIN=2: one cooperative launch streaming the trailing matrix, then EZPZ_FREEDOM_CHAIN=1: round 3's chain of a launch pair per Householder step)"; python tools/freedom_wide.py 150 400 850 1000 2500 2>&1 | grep variables; EZPZ_FREEDOM_PROBES=0 python tools/freedom_wide.py 150 400 850 1000 2>&1 | grep variables; EZPZ_FREEDOM_PROBES=0 EZPZ_FREEDOM_CHAIN=2 python tools/freedom_wide.py 150 400 850 1000 2>&1 | grep variables; EZPZ_FREEDOM_PROBES=0 EZPZ_FREEDOM_CHAIN=1 python tools/freedom_wide.py 150 400 850 1000 2>&1 | grep variables) > $out/freedom_wide.txt
 # round 5: who solves which system -- the headline with drawn systems against fixed shares (same build), small calls of batch systems, and
 # what a resident one-call kernel costs a batch on another stream (with the residency switched off as the control)
-(echo "# EZPZ_TICKETS=<0|1> python bench.py --steps 20 --warmup 5 --legs 0 --cpu-seconds 0 --extras 0 --pmc 0  (0 = fixed shares of the batch per workgroup, 1 = the default: workgroups draw their systems from eight counters)"; for t in 0 1 0 1; do EZPZ_TICKETS=$t python bench.py --steps 20 --warmup 5 --legs 0 --cpu-seconds 0 --extras 0 --pmc 0 2>/dev/null | $PY -c "import json,sys; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('EZPZ_TICKETS=$t:', round(l['value']/1e6,2), 'M solves/s,', round(l['ms_per_step'],4), 'ms per launch of', l['config']['systems_per_launch_per_gpu'], 'systems; oracle check', l['oracle_check']['bitwise_equal'])"; done) > $out/tickets_ab.txt
+(echo "# EZPZ_TICKETS=<0|1> python bench.py --full --steps 20 --warmup 5 --legs 0 --cpu-seconds 0 --extras 0 --pmc 0  (0 = fixed shares of the batch per workgroup, 1 = the default: workgroups draw their systems from eight counters)"; for t in 0 1 0 1; do EZPZ_TICKETS=$t python bench.py --full --steps 20 --warmup 5 --legs 0 --cpu-seconds 0 --extras 0 --pmc 0 2>/dev/null | $PY -c "import json,sys; l=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('EZPZ_TICKETS=$t:', round(l['value']/1e6,2), 'M solves/s,', round(l['ms_per_step'],4), 'ms per launch of', l['config']['systems_per_launch_per_gpu'], 'systems; oracle check', l['oracle_check']['bitwise_equal'])"; done) > $out/tickets_ab.txt
 (echo "# python tools/small_calls.py; BATCHES=1,8,24,42,54,55,64 python tools/small_calls.py 400 1000 2500"; python tools/small_calls.py 2>&1 | grep -v amdgpu.ids; BATCHES=1,8,24,42,54,55,64 python tools/small_calls.py 400 1000 2500 2>&1 | grep -v amdgpu.ids) > $out/small_calls.txt
 (echo "# python tools/graph_families.py  (the graph families and seeds of tests/test_gpu_fuzz.py, one solve: the automatic latency shape against the record walk)"; python tools/graph_families.py 2>&1 | grep -v amdgpu.ids) > $out/graph_families.txt
 (python tools/resident_cost.py 2>&1 | grep -v amdgpu.ids) > $out/resident_cost.txt
