@@ -130,9 +130,6 @@ struct CompLaunch {
     // lane-per-system kernel only: the systems of one topology inside a ragged batch, in place (jit_kernel.hip.hpp: LaneArgs)
     const uint64_t* row_offset = nullptr;
     const uint32_t* sys_of = nullptr;
-    // the specialised kernels' work counters (jit_kernel.hip.hpp: JitArgs::ticket) and where each of the eight stands
-    unsigned int* ticket = nullptr;
-    const unsigned int* ticket_base = nullptr;
 };
 int comp_launch(const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch& launch, int device, int cus,
                 size_t lds_limit, void* stream);
@@ -182,18 +179,24 @@ void comp_jit_destroy(CompJit* jit);
 int comp_jit_request(CompJit* jit, bool wait);
 int comp_jit_state(const CompJit* jit);
 const char* comp_jit_log(const CompJit* jit);
-// (a system on several workgroups: `grid_slots` systems in flight on `grid_scratch`; fast_slots / redo: the same for the kernel
-// that does not wait for its verdicts, and the device list -- 1 + batch words, count zero -- of the systems it leaves to the loop;
-// redo_next: the list of the system's next call, whose count this call zeroes; redo_seen_dev / _host: a word of mapped host memory
-// the loop's launch leaves its count in, the hint for the width of the next one.  0 / null: the loop alone)
-int comp_jit_launch(CompJit* jit, const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch& launch, int device, int cus, void* stream,
-                    void* grid_scratch = nullptr, uint32_t grid_slots = 0, uint32_t fast_slots = 0, unsigned int* redo = nullptr,
-                    unsigned int* redo_next = nullptr, unsigned int* redo_seen_dev = nullptr, const unsigned int* redo_seen_host = nullptr);
+// What one comp_jit_launch enqueued, kernel by kernel: whether it went out, on how many workgroups, and whether they drew their
+// systems from the counters (JitLaunchState::commit keeps the totals from this and from nothing else).
+struct JitEnqueued {
+    struct Kernel { bool ran = false; uint32_t wgs = 0; bool tickets = false; };
+    int rc = EZPZ_OK;
+    Kernel fast, loop;  // the `_fast` entry; the loop, or `_list` behind `_fast`
+};
+struct JitLaunchState;
+// `shared`: the state the system's launches share (system.hpp), the scratch of a system on several workgroups (`grid_slots` systems in
+// flight) among it.  fast_slots: the same for the kernel that does not wait for its verdicts, which then goes first and lists what it
+// leaves to the loop on the redo list of the turn (the caller has made the lists: JitLaunchState::redo_lists).  0: the loop alone.
+JitEnqueued comp_jit_launch(CompJit* jit, const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch& launch, int device, int cus,
+                            void* stream, JitLaunchState& shared, uint32_t grid_slots = 0, uint32_t fast_slots = 0);
 // workgroups of the specialised kernel the device holds at once (loads the code object on first use); 0 on failure
 uint64_t comp_jit_capacity(CompJit* jit, const CompPlan& plan, int device, int cus);
 // ... of its `_fast` entry (0: the kernel has none)
 uint64_t comp_jit_capacity_fast(CompJit* jit, const CompPlan& plan, int device, int cus);
-// whether this launch may take the `_fast` entry (then: fast_slots, redo, redo_next to comp_jit_launch)
+// whether this launch may take the `_fast` entry (then: fast_slots to comp_jit_launch)
 bool comp_jit_fast_ok(CompJit* jit, const CompPlan& plan, const CompLaunch& launch, int device, int cus);
 // (through the on-disk cache of code objects; _uncached always compiles; comp_jit_cached: is it in the cache?)
 int comp_jit_compile(const std::string& source, std::vector<char>& code, std::string& log);

@@ -8,9 +8,6 @@ using namespace ezpz;
 
 namespace ezpz {
 
-extern std::mutex g_grid_mu;          // launch.hip: launches whose workgroups wait for each other are chained per device
-extern hipEvent_t g_grid_event[16];
-
 // What a probe launch adds to a solve launch (FrontArgs::probe_*).
 struct FrontProbe {
     uint32_t m = 0;
@@ -49,22 +46,14 @@ static int front_launch_kernel(EzpzSystem& s, FrontArgs& fa, hipStream_t stream)
     fa.scratch = s.front_scratch.p;
     fa.scratch_stride = stride;
     fa.done.request = nullptr;
-    // every workgroup of the launch must become resident: slots x G never exceeds what the device holds, and launches of
-    // this kind are chained on one event per device (launch.hip: launch_grid_kernel)
-    std::lock_guard<std::mutex> lock(g_grid_mu);
-    hipEvent_t& ev = g_grid_event[s.device & 15];
-    if (!ev)
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
-    // (per LM iteration a factorisation's hops up and down the tree and the reductions of the LM control -- at most a few per level;
+    // (slots x G never exceeds what the device holds: launch_resident.  Per LM iteration a factorisation's hops up and down the tree and the reductions of the LM control -- at most a few per level;
     // the sequence numbers of the scratch start again before they wrap: system.hpp)
-    if (seq_budget_spent(s.front_seq_used, fa.batch, 16ull * ((uint64_t)fa.max_iterations + 4) * std::max<uint32_t>(1, plan.n_levels)))
-        HIP_TRY(hipMemsetAsync(s.front_scratch.p, 0, s.front_scratch.cap, stream));
-    hipLaunchKernelGGL(kernel, dim3(slots * G), dim3(plan.threads), plan.lds_bytes, stream, fa);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev, stream));
-    return EZPZ_OK;
+    return launch_resident(s.device, stream, s.front_scratch.p, s.front_scratch.cap, s.front_seq_used, fa.batch,
+                           16ull * ((uint64_t)fa.max_iterations + 4) * std::max<uint32_t>(1, plan.n_levels), [&] {
+                               hipLaunchKernelGGL(kernel, dim3(slots * G), dim3(plan.threads), plan.lds_bytes, stream, fa);
+                               HIP_TRY(hipGetLastError());
+                               return EZPZ_OK;
+                           });
 }
 
 static int front_launch_with(EzpzSystem& s, SolveArgs& args, hipStream_t stream, const FrontProbe& probe) {

@@ -44,23 +44,131 @@ int launch_sub(EzpzSystem& s, const SolveArgs& args, uint32_t grid, hipStream_t 
                          : launch_variant<TEAM, MODE_SUB, true, false>(s, args, grid, stream);
 }
 
+std::mutex g_grid_mu;
+hipEvent_t g_grid_event[16] = {};  // per device: completion of the last launch of this process whose workgroups wait for each other
+
+bool stream_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        capturing = hipStreamCaptureStatusNone;
+    }
+    return capturing != hipStreamCaptureStatusNone;
+}
+
+// The system's workspace in global memory -- the lanes kernel's, the list walk's when its workspace or its Jacobian lives there -- is
+// one per system object: `launch` runs behind the last launch that used it, whatever stream that was, and leaves its own completion
+// behind when it succeeds.
+template <class Launch>
+int on_workspace(EzpzSystem& s, hipStream_t stream, Launch&& launch) {
+    HIP_TRY(s.lanes_done ? hipStreamWaitEvent(stream, s.lanes_done, 0) : hipEventCreateWithFlags(&s.lanes_done, hipEventDisableTiming));
+    const int rc = launch();
+    if (rc == EZPZ_OK) HIP_TRY(hipEventRecord(s.lanes_done, stream));
+    return rc;
+}
+
 }  // namespace
 namespace ezpz {
 thread_local uint64_t t_call_batch = 0;
-std::mutex g_grid_mu;
-hipEvent_t g_grid_event[16] = {};  // per device: completion of the last grid-team launch of this process (front.hip's too)
+
+// Every workgroup of the launch must become resident (they wait for each other).  The launch never asks for more than the device
+// holds, and such launches of this process are chained on one event per device, so two of them are never half-resident at the same
+// time whatever streams they were enqueued on; other kernels only delay residency.  (hipLaunchCooperativeKernel gives the same
+// guarantee across processes but costs 21 us per launch, more than a third of a 200 000-variable solve; another process running
+// them on the same device at the same time is not supported.)
+int launch_resident(int device, hipStream_t stream, void* scratch, size_t scratch_bytes, uint64_t& seq_used, uint64_t batch,
+                    uint64_t exchanges_per_system, const std::function<int()>& launch) {
+    std::lock_guard<std::mutex> lock(g_grid_mu);
+    hipEvent_t& ev = g_grid_event[device & 15];
+    HIP_TRY(ev ? hipStreamWaitEvent(stream, ev, 0) : hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (seq_budget_spent(seq_used, batch, exchanges_per_system)) HIP_TRY(hipMemsetAsync(scratch, 0, scratch_bytes, stream));
+    const int rc = launch();
+    if (rc != EZPZ_OK) return rc;
+    HIP_TRY(hipEventRecord(ev, stream));
+    return EZPZ_OK;
+}
+
+// Launches of one system that share device state -- the counters its workgroups draw their systems from, the redo lists of its
+// `_fast` entry, whose count a call's last launch zeroes for the NEXT call -- run one after the other whatever streams they are
+// enqueued on: a launch on another stream than the last one waits for everything enqueued there.  (An event per launch instead cost the
+// back-to-back launches of one stream two runtime calls and a barrier packet each.)
+bool JitLaunchState::chain(hipStream_t on) {
+    bool ok = true;
+    if (!done) ok = hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess;
+    if (ok && used && stream != on) {
+        ok = hipEventRecord(done, stream) == hipSuccess && hipStreamWaitEvent(on, done, 0) == hipSuccess;
+        if (!ok) {  // (the old stream is gone: whatever ran on it is awaited the blunt way)
+            (void)hipGetLastError();
+            ok = hipDeviceSynchronize() == hipSuccess;
+        }
+    }
+    if (!ok) (void)hipGetLastError();
+    return ok;
+}
+
+bool JitLaunchState::tickets(hipStream_t on) {
+    // (a launch that is being recorded into a graph keeps fixed shares: a replay would find the counters elsewhere)
+    if (stream_capturing(on)) return false;
+    bool ok = ticket.p != nullptr;
+    if (!ok && ticket.ensure(8 * 1024) == EZPZ_OK) {  // (jit_kernel.hip.hpp: kTicketStride words apart)
+        ok = hipMemset(ticket.p, 0, 8 * 1024 * sizeof(unsigned int)) == hipSuccess;
+        for (unsigned int& b : ticket_base) b = 0;
+    }
+    ok = ok && chain(on);
+    if (!ok) (void)hipGetLastError();
+    return ok;
+}
+
+int JitLaunchState::redo_lists(uint64_t batch, hipStream_t on) {
+    for (auto& list : redo)
+        if (list.cap < batch + 1) {
+            int rc = list.ensure(batch + 1);  // (synchronises the device: nobody reads the old one any more)
+            if (rc != EZPZ_OK) return rc;
+            HIP_TRY(hipMemsetAsync(list.p, 0, sizeof(unsigned int), on));
+        }
+    if (!redo_seen) {
+        HIP_TRY(hipHostMalloc((void**)&redo_seen, sizeof(unsigned int), hipHostMallocMapped));
+        *redo_seen = 0;
+        HIP_TRY(hipHostGetDevicePointer((void**)&redo_seen_dev, redo_seen, 0));
+    }
+    return EZPZ_OK;
+}
+
+void JitLaunchState::commit(const JitEnqueued& e, uint64_t batch, hipStream_t on) {
+    // What a kernel of `wgs` workgroups over `batch` systems has drawn from each counter: counter c hands out its share of the systems
+    // beyond the workgroups' own, and `in_vain` values more to each of its workgroups (the loop draws once per system it solves, the
+    // last time in vain; `_fast` asks for its guesses a system ahead: twice in vain)
+    auto advance = [&](const JitEnqueued::Kernel& k, unsigned int in_vain) {
+        if (!k.tickets) return;
+        for (uint64_t c = 0; c < 8; ++c) {
+            const uint64_t wgs_c = (k.wgs + 7 - c) / 8, beyond = batch - k.wgs;
+            ticket_base[c] += (unsigned int)(in_vain * wgs_c + (beyond > c ? (beyond - c + 7) / 8 : 0));
+        }
+    };
+    advance(e.fast, 2);
+    advance(e.loop, 1);
+    if (e.fast.ran) turn ^= 1u;  // (the next call's list is the one this call's loop has zeroed)
+    if (e.fast.ran || e.loop.tickets) stream = on, used = true;
+}
+
+int JitLaunchState::resync(hipStream_t on) {
+    if (ticket.p) HIP_TRY(hipMemsetAsync(ticket.p, 0, ticket.cap * sizeof(unsigned int), on));
+    for (auto& list : redo)
+        if (list.p) HIP_TRY(hipMemsetAsync(list.p, 0, sizeof(unsigned int), on));
+    for (unsigned int& b : ticket_base) b = 0;
+    turn = 0;
+    stream = on, used = true;  // (a launch on another stream waits for the zeroing: chain)
+    return EZPZ_OK;
+}
+
 }  // namespace ezpz
 namespace {
 
 // Grid team: G workgroups per system, all of a launch's workgroups resident at once, as many systems in flight as
 // the device holds.
-bool stream_capturing(hipStream_t stream);
-
 template <bool LIN>
 int launch_grid_kernel(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
-    // (launches whose workgroups wait for each other are chained on a process-wide event and zero their scratch on first use: neither
-    // may end up inside a stream capture, which would be invalidated and leave the event unusable -- refused up front)
-    if (stream_capturing(stream)) return EZPZ_ERR_INVALID_ARGUMENT;
+    if (stream_capturing(stream)) return EZPZ_ERR_INVALID_ARGUMENT;  // (launch_resident)
     auto kernel = lm_solve_kernel<64, MODE_PART, true, true, LIN, true>;
     if (s.grid_capacity == 0) {  // once per system: these two runtime calls cost more than the solve
         if (s.lds_bytes > 48 * 1024)
@@ -92,111 +200,33 @@ int launch_grid_kernel(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
     args.grid_scratch = s.grid_scratch.p;
     args.grid_views = s.grid_views.p;
     args.grid_wgs = s.grid_wgs;
-    // Every workgroup of the launch must become resident (they wait for each other).  slots * G never exceeds what
-    // the device holds, and grid-team launches of this process are chained on one event per device, so two of them
-    // are never half-resident at the same time whatever streams they were enqueued on; other kernels only delay
-    // residency.  (hipLaunchCooperativeKernel gives the same guarantee across processes but costs 21 us per launch,
-    // more than a third of a 200 000-variable solve; another process running grid teams on the same device at the
-    // same time is not supported.)
-    {
-        std::lock_guard<std::mutex> lock(g_grid_mu);
-        hipEvent_t& ev = g_grid_event[s.device & 15];
-        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
-        // (three exchanges per LM iteration and a few around them; the sequence numbers start again before they wrap: system.hpp)
-        if (seq_budget_spent(s.grid_seq_used, args.batch, 3ull * ((uint64_t)args.max_iterations + 4)))
-            HIP_TRY(hipMemsetAsync(s.grid_scratch.p, 0, s.grid_scratch.cap * sizeof(GridScratch), stream));
-        hipLaunchKernelGGL(kernel, dim3(slots * s.grid_wgs), dim3(s.block_threads), s.lds_bytes, stream, args);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev, stream));
-    }
-    return EZPZ_OK;
+    // (three exchanges per LM iteration and a few around them; the sequence numbers start again before they wrap: system.hpp)
+    return launch_resident(s.device, stream, s.grid_scratch.p, s.grid_scratch.cap * sizeof(GridScratch), s.grid_seq_used, args.batch,
+                           3ull * ((uint64_t)args.max_iterations + 4), [&] {
+                               hipLaunchKernelGGL(kernel, dim3(slots * s.grid_wgs), dim3(s.block_threads), s.lds_bytes, stream, args);
+                               HIP_TRY(hipGetLastError());
+                               return EZPZ_OK;
+                           });
 }
 
-int launch_grid_team(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
-    return s.linear_only ? launch_grid_kernel<true>(s, args, stream) : launch_grid_kernel<false>(s, args, stream);
-}
-
-// (a launch that is being recorded into a graph never takes the `_fast` entry: its redo list is zeroed by the NEXT call's launches,
-// which a replay does not run)
-bool stream_capturing(hipStream_t stream) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
-        (void)hipGetLastError();
-        capturing = hipStreamCaptureStatusNone;
-    }
-    return capturing != hipStreamCaptureStatusNone;
-}
-
-// Launches of one system that share device state between them -- the counters its workgroups draw their systems from, the redo lists of
-// its `_fast` entry, whose count a call's last launch zeroes for the NEXT call -- run one after the other whatever streams they are
-// enqueued on: a launch on another stream than the last one waits for everything enqueued there.  (An event per launch instead cost the
-// back-to-back launches of one stream two runtime calls and a barrier packet each.)  False: could not be arranged.
-bool chain_launches(EzpzSystem& s, hipStream_t stream) {
-    bool ok = true;
-    if (!s.ticket_done) ok = hipEventCreateWithFlags(&s.ticket_done, hipEventDisableTiming) == hipSuccess;
-    if (ok && s.ticket_used && s.ticket_stream != stream) {
-        ok = hipEventRecord(s.ticket_done, s.ticket_stream) == hipSuccess && hipStreamWaitEvent(stream, s.ticket_done, 0) == hipSuccess;
-        if (!ok) {  // (the old stream is gone: whatever ran on it is awaited the blunt way)
-            (void)hipGetLastError();
-            ok = hipDeviceSynchronize() == hipSuccess;
-        }
-    }
-    if (!ok) (void)hipGetLastError();
-    return ok;
-}
-// The counters a specialised kernel's workgroups draw their systems from (jit_kernel.hip.hpp: JitArgs::ticket), for a launch on
-// `stream`: created on first use; launches that share them are chained.  False: the launch keeps fixed shares.
-bool prepare_tickets(EzpzSystem& s, hipStream_t stream) {
-    static const bool tickets_enabled = [] {  // EZPZ_TICKETS=0: fixed shares (A/B runs: 101.1 -> 110.0 M solves/s with them)
-        const char* e = std::getenv("EZPZ_TICKETS");
-        return !(e && e[0] == '0');
-    }();
-    // (a launch that is being recorded into a graph keeps fixed shares: a replay would find the counters elsewhere)
-    if (!tickets_enabled || stream_capturing(stream)) return false;
-    bool ok = s.ticket.p != nullptr;
-    if (!ok && s.ticket.ensure(8 * 1024) == EZPZ_OK) {  // (jit_kernel.hip.hpp: kTicketStride words apart)
-        ok = hipMemset(s.ticket.p, 0, 8 * 1024 * sizeof(unsigned int)) == hipSuccess;
-        for (unsigned int& b : s.ticket_base) b = 0;
-    }
-    ok = ok && chain_launches(s, stream);
-    if (!ok) (void)hipGetLastError();
-    return ok;
-}
-// ... and what a launch of `workgroups` workgroups over `batch` systems has drawn from each: counter c hands out its share of the
-// systems beyond the workgroups' own, and `in_vain` values more to each of its workgroups (the loop kernel draws once per system
-// it solves, the last time in vain; the kernel that asks for its guesses a system ahead draws a system ahead: twice in vain)
-void advance_tickets(EzpzSystem& s, hipStream_t stream, uint64_t workgroups, uint64_t batch, unsigned int in_vain) {
-    for (uint64_t c = 0; c < 8; ++c) {
-        const uint64_t wgs_c = (workgroups + 7 - c) / 8, beyond = batch - workgroups;
-        s.ticket_base[c] += (unsigned int)(in_vain * wgs_c + (beyond > c ? (beyond - c + 7) / 8 : 0));
-    }
-    s.ticket_stream = stream;
-    s.ticket_used = true;
-}
-
-// The two redo lists of a system whose specialised kernel has a `_fast` entry (system.hpp: jit_redo), for `batch` systems, and the
-// mapped word the loop's launch leaves its count in.
-int jit_redo_lists(EzpzSystem& s, uint64_t batch, hipStream_t stream) {
-    for (auto& list : s.jit_redo)
-        if (list.cap < batch + 1) {
-            int rc = list.ensure(batch + 1);  // (synchronises the device: nobody reads the old one any more)
-            if (rc != EZPZ_OK) return rc;
-            HIP_TRY(hipMemsetAsync(list.p, 0, sizeof(unsigned int), stream));
-        }
-    if (!s.jit_redo_seen) {
-        HIP_TRY(hipHostMalloc((void**)&s.jit_redo_seen, sizeof(unsigned int), hipHostMallocMapped));
-        *s.jit_redo_seen = 0;
-        HIP_TRY(hipHostGetDevicePointer((void**)&s.jit_redo_seen_dev, s.jit_redo_seen, 0));
-    }
-    return EZPZ_OK;
+// The specialised kernel of a block system with the state its launches share (JitLaunchState): the host's totals follow what went
+// out.  A call that went out only in part leaves the device's counters and redo counts zeroed behind it, for the fallback and the
+// calls after it.
+int jit_launch(EzpzSystem& s, const CompLaunch& L, hipStream_t stream, uint32_t grid_slots, uint32_t fast_slots) {
+    const JitEnqueued e = comp_jit_launch(s.jit, *s.comp, s.dev_comp, L, s.device, s.lim.cus, stream, s.jit_state, grid_slots, fast_slots);
+    if (e.rc == EZPZ_OK)
+        s.jit_state.commit(e, L.batch, stream);
+    else if ((e.fast.ran || e.loop.ran) && s.jit_state.resync(stream) != EZPZ_OK)
+        return EZPZ_ERR_HIP;
+    return e.rc;
 }
 
 // The class-specialised kernel of a system spread over several workgroups (CompPlan::jit_wgs > 1): as many systems in
-// flight as the device holds whole teams of; every workgroup of the launch must be resident (they wait for each other),
-// so launches of this kind are chained like the list-walk grid teams' (launch_grid_kernel).
-int launch_jit_grid(EzpzSystem& s, const CompLaunch& L, hipStream_t stream) {
-    if (stream_capturing(stream)) return EZPZ_ERR_INVALID_ARGUMENT;  // (as launch_grid_kernel)
+// flight as the device holds whole teams of; every workgroup of the launch must be resident (launch_resident).
+int launch_jit_grid(EzpzSystem& s, CompLaunch L, hipStream_t stream) {
+    if (stream_capturing(stream)) return EZPZ_ERR_INVALID_ARGUMENT;  // (launch_resident)
+    L.done.request = nullptr;  // (several workgroups per system: never resident)
+    JitLaunchState& js = s.jit_state;
     const uint32_t G = s.comp->jit_wgs;
     const uint64_t capacity = comp_jit_capacity(s.jit, *s.comp, s.device, s.lim.cus);
     if (capacity < G) return EZPZ_ERR_TOO_LARGE;
@@ -205,37 +235,22 @@ int launch_jit_grid(EzpzSystem& s, const CompLaunch& L, hipStream_t stream) {
     // loop solves what it lists)
     const uint32_t fast_slots = (uint32_t)(comp_jit_capacity_fast(s.jit, *s.comp, s.device, s.lim.cus) / G);
     const uint32_t most = std::max(slots, fast_slots);
-    if (s.jit_scratch.cap < (size_t)most * kJitGridScratchBytes) {
+    if (js.scratch.cap < (size_t)most * kJitGridScratchBytes) {
         // (sized for the device, not the call: a later, larger call must find the sequence numbers the slots have reached)
         const uint32_t all = (uint32_t)std::max<uint64_t>(most, std::max<uint64_t>(capacity / G, fast_slots));
-        int rc = s.jit_scratch.ensure((size_t)all * kJitGridScratchBytes);
+        int rc = js.scratch.ensure((size_t)all * kJitGridScratchBytes);
         if (rc != EZPZ_OK) return rc;
-        HIP_TRY(hipMemsetAsync(s.jit_scratch.p, 0, s.jit_scratch.cap, stream));
+        HIP_TRY(hipMemsetAsync(js.scratch.p, 0, js.scratch.cap, stream));
     }
     const bool lists = fast_slots && comp_jit_fast_ok(s.jit, *s.comp, L, s.device, s.lim.cus) && !stream_capturing(stream);
     if (lists) {
-        int rc = jit_redo_lists(s, L.batch, stream);
+        int rc = js.redo_lists(L.batch, stream);
         if (rc != EZPZ_OK) return rc;
     }
-    std::lock_guard<std::mutex> lock(g_grid_mu);
-    hipEvent_t& ev = g_grid_event[s.device & 15];
-    if (!ev)
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else
-        HIP_TRY(hipStreamWaitEvent(stream, ev, 0));
     // (the loop's three exchanges per LM iteration, the ring's one per system: the sequence numbers start again before they wrap)
-    if (seq_budget_spent(s.jit_seq_used, L.batch, 3ull * ((uint64_t)L.max_iterations + 4)))
-        HIP_TRY(hipMemsetAsync(s.jit_scratch.p, 0, s.jit_scratch.cap, stream));
-    const unsigned int turn = s.jit_redo_turn;
-    int rc = comp_jit_launch(s.jit, *s.comp, s.dev_comp, L, s.device, s.lim.cus, stream, s.jit_scratch.p, slots, lists ? fast_slots : 0,
-                             lists ? s.jit_redo[turn].p : nullptr, lists ? s.jit_redo[turn ^ 1u].p : nullptr, s.jit_redo_seen_dev,
-                             s.jit_redo_seen);
-    if (lists) s.jit_redo_turn = turn ^ 1u;
-    if (rc != EZPZ_OK) return rc;
-    HIP_TRY(hipEventRecord(ev, stream));
-    return EZPZ_OK;
+    return launch_resident(s.device, stream, js.scratch.p, js.scratch.cap, js.seq_used, L.batch, 3ull * ((uint64_t)L.max_iterations + 4),
+                           [&] { return jit_launch(s, L, stream, slots, lists ? fast_slots : 0); });
 }
-
 
 CompLaunch comp_launch_args(const SolveArgs& args) {
     CompLaunch L{};
@@ -253,7 +268,6 @@ CompLaunch comp_launch_args(const SolveArgs& args) {
     L.done = args.done;
     return L;
 }
-
 
 // The list-walk teams of a system (lm_kernel.hip.hpp), whatever their shape: sub-wavefront teams, workgroups with their
 // workspace in LDS or in global memory, grid teams.  (launch() holds the system's launch lock.)
@@ -279,7 +293,7 @@ int launch_list_walk(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
     if (s.grid_wgs > 1) {
         // (a grid team starts every system from its guesses: its shared warning counter has no resumed value)
         if (args.resume) return EZPZ_ERR_INVALID_ARGUMENT;
-        return launch_grid_team(s, args, stream);
+        return s.linear_only ? launch_grid_kernel<true>(s, args, stream) : launch_grid_kernel<false>(s, args, stream);
     }
     const uint32_t per_cu = s.lds_ws ? (uint32_t)std::max<size_t>(1, s.lim.lds_bytes / std::max<size_t>(s.lds_bytes, 1))
                                      : 2048u / s.block_threads;
@@ -295,191 +309,169 @@ int launch_list_walk(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
     if (s.rec && s.rec_jglobal)  // (a workgroup's Jacobian values in global memory: at most 256 MiB of them per system object)
         grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, (1ull << 25) / ((s.counts.zj + 2) & ~1ull)));
     if (!s.lds_ws) {
+        // the workspace in global memory is one per system object (like the lanes kernel's)
         int rc = s.gws_dev.ensure((size_t)grid * s.ws_doubles);
         if (rc != EZPZ_OK) return rc;
         args.gws = s.gws_dev.p;
+        return on_workspace(s, stream, [&] {
+            return s.mode == MODE_PART ? launch_variant<64, MODE_PART, false, false>(s, args, grid, stream)
+                   : !s.rec            ? launch_variant<64, MODE_WGB, false, false>(s, args, grid, stream)
+                   : s.linear_only     ? launch_kernel<64, MODE_WGB, false, false, true, false, 2>(s, args, grid, stream)
+                                       : launch_kernel<64, MODE_WGB, false, false, false, false, 2>(s, args, grid, stream);
+        });
     }
     const bool staged = s.prog_in_lds;
-    if (!s.lds_ws) {
-        // the workspace in global memory is one per system object: launches on different streams are chained on an event
-        // (like the lanes kernel's), never overlapped
-        if (!s.lanes_done)
-            HIP_TRY(hipEventCreateWithFlags(&s.lanes_done, hipEventDisableTiming));
-        else
-            HIP_TRY(hipStreamWaitEvent(stream, s.lanes_done, 0));
-        const int rc = s.mode == MODE_PART ? launch_variant<64, MODE_PART, false, false>(s, args, grid, stream)
-                       : !s.rec            ? launch_variant<64, MODE_WGB, false, false>(s, args, grid, stream)
-                       : s.linear_only     ? launch_kernel<64, MODE_WGB, false, false, true, false, 2>(s, args, grid, stream)
-                                           : launch_kernel<64, MODE_WGB, false, false, false, false, 2>(s, args, grid, stream);
-        if (rc == EZPZ_OK) HIP_TRY(hipEventRecord(s.lanes_done, stream));
-        return rc;
-    }
     if (s.mode == MODE_PART)
         return staged ? launch_variant<64, MODE_PART, true, true>(s, args, grid, stream)
                       : launch_variant<64, MODE_PART, true, false>(s, args, grid, stream);
-    if (s.rec) {  // one connected system, its linear solve as a record walk
-        if (s.rec_jglobal) {
-            // the Jacobian's values of every workgroup in global memory: one array per system object, launches on different
-            // streams chained on an event (like the other per-system device scratch)
-            const size_t stride = (s.counts.zj + 2) & ~1u;
-            int rc = s.gws_dev.ensure((size_t)grid * stride);
-            if (rc != EZPZ_OK) return rc;
-            args.gws = s.gws_dev.p;
-            if (!s.lanes_done)
-                HIP_TRY(hipEventCreateWithFlags(&s.lanes_done, hipEventDisableTiming));
-            else
-                HIP_TRY(hipStreamWaitEvent(stream, s.lanes_done, 0));
-            rc = s.linear_only ? (staged ? launch_kernel<64, MODE_WGB, true, true, true, false, 1>(s, args, grid, stream)
-                                         : launch_kernel<64, MODE_WGB, true, false, true, false, 1>(s, args, grid, stream))
-                               : (staged ? launch_kernel<64, MODE_WGB, true, true, false, false, 1>(s, args, grid, stream)
-                                         : launch_kernel<64, MODE_WGB, true, false, false, false, 1>(s, args, grid, stream));
-            if (rc == EZPZ_OK) HIP_TRY(hipEventRecord(s.lanes_done, stream));
-            return rc;
-        }
+    if (!s.rec)
+        return staged ? launch_variant<64, MODE_WGB, true, true>(s, args, grid, stream)
+                      : launch_variant<64, MODE_WGB, true, false>(s, args, grid, stream);
+    // one connected system, its linear solve as a record walk
+    auto walk = [&] {
         if (s.linear_only)
             return staged ? launch_kernel<64, MODE_WGB, true, true, true, false, 1>(s, args, grid, stream)
                           : launch_kernel<64, MODE_WGB, true, false, true, false, 1>(s, args, grid, stream);
         return staged ? launch_kernel<64, MODE_WGB, true, true, false, false, 1>(s, args, grid, stream)
                       : launch_kernel<64, MODE_WGB, true, false, false, false, 1>(s, args, grid, stream);
+    };
+    if (!s.rec_jglobal) return walk();
+    // the Jacobian's values of every workgroup in global memory: one array per system object, like the workspace
+    int rc = s.gws_dev.ensure((size_t)grid * ((s.counts.zj + 2) & ~1u));
+    if (rc != EZPZ_OK) return rc;
+    args.gws = s.gws_dev.p;
+    return on_workspace(s, stream, walk);
+}
+
+// launch() asks its routes in turn; each serves the call (EZPZ_OK), fails it (an error), or leaves it to the next (kNextRoute).
+constexpr int kNextRoute = 1;
+
+// A device-filling batch of one connected sketch: lanes across the batch (batch_kernel.hip.hpp).
+int route_lanes(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
+    constexpr uint64_t kNoLanesWorkspace = ~0ull;  // the allocation failed once: not tried again on every call
+    if (!s.lanes || args.batch < s.lanes_min) return kNextRoute;
+    args.done.request = nullptr;
+    if (s.lanes_ws_waves == 0) {
+        // one workspace per wavefront the device holds (capped at 24 GiB of the 288: fewer wavefronts then)
+        uint64_t waves = batch_launch_waves(s.lim.cus);
+        const uint64_t per = (uint64_t)s.lanes->rows * 512;
+        while (waves > 4 && waves * per > (24ull << 30)) waves /= 2;
+        s.lanes_ws_waves = s.lanes_ws.ensure((size_t)(waves * per / 8)) == EZPZ_OK ? waves : kNoLanesWorkspace;
     }
-    return staged ? launch_variant<64, MODE_WGB, true, true>(s, args, grid, stream)
-                  : launch_variant<64, MODE_WGB, true, false>(s, args, grid, stream);
+    if (s.lanes_ws_waves == kNoLanesWorkspace) return kNextRoute;
+    int teams = EZPZ_OK;
+    const int rc = on_workspace(s, stream, [&]() -> int {
+        // the systems the lanes give up (stragglers, batch_kernel.hip.hpp) are listed on the device and resumed by this
+        // system's list-walk teams right after: an indirect batch whose count stays on the device
+        // (room for every wavefront handing over its threshold's worth of lanes once: a list that overflows leaves the lanes their tail)
+        const uint64_t strag_most = std::min<uint64_t>(s.lanes_ws_waves, (args.batch + 63) / 64) * batch_straggler_lanes();
+        const uint32_t strag_cap = args.batch < (1ull << 32) && args.batch >= 256 && strag_most
+                                       ? (uint32_t)std::min<uint64_t>(args.batch, std::max<uint64_t>(4096, strag_most)) : 0u;
+        bool list_ok = strag_cap && s.strag_list.ensure(strag_cap) == EZPZ_OK && s.strag_count.ensure(1) == EZPZ_OK &&
+                       s.strag_state.ensure(strag_cap) == EZPZ_OK;
+        if (list_ok && hipMemsetAsync(s.strag_count.p, 0, sizeof(uint32_t), stream) != hipSuccess) {
+            (void)hipGetLastError();
+            list_ok = false;
+        }
+        if (batch_launch(*s.lanes, s.dev_lanes, s.lanes_ws.p, s.lanes_ws_waves, s.counts.n_cons, comp_launch_args(args), stream,
+                         list_ok ? s.strag_list.p : nullptr, list_ok ? s.strag_count.p : nullptr, list_ok ? strag_cap : 0u,
+                         list_ok ? s.strag_state.p : nullptr) != EZPZ_OK)
+            return kNextRoute;
+        if (list_ok) {
+            args.sys_list = s.strag_list.p;
+            args.sys_count = s.strag_count.p;
+            args.resume = s.strag_state.p;  // (the teams go on from the values the lanes left in x_out)
+            args.batch = strag_cap;
+            teams = launch_list_walk(s, args, stream);
+        }
+        return EZPZ_OK;  // (recorded after the teams: the next launch of this system, on whatever stream, resets the list's count)
+    });
+    return rc == EZPZ_OK ? teams : rc;
+}
+
+// One connected sketch as a tree of dense fronts (fronts.cpp): every call of a system created for one solve, the small calls of a
+// system created for batches.
+int route_fronts(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
+    if (!s.fronts || args.resume || args.sys_list || (t_call_batch ? t_call_batch : args.batch) > s.front_max_batch) return kNextRoute;
+    // (a launch that is being recorded into a graph: fronts on several workgroups allocate and zero their scratch on first use and
+    // chain their launches on the process-wide event of launch_resident -- neither may end up inside a capture, which would also
+    // leave that event unusable for the launches after it.  A system created for batches has its other shapes and takes them; a
+    // system the fronts alone serve says so)
+    if (s.fronts->n_wgs > 1 && stream_capturing(stream)) return s.front_max_batch == 0xFFFFFFFFu ? EZPZ_ERR_INVALID_ARGUMENT : kNextRoute;
+    return front_launch(s, args, stream);
+}
+
+// One solve (or a few) of a small system built for latency: one wavefront per system, sweeps and assembly across its lanes
+// (jit_kernel.hip.hpp: wave_kernel), compiled like the lane kernel.
+int route_wave_jit(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
+    if (!s.lane || !s.wave_jit || args.batch > (uint64_t)s.lim.cus) return kNextRoute;
+    if (s.launches.load(std::memory_order_relaxed) == 0) comp_jit_probe(s.wave_jit);
+    int st = comp_jit_state(s.wave_jit);
+    if (st == 0 && (jit_sync() || s.launches.load(std::memory_order_relaxed) >= s.lim.policy.jit_after_launches)) st = comp_jit_request(s.wave_jit, jit_sync());
+    return st == 2 && wave_jit_launch(s.wave_jit, *s.lane, comp_launch_args(args), s.device, s.lim.cus, stream) == EZPZ_OK ? EZPZ_OK : kNextRoute;
+}
+
+// A small system: one lane per system once the specialised kernel is compiled.
+int route_lane_jit(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
+    if (!s.lane || !s.jit) return kNextRoute;
+    int st = comp_jit_state(s.jit);
+    const EzpzLaunchPolicy& pol = s.lim.policy;
+    if (st == 0 && (args.batch >= pol.jit_lane_min_batch || jit_sync() || s.launches.fetch_add(1) >= pol.jit_after_launches))
+        st = comp_jit_request(s.jit, jit_sync());
+    return st == 2 && lane_jit_launch(s.jit, *s.lane, comp_launch_args(args), s.device, s.lim.cus, stream) == EZPZ_OK ? EZPZ_OK : kNextRoute;
+}
+
+// A block system's compiled kernel in one of its three forms; anything but EZPZ_OK leaves the call to the interpreter.
+int launch_block_jit(EzpzSystem& s, SolveArgs& args, const CompLaunch& L, hipStream_t stream) {
+    if (s.comp->jit_wgs > 1) {
+        const int rc = launch_jit_grid(s, L, stream);
+        if (rc == EZPZ_OK) args.done.request = nullptr;
+        return rc;
+    }
+    JitLaunchState& js = s.jit_state;
+    if (comp_jit_fast_ok(s.jit, *s.comp, L, s.device, s.lim.cus) && !stream_capturing(stream) && js.redo_lists(L.batch, stream) == EZPZ_OK &&
+        js.chain(stream)) {
+        // a linear system: the kernel that does not wait for the LM control's verdicts, then the loop over the systems it lists
+        // (jit_kernel.hip.hpp: solve_kernel_fast).  Never inside a capture: the redo list is zeroed by the NEXT call's launches,
+        // which a replay does not run
+        const uint32_t fast_slots = (uint32_t)std::min<uint64_t>(comp_jit_capacity_fast(s.jit, *s.comp, s.device, s.lim.cus), 0xFFFFFFFFull);
+        return jit_launch(s, L, stream, 0, fast_slots);
+    }
+    return jit_launch(s, L, stream, 0, 0);  // the loop alone
+}
+
+// Many small components in few classes: the class-specialised kernel once it is compiled -- large batches start its compilation
+// (background thread) -- else one lane per component on the interpreter (comp_kernel.hip.hpp).
+int route_blocks(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
+    if (!s.comp) return kNextRoute;
+    const CompLaunch L = comp_launch_args(args);
+    if (s.jit) {
+        const bool sync = jit_sync();
+        int st = comp_jit_state(s.jit);
+        const EzpzLaunchPolicy& pol = s.lim.policy;
+        const bool big = args.batch >= pol.jit_comp_min_batch || args.batch * (uint64_t)s.counts.n_vars >= pol.jit_comp_min_values;
+        if (st == 0 && (big || sync || s.launches.fetch_add(1) >= pol.jit_after_launches)) st = comp_jit_request(s.jit, sync);
+        if (st == 2 && launch_block_jit(s, args, L, stream) == EZPZ_OK) return EZPZ_OK;
+    }
+    if (s.comp->interpretable) return comp_launch(*s.comp, s.dev_comp, L, s.device, s.lim.cus, s.lim.lds_bytes, stream);
+    return kNextRoute;  // (a system too large for the interpreter's LDS state: the list-walk grid team until the compiled kernel is ready)
 }
 
 int launch(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
     if (args.batch == 0) return EZPZ_OK;
     // enqueueing on one EzpzSystem from several threads (each on its own stream) is allowed: what a launch creates on
     // first use -- workspaces, events, occupancy figures -- is created under this lock, and launches that share a
-    // workspace are chained on an event below
+    // workspace are chained on an event
     std::lock_guard<std::mutex> launch_lock(s.launch_mu);
-    constexpr uint64_t kNoLanesWorkspace = ~0ull;  // the allocation failed once: not tried again on every call
     if (args.batch != 1) args.done.request = nullptr;  // (residency is for one-call launches: one system, one workgroup)
-    if (s.lanes && args.batch >= s.lanes_min) {
-        args.done.request = nullptr;  // a device-filling batch of one connected sketch: lanes across the batch
-        if (s.lanes_ws_waves == 0) {
-            // one workspace per wavefront the device holds (capped at 24 GiB of the 288: fewer wavefronts then)
-            uint64_t waves = batch_launch_waves(s.lim.cus);
-            const uint64_t per = (uint64_t)s.lanes->rows * 512;
-            while (waves > 4 && waves * per > (24ull << 30)) waves /= 2;
-            s.lanes_ws_waves = s.lanes_ws.ensure((size_t)(waves * per / 8)) == EZPZ_OK ? waves : kNoLanesWorkspace;
-        }
-        if (s.lanes_ws_waves != kNoLanesWorkspace) {
-            // one workspace per system object: launches on different streams are chained, never overlapped
-            if (!s.lanes_done)
-                HIP_TRY(hipEventCreateWithFlags(&s.lanes_done, hipEventDisableTiming));
-            else
-                HIP_TRY(hipStreamWaitEvent(stream, s.lanes_done, 0));
-            // the systems the lanes give up (stragglers, batch_kernel.hip.hpp) are listed on the device and resumed by this
-            // system's list-walk teams right after: an indirect batch whose count stays on the device
-            // (room for every wavefront handing over its threshold's worth of lanes once: a list that overflows leaves the lanes their tail)
-            const uint64_t strag_most = std::min<uint64_t>(s.lanes_ws_waves, (args.batch + 63) / 64) * batch_straggler_lanes();
-            const uint32_t strag_cap = args.batch < (1ull << 32) && args.batch >= 256 && strag_most
-                                           ? (uint32_t)std::min<uint64_t>(args.batch, std::max<uint64_t>(4096, strag_most)) : 0u;
-            bool list_ok = strag_cap && s.strag_list.ensure(strag_cap) == EZPZ_OK && s.strag_count.ensure(1) == EZPZ_OK &&
-                           s.strag_state.ensure(strag_cap) == EZPZ_OK;
-            if (list_ok && hipMemsetAsync(s.strag_count.p, 0, sizeof(uint32_t), stream) != hipSuccess) {
-                (void)hipGetLastError();
-                list_ok = false;
-            }
-            if (batch_launch(*s.lanes, s.dev_lanes, s.lanes_ws.p, s.lanes_ws_waves, s.counts.n_cons, comp_launch_args(args), stream,
-                             list_ok ? s.strag_list.p : nullptr, list_ok ? s.strag_count.p : nullptr, list_ok ? strag_cap : 0u,
-                             list_ok ? s.strag_state.p : nullptr) == EZPZ_OK) {
-                int rc = EZPZ_OK;
-                if (list_ok) {
-                    args.sys_list = s.strag_list.p;
-                    args.sys_count = s.strag_count.p;
-                    args.resume = s.strag_state.p;  // (the teams go on from the values the lanes left in x_out)
-                    args.batch = strag_cap;
-                    rc = launch_list_walk(s, args, stream);
-                }
-                // (after the teams: the next launch of this system, on whatever stream, resets the list's count)
-                HIP_TRY(hipEventRecord(s.lanes_done, stream));
-                return rc;
-            }
-        }
-    }
-    // one connected sketch as a tree of dense fronts (fronts.cpp): every call of a system created for one solve, the small calls
-    // of a system created for batches
-    if (s.fronts && !args.resume && !args.sys_list && (t_call_batch ? t_call_batch : args.batch) <= s.front_max_batch) {
-        // (a launch that is being recorded into a graph: fronts on several workgroups allocate and zero their scratch on first use and
-        // chain their launches on the process-wide event of the grid teams -- neither may end up inside a capture, which would also
-        // leave that event unusable for the launches after it.  A system created for batches has its other shapes and takes them; a
-        // system the fronts alone serve says so)
-        if (s.fronts->n_wgs > 1 && stream_capturing(stream)) {
-            if (s.front_max_batch == 0xFFFFFFFFu) return EZPZ_ERR_INVALID_ARGUMENT;
-        } else {
-            return front_launch(s, args, stream);
-        }
-    }
+    int rc = route_lanes(s, args, stream);
+    if (rc == kNextRoute) rc = route_fronts(s, args, stream);
+    if (rc != kNextRoute) return rc;
     if (s.jit && s.launches.load(std::memory_order_relaxed) == 0) comp_jit_probe(s.jit);  // the kernel may be in the on-disk cache
-    if (s.lane && s.wave_jit && args.batch <= (uint64_t)s.lim.cus) {
-        // one solve (or a few) of a small system built for latency: one wavefront per system, sweeps and assembly across its
-        // lanes (jit_kernel.hip.hpp: wave_kernel), compiled like the lane kernel
-        if (s.launches.load(std::memory_order_relaxed) == 0) comp_jit_probe(s.wave_jit);
-        int st = comp_jit_state(s.wave_jit);
-        if (st == 0 && (jit_sync() || s.launches.load(std::memory_order_relaxed) >= s.lim.policy.jit_after_launches)) st = comp_jit_request(s.wave_jit, jit_sync());
-        if (st == 2 && wave_jit_launch(s.wave_jit, *s.lane, comp_launch_args(args), s.device, s.lim.cus, stream) == EZPZ_OK) return EZPZ_OK;
-    }
-    if (s.lane && s.jit) {  // a small system: one lane per system once the specialised kernel is compiled
-        int st = comp_jit_state(s.jit);
-        const EzpzLaunchPolicy& pol = s.lim.policy;
-        if (st == 0 && (args.batch >= pol.jit_lane_min_batch || jit_sync() || s.launches.fetch_add(1) >= pol.jit_after_launches))
-            st = comp_jit_request(s.jit, jit_sync());
-        if (st == 2 && lane_jit_launch(s.jit, *s.lane, comp_launch_args(args), s.device, s.lim.cus, stream) == EZPZ_OK) return EZPZ_OK;
-    }
-    if (s.comp) {  // many small components in few classes: one lane per component (comp_kernel.hip.hpp)
-        const CompLaunch L = comp_launch_args(args);
-        // the class-specialised kernel once it is compiled; large batches start its compilation (background thread)
-        if (s.jit) {
-            const bool sync = jit_sync();
-            int st = comp_jit_state(s.jit);
-            const EzpzLaunchPolicy& pol = s.lim.policy;
-            const bool big = args.batch >= pol.jit_comp_min_batch || args.batch * (uint64_t)s.counts.n_vars >= pol.jit_comp_min_values;
-            if (st == 0 && (big || sync || s.launches.fetch_add(1) >= pol.jit_after_launches)) st = comp_jit_request(s.jit, sync);
-            if (st == 2) {
-                if (s.comp->jit_wgs <= 1 && comp_jit_fast_ok(s.jit, *s.comp, L, s.device, s.lim.cus) && !stream_capturing(stream) &&
-                    jit_redo_lists(s, L.batch, stream) == EZPZ_OK && chain_launches(s, stream)) {
-                    // a linear system: the kernel that does not wait for the LM control's verdicts, then the loop over the systems it
-                    // lists (jit_kernel.hip.hpp: solve_kernel_fast)
-                    const unsigned int turn = s.jit_redo_turn;
-                    const uint32_t fast_wgs = (uint32_t)std::min<uint64_t>(comp_jit_capacity_fast(s.jit, *s.comp, s.device, s.lim.cus), 0xFFFFFFFFull);
-                    CompLaunch Lt = L;
-                    if (L.batch > fast_wgs && prepare_tickets(s, stream)) Lt.ticket = s.ticket.p, Lt.ticket_base = s.ticket_base;
-                    if (comp_jit_launch(s.jit, *s.comp, s.dev_comp, Lt, s.device, s.lim.cus, stream, nullptr, 0, fast_wgs, s.jit_redo[turn].p,
-                                        s.jit_redo[turn ^ 1u].p, s.jit_redo_seen_dev, s.jit_redo_seen) == EZPZ_OK) {
-                        if (Lt.ticket) advance_tickets(s, stream, fast_wgs, L.batch, 2);
-                        s.ticket_stream = stream;  // (the redo lists are shared with the next call: chain_launches)
-                        s.ticket_used = true;
-                        s.jit_redo_turn = turn ^ 1u;
-                        return EZPZ_OK;
-                    }
-                } else if (s.comp->jit_wgs <= 1) {
-                    // a batch beyond the launch's workgroups: the workgroups draw their systems from the system's counter, and
-                    // launches that share the counter are chained
-                    const uint64_t capacity = L.done.flag ? 0 : comp_jit_capacity(s.jit, *s.comp, s.device, s.lim.cus);
-                    CompLaunch Lt = L;
-                    if (capacity && L.batch > capacity && L.batch < (1ull << 32) && prepare_tickets(s, stream)) Lt.ticket = s.ticket.p, Lt.ticket_base = s.ticket_base;
-                    if (comp_jit_launch(s.jit, *s.comp, s.dev_comp, Lt, s.device, s.lim.cus, stream) == EZPZ_OK) {
-                        if (Lt.ticket) advance_tickets(s, stream, capacity, L.batch, 1);
-                        return EZPZ_OK;
-                    }
-                } else {
-                    CompLaunch Lg = L;
-                    Lg.done.request = nullptr;  // (several workgroups per system: never resident)
-                    if (launch_jit_grid(s, Lg, stream) == EZPZ_OK) {
-                        args.done.request = nullptr;
-                        return EZPZ_OK;
-                    }
-                }
-            }
-        }
-        if (s.comp->interpretable) return comp_launch(*s.comp, s.dev_comp, L, s.device, s.lim.cus, s.lim.lds_bytes, stream);
-        // (a system too large for the interpreter's LDS state: the list-walk grid team below until the specialised
-        // kernel is ready)
-    }
+    for (auto route : {route_wave_jit, route_lane_jit, route_blocks})
+        if ((rc = route(s, args, stream)) != kNextRoute) return rc;
     return launch_list_walk(s, args, stream);
 }
-
 
 void fill_cfg(SolveArgs& a, const EzpzConfig* cfg) {
     EzpzConfig d;
@@ -512,7 +504,6 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
     a.unsat_mask = unsat_mask_dev;
     a.warn_log = warn_cap ? warn_log_dev : nullptr;
     a.warn_cap = warn_cap;
-    a.gws = nullptr;
     a.batch = batch;
     a.ws_doubles = sys->ws_doubles;
     a.prog_lds_doubles = sys->prog_lds_doubles;
@@ -525,12 +516,7 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
     a.dense_lds_doubles = sys->dense_lds_doubles;
     a.stamps = g_stamps;
     a.unit_weights = sys->unit_weights ? 1u : 0u;
-    a.grid_wgs = 1;
-    a.grid_scratch = nullptr;
-    a.grid_views = nullptr;
-    a.sys_list = nullptr;
-    a.sys_count = nullptr;
-    a.resume = nullptr;
+    a.grid_wgs = 1;  // (gws, the grid team's scratch, the list of systems and the resumed states: none)
     a.done = done;
     if (sys->rec) {
         const unsigned char* base = static_cast<const unsigned char*>(sys->dev_program);
@@ -556,7 +542,6 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
     if (resident) *resident = rc == EZPZ_OK && a.done.request != nullptr;
     return rc;
 }
-
 
 // The systems of one topology inside a heterogeneous batch, solved IN PLACE by the lane-per-system kernel (mixed.hip): lane i
 // reads its values at row_offset[i] of the caller's ragged buffer, writes them back there and its status to
@@ -672,8 +657,3 @@ int ezpz::eval_batch_locked(EzpzSystem* sys, const double* x, size_t batch, doub
         HIP_TRY(hipMemcpy(degenerate_count_out, dd.p, batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return EZPZ_OK;
 }
-
-extern "C" {
-
-
-}  // extern "C"

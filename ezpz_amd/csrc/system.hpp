@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -154,6 +155,35 @@ struct PinnedBuf {
     }
 };
 
+// What the launches of one system's specialised kernel share on the device (jit_kernel.hip.hpp) and the host's view of it, touched
+// under the system's launch_mu (methods: launch.hip).  The work counters (JitArgs::ticket) are never reset: what a launch draws from
+// each follows from its batch and its workgroups, the host keeps the running totals (ticket_base) -- so launches that use the state
+// must not overlap: on one stream they do not anyway; when the stream CHANGES, an event recorded on the old one is waited for on the
+// new one (chain).  The two redo lists of the `_fast` entry (count, then systems) alternate between calls, each zeroing the other's count.
+struct JitLaunchState {
+    DevBuf<unsigned int> ticket;
+    unsigned int ticket_base[8] = {};
+    hipEvent_t done = nullptr;
+    hipStream_t stream = nullptr;  // the stream of the last launch that used the state
+    bool used = false;
+    DevBuf<unsigned int> redo[2];
+    unsigned int turn = 0;
+    unsigned int* redo_seen = nullptr;      // mapped host memory: the count the loop's last launch found (a hint, jit.cpp)
+    unsigned int* redo_seen_dev = nullptr;  // ... its device address
+    DevBuf<unsigned char> scratch;  // a system on several workgroups: their reduction scratch, and its sequence numbers used
+    uint64_t seq_used = 0;
+
+    bool chain(hipStream_t stream);    // false: could not be arranged
+    bool tickets(hipStream_t stream);  // the counters for a launch on `stream`, chained; false: the launch keeps fixed shares
+    int redo_lists(uint64_t batch, hipStream_t stream);  // both lists for `batch` systems, and the mapped word
+    void commit(const JitEnqueued& e, uint64_t batch, hipStream_t stream);  // the totals and the turn from what a launch enqueued
+    int resync(hipStream_t stream);  // after a launch that went out in part: device counters, redo counts, totals and turn zeroed
+    ~JitLaunchState() {
+        if (done) (void)hipEventDestroy(done);
+        if (redo_seen) (void)hipHostFree(redo_seen);
+    }
+};
+
 }  // namespace ezpz
 
 // (the opaque type of the C ABI lives in the global namespace; this header is internal to the library)
@@ -183,12 +213,7 @@ struct EzpzSystem {
     std::vector<EzpzConstraint> deferred_cs;
     std::mutex defer_mu;
     CompJit* jit = nullptr;  // the plan's class-specialised kernel (run-time compiled), when it has one
-    DevBuf<unsigned char> jit_scratch;  // ... and, when it spreads a system over several workgroups, their reduction scratch
-    DevBuf<unsigned int> jit_redo[2];   // ... and the lists of systems its `_fast` entry leaves to the loop (count, then systems):
-                                        // calls alternate between the two, each zeroes the other's count (launch.hip)
-    unsigned int jit_redo_turn = 0;
-    unsigned int* jit_redo_seen = nullptr;      // mapped host memory: the count the loop's last launch found (a hint, jit.cpp)
-    unsigned int* jit_redo_seen_dev = nullptr;  // ... its device address
+    JitLaunchState jit_state;  // ... and what its launches share on the device
     std::unique_ptr<LanePlan> lane;  // small systems: one lane per system, run-time compiled (jit stands for it then)
     CompJit* wave_jit = nullptr;     // ... and, for the latency of one solve, the same class on one wavefront per system
     // connected sketches in large batches: one lane per system, uniform program, state in global memory (batch_kernel.hip.hpp)
@@ -198,14 +223,6 @@ struct EzpzSystem {
     DevBuf<uint32_t> strag_list, strag_count;  // the systems a lanes launch hands over to the teams (device-side list + count)
     DevBuf<LmResume> strag_state;              // ... and the LM state each had reached
     uint64_t lanes_ws_waves = 0;
-    // the specialised kernels' work counters (JitArgs::ticket): never reset -- what a launch draws from each follows from its batch and
-    // its workgroups, the host keeps the running totals -- so launches that use them must not overlap: on one stream they do not
-    // anyway; when the stream CHANGES, an event recorded on the old one is waited for on the new one (under launch_mu)
-    DevBuf<unsigned int> ticket;
-    unsigned int ticket_base[8] = {};
-    hipEvent_t ticket_done = nullptr;
-    hipStream_t ticket_stream = nullptr;  // the stream of the last launch that drew from the counters
-    bool ticket_used = false;
     hipEvent_t lanes_done = nullptr;  // completion of this system's last launch that used its global-memory workspace (lanes
                                       // kernel, list walk with the workspace in global memory): the next one, on any stream, waits for it
     uint64_t lanes_min = ~0ull;  // systems per call from which `lanes` serves the call
@@ -228,7 +245,7 @@ struct EzpzSystem {
     // launch to launch (grid_ops.hip.hpp, jit_kernel.hip.hpp, front_kernel.hip.hpp).  An upper bound of what the launches so far
     // have used of them; past kSeqBudget the launch code zeroes the area first (ordered behind the last launch that used it), and
     // the numbers start again -- a process that solves one such system for days never meets the wrap.
-    uint64_t grid_seq_used = 0, jit_seq_used = 0, front_seq_used = 0;
+    uint64_t grid_seq_used = 0, front_seq_used = 0;  // (the specialised kernel's: jit_state)
     void* dev_grid_blob = nullptr;
     DevBuf<ProgramView> grid_views;
     uint32_t prog_lds_doubles = 0;
@@ -293,8 +310,6 @@ struct EzpzSystem {
         if (dev_lanes) (void)hipFree(dev_lanes);
         if (dev_fronts) (void)hipFree(dev_fronts);
         if (lanes_done) (void)hipEventDestroy(lanes_done);
-        if (ticket_done) (void)hipEventDestroy(ticket_done);
-        if (jit_redo_seen) (void)hipHostFree(jit_redo_seen);
         comp_jit_destroy(jit);
         comp_jit_destroy(wave_jit);
     }
@@ -395,6 +410,11 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
 // The whole call's systems while a host entry of this thread feeds them to launch() in pieces (pipeline.cpp): the launch shape is
 // chosen once per call, not per piece -- a short last piece does not change shape (0: the piece is the call).
 extern thread_local uint64_t t_call_batch;
+// A launch whose workgroups wait for each other (grid teams, the specialised kernel or fronts on several workgroups), sized by the caller
+// to what the device holds, behind the process's last such launch on the device; `scratch` is zeroed first when `seq_used` has spent
+// the sequence budget.  (The caller refuses stream capture before it allocates anything: it would leave the chaining event unusable.)
+int launch_resident(int device, hipStream_t stream, void* scratch, size_t scratch_bytes, uint64_t& seq_used, uint64_t batch,
+                    uint64_t exchanges_per_system, const std::function<int()>& launch);
 int front_launch(EzpzSystem& s, SolveArgs& args, hipStream_t stream);
 int front_launch_probe(EzpzSystem& s, const double* x_dev, size_t batch, double* y_dev, uint32_t m, hipStream_t stream,
                        const double* w_dev = nullptr, double lambda_scale = 1e-11);  // front.hip  // front.hip: the frontal shape (EzpzSystem::fronts)

@@ -406,7 +406,7 @@ def test_verdicts_not_waited_for_row_layouts(E, lines, permute):
 def test_verdicts_not_waited_for_on_two_streams(E):
     """The `_device` entry may be called on one EzpzSystem from several streams.  The kernels that do not wait for verdicts share two
     redo lists per system between consecutive calls (each call's last launch zeroes the other list's count): calls on another
-    stream than the last one are chained behind it (launch.hip: chain_launches).  Twelve calls alternating between two streams, every
+    stream than the last one are chained behind it (launch.hip: JitLaunchState::chain).  Twelve calls alternating between two streams, every
     third system of every call one that needs the loop kernel: every call's results equal the host entry's."""
     import torch
 

@@ -22,8 +22,6 @@ B="--legs 0 --pmc 0 --cpu-seconds 0 --extras 0"
 (echo "# EZPZ_JIT_AHEAD=<0|1> python bench.py --full <workload> $B   (0 = the loop kernels of round 5: every verdict of the LM control waited for; 1 = the default)"
 for i in 1 2; do for v in 0 1; do for w in "--steps 20 --warmup 5" "--workload massive200 --batch 65536" "--workload massive600 --batch 65536" "--workload massive50000 --batch 64 --steps 20" "--workload massive50000 --batch 256 --steps 20"; do
   echo "EZPZ_JIT_AHEAD=$v bench.py $w"; EZPZ_JIT_AHEAD=$v python bench.py --full $w $B 2>/dev/null | python -c "$P"; done; done; done) > $out/fast_ab.txt
-(echo "# EZPZ_TICKETS=<0|1> python bench.py --full --steps 20 --warmup 5 $B   (0 = fixed shares of the batch per workgroup, 1 = the default: workgroups draw their systems)"
-for i in 1 2; do for v in 0 1; do echo "EZPZ_TICKETS=$v"; EZPZ_TICKETS=$v python bench.py --full --steps 20 --warmup 5 $B 2>/dev/null | python -c "$P"; done; done) > $out/tickets_ab.txt
 (python tools/resident_cost.py 2>&1 | grep -v amdgpu.ids) > $out/resident_cost.txt
 (echo "# python tools/ladder_stamps.py 50000 280  (the kernel that does not wait for verdicts, compiled with its time stamps: 0 start, 1 both steps taken and stores issued, 2 the barrier, 3 partials published, 4 its turn at the totals of the system before; us)"; python tools/ladder_stamps.py 50000 280 2>&1 | grep -v "amdgpu.ids\|^  system") > $out/ladder_stamps.txt
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/row_copy_bench.bin tools/row_copy_bench.hip 2>/dev/null && (echo "# tools/row_copy_bench.bin  (what memory allows a kernel that streams 16 KB rows in and out at the solve kernels' occupancy: their access pattern against full lines)"; ./tools/row_copy_bench.bin 2>&1) > $out/row_copy_bench.txt
