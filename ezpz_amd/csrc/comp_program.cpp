@@ -466,8 +466,9 @@ void emit_class(std::string& o, size_t k, const Class& cl, bool lane = false, co
             }
         }
         o += "        (void)ok;\n        return bad;\n    }\n";
-        o += "    static __device__ __forceinline__ void solve_f(const double (&F)[NF], const double (&r)[" + S(std::max(m, 1u)) + "], double (&d)[" + S(nv) +
-             "], double& dmax, bool& ok) {\n";
+        // (OK: what div_by folds its range test into -- jit_kernel.hip.hpp: DivRange)
+        o += "    template <class OK> static __device__ __forceinline__ void solve_f(const double (&F)[NF], const double (&r)[" + S(std::max(m, 1u)) + "], double (&d)[" + S(nv) +
+             "], double& dmax, OK& ok) {\n";
         for (uint32_t v = 0; v < nv; ++v) o += "        const double D" + S(v) + " = F[" + S(2 * v) + "], Y" + S(v) + " = F[" + S(2 * v + 1) + "]; (void)Y" + S(v) + ";\n";
         for (uint32_t s2 = 0; s2 < zlo; ++s2) o += "        const double L" + S(s2) + " = F[" + S(2 * nv + s2) + "];\n";
         for (uint32_t v = 0; v < nv; ++v) {

@@ -218,6 +218,23 @@ __device__ __forceinline__ double div_by(double n, double D, double y, bool& ok)
     const double e = __builtin_fma(D, q0, -n);
     return __builtin_fma(-e, y, q0);
 }
+// The same range test folded over many divisions, for the kernels that decide once per system (fast_wave): the largest |n| -- a
+// maximum that ignores NaN, as the test above lets it pass -- and the smallest binary exponent, which v_frexp_exp_i32_f64 gives as
+// 0 for a zero, an infinity and a NaN (they pass this half, as above) and as the true exponent for a denormal: |n| < 2^-900 is
+// exponent < -899.  failed() is true for exactly the lanes in which one of the divisions would have cleared `ok`.
+struct DivRange {
+    double amax = 0.0;
+    int emin = 0;
+    __device__ __forceinline__ bool failed() const { return amax > 0x1p+600 || emin < -899; }
+};
+__device__ __forceinline__ double div_by(double n, double D, double y, DivRange& range) {
+    range.amax = ezpz::dev::fmax_abs(range.amax, n);
+    const int ex = __builtin_amdgcn_frexp_exp(n);
+    range.emin = ex < range.emin ? ex : range.emin;
+    const double q0 = n * y;
+    const double e = __builtin_fma(D, q0, -n);
+    return __builtin_fma(-e, y, q0);
+}
 
 // A copy of `a` the optimiser cannot relate to the original: the fallback's inputs.  Without it the sums the two
 // solves have in common (the normal equations) are formed once and kept in registers across the short solve for a
@@ -1088,6 +1105,15 @@ __device__ __forceinline__ void store_at(__amdgpu_buffer_rsrc_t row, uint32_t by
 // parameters, and the factorisation of every class at the two lambdas of the expected path -- J^T J + lambda I of a linear class is
 // the same matrix for every instance of every system: factorised once per launch (newton.rs:73-99: the operations of C::solve
 // that do not involve the right-hand side, in its order), kept in scalar registers by the class's first slot.
+// Whether this lane has an instance in the slot, asked of its first id, every time anew (the empty asm): the answers do not change from
+// system to system, and kept across the loop they are a pair of scalar registers per slot that the kernel does not have -- they were
+// spilled to lanes of a vector register and read back two v_readlane per slot and system; asked anew it is one compare.
+constexpr uint32_t kNoInstance = 0xFFFFFFFFu;  // (an id is a byte offset of a double: a multiple of 8)
+template <class S>
+__device__ __forceinline__ bool fast_has_instance(S& s) {
+    asm volatile("" : "+v"(s.ids[0]));
+    return s.ids[0] != kNoInstance;
+}
 template <class SEQ>
 __device__ __forceinline__ void fast_setup(SEQ& seq, const JitArgs& a, const uint32_t wave_global, const int lane, const uint32_t first_byte = 0) {
     seq.each([&](auto& s, auto* cls, int index) {
@@ -1095,9 +1121,10 @@ __device__ __forceinline__ void fast_setup(SEQ& seq, const JitArgs& a, const uin
         const uint32_t* t = a.blob + a.o_slots + 4 * ((size_t)wave_global * SEQ::N + index);
         const uint32_t ids_off = t[0], par_off = t[1], count = t[3];
         s.active = (uint32_t)lane < count;
-        // (first_byte: the wavefront's piece of the row starts there -- offsets into the piece; a lane without an instance reads its start)
+        // (first_byte: the wavefront's piece of the row starts there -- offsets into the piece; a lane without an instance: fast_has_instance)
+        static_assert(C::NV > 0, "a slot's first id says whether the lane has an instance");
 #pragma unroll
-        for (int k = 0; k < C::NV; ++k) s.ids[k] = s.active ? a.blob[ids_off + (size_t)k * C::STRIDE + lane] * 8u - first_byte : 0u;
+        for (int k = 0; k < C::NV; ++k) s.ids[k] = s.active ? a.blob[ids_off + (size_t)k * C::STRIDE + lane] * 8u - first_byte : kNoInstance;
         const double* par = reinterpret_cast<const double*>(a.blob + par_off) + lane;
 #pragma unroll
         for (int k = 0; k < C::NC; ++k) s.par[k] = par[(size_t)k * C::STRIDE];
@@ -1108,8 +1135,10 @@ __device__ __forceinline__ void fast_fetch(SEQ& seq, const JitArgs& a, const uin
     const __amdgpu_buffer_rsrc_t x0 = row_at(a.x0 + sys * a.n_row);
     seq.each([&](auto& s, auto* cls, int) {
         using C = typename class_of<decltype(cls)>::type;
+        if (s.active) {
 #pragma unroll
-        for (int i = 0; i < C::NV; ++i) s.xn[i] = load_at(x0, s.ids[i]);
+            for (int i = 0; i < C::NV; ++i) s.xn[i] = load_at(x0, s.ids[i]);
+        }
     });
 }
 // A wavefront's CONTIGUOUS piece of a row -- `bytes` from `first_byte` on: the generator found that the variables of the wavefront's
@@ -1151,23 +1180,32 @@ __device__ __forceinline__ void piece_store(const double* buf, const __amdgpu_bu
             __builtin_amdgcn_raw_buffer_store_b64(bufword2_t{q.x, q.y}, row, (int)(first_byte + at), 0, 0);
     }
 }
+// Returns what the factorisations alone say about every system of the launch, as fast_wave's flag bits -- bit 0 / 1: a pivot of the
+// first / second step failed, bit 2: a factorisation left the short division's range with its pivots fine -- over the slots in which
+// the wavefront has an instance at all: uniform, and the same for every system, so nothing of it is tested slot by slot.
 template <class SEQ>
-__device__ __forceinline__ void fast_factor(SEQ& seq, const JitArgs& a) {
+__device__ __forceinline__ unsigned int fast_factor(SEQ& seq, const JitArgs& a) {
     const double lambda1 = a.initial_lambda * ezpz::dev::LM_LAMBDA_DECR;
+    unsigned int slot_flags = 0;
     seq.each([&](auto& s, auto* cls, int) {
         using C = typename class_of<decltype(cls)>::type;
-        if (&s != &seq.template first<C>()) return;  // (once per class: its other slots read the first one's)
+        auto& f = seq.template first<C>();
+        if (&s == &f) {  // (once per class: its other slots read the first one's)
 #pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            double F[C::NF];
-            bool ok = true;
-            const bool bad = C::factor(st == 0 ? a.initial_lambda : lambda1, F, ok);
+            for (int st = 0; st < 2; ++st) {
+                double F[C::NF];
+                bool ok = true;
+                const bool bad = C::factor(st == 0 ? a.initial_lambda : lambda1, F, ok);
 #pragma unroll
-            for (int i = 0; i < C::NF; ++i) s.F[st][i] = uniform(F[i]);
-            s.fbad[st] = __builtin_amdgcn_readfirstlane((int)bad) != 0;
-            s.fok[st] = __builtin_amdgcn_readfirstlane((int)ok) != 0;
+                for (int i = 0; i < C::NF; ++i) s.F[st][i] = uniform(F[i]);
+                s.fbad[st] = __builtin_amdgcn_readfirstlane((int)bad) != 0;
+                s.fok[st] = __builtin_amdgcn_readfirstlane((int)ok) != 0;
+            }
         }
+        if (__ballot(s.active) != 0)
+            slot_flags |= (f.fbad[0] ? 1u : 0u) | (f.fbad[1] ? 2u : 0u) | ((!f.fok[0] && !f.fbad[0]) || (!f.fok[1] && !f.fbad[1]) ? 4u : 0u);
     });
+    return slot_flags;
 }
 // One wavefront's share of system `sys` from the guesses in Slot::xn to the stored values: eval() (newton.rs:45, :232-236), then two
 // iterations taken for accepted -- the loop's two passes (newton.rs:73-116), x += d, r = r_next.  SLOT BY SLOT: one slot's x, d and
@@ -1190,7 +1228,7 @@ __device__ __forceinline__ bool fast_exceeds(unsigned int flags, int k) {  // !(
 // system's values are in `out_lds`, the slots read and write them there, the next system's piece is loaded as full lines at the top
 // and put into `next_lds` at the end, this one's is stored as full lines.
 template <int IO, class SEQ>
-__device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, const uint64_t sys, const uint64_t sys_n, const bool next,
+__device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, const unsigned int slot_flags, const uint64_t sys, const uint64_t sys_n, const bool next,
                                                   const uint32_t wave_global, const int lane, double (&v)[4], double* const out_lds,
                                                   double* const next_lds = nullptr, const uint32_t first_byte = 0, const uint32_t bytes = 0) {
     using namespace ezpz::dev;
@@ -1207,74 +1245,58 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
     v[0] = v[1] = v[2] = 0.0;
     v[3] = __builtin_nan("");
     double m[4] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan(""), __builtin_nan("")};  // this lane's max|r0|, |d1|, max|r1|, |d2|
-    bool lane_bad1 = false, lane_bad2 = false, lane_redo = false;
+    DivRange range;  // of every numerator of this lane's short divisions, tested once below
     int var0 = 0;
     seq.each([&](auto& s, auto* cls, int index) {
         using C = typename class_of<decltype(cls)>::type;
         auto& f = seq.template first<C>();
-        if constexpr (IO == 2) {
-#pragma unroll
-            for (int i = 0; i < C::NV; ++i) s.x[i] = *reinterpret_cast<const lds_f64_t*>(reinterpret_cast<const char*>(out_lds) + s.ids[i]);
-        } else {
+        // ONE predicated region per slot: a lane without an instance (the last wavefront's last slot of a class, at most) sits the
+        // whole slot out -- it reads nothing, adds nothing to the sums and the maxima, writes nothing -- instead of computing on the
+        // piece's first value and having every result deselected (eight 64-bit selects per slot, on slots that are almost all full)
+        // (the next system's guesses are asked for by every lane, outside the region: a register loaded under a predicate is merged
+        // with its old value where the region ends, and that waits for the load -- a lane without an instance reads the row's start)
+        if constexpr (IO != 2) {
 #pragma unroll
             for (int i = 0; i < C::NV; ++i) s.x[i] = s.xn[i];
             if (next) {
 #pragma unroll
-                for (int i = 0; i < C::NV; ++i) s.xn[i] = load_at(x0n, s.ids[i]);
+                for (int i = 0; i < C::NV; ++i) s.xn[i] = load_at(x0n, s.ids[0] != kNoInstance ? s.ids[i] : 0u);
             }
         }
-        unsigned long long wm = 0;
-        {
-            double sq_s = v[0], mx_s = m[0];
-            C::residuals(s.x, s.par, s.r, true, sq_s, mx_s, wm);
-            v[0] = s.active ? sq_s : v[0];
-            m[0] = s.active ? mx_s : m[0];
-        }
+        if (fast_has_instance(s)) {
+            if constexpr (IO == 2) {
 #pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            double cd = __builtin_nan("");
-            bool ok = f.fok[st];
-            C::solve_f(f.F[st], s.r, s.d, cd, ok);
-            const bool cb = f.fbad[st];
-            lane_redo = lane_redo || (s.active && !ok && !cb);
-            double& dmax = m[1 + 2 * st];
-            const double dm = fmax_nc(dmax, cd);
-            dmax = s.active ? dm : dmax;
-            if (st == 0)
-                lane_bad1 = lane_bad1 || (s.active && cb);
-            else
-                lane_bad2 = lane_bad2 || (s.active && cb);
-#pragma unroll
-            for (int i = 0; i < C::NV; ++i) s.x[i] = s.x[i] + s.d[i];
-            double& mx = st == 0 ? m[2] : v[3];
-            double sq_s = v[1 + st], mx_s = mx;
-            C::residuals(s.x, s.par, s.r, true, sq_s, mx_s, wm);
-            v[1 + st] = s.active ? sq_s : v[1 + st];
-            mx = s.active ? mx_s : mx;
-        }
-        if (mask) {
-            const uint32_t pos_off = __builtin_amdgcn_readfirstlane(a.blob[a.o_slots + 4 * ((size_t)wave_global * SEQ::N + index) + 2]);
-#pragma unroll
-            for (int ci = 0; ci < C::NC; ++ci) {
-                const uint32_t at = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(table, lane * 4, (int)((pos_off + (uint32_t)ci * C::STRIDE) * 4u), 0);
-                if (s.active) mask[at] = 0;
+                for (int i = 0; i < C::NV; ++i) s.x[i] = *reinterpret_cast<const lds_f64_t*>(reinterpret_cast<const char*>(out_lds) + s.ids[i]);
             }
-        }
-        if constexpr (IO == 2) {
-            if (s.active) {
+            unsigned long long wm = 0;
+            C::residuals(s.x, s.par, s.r, true, v[0], m[0], wm);
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                C::solve_f(f.F[st], s.r, s.d, m[1 + 2 * st], range);
+#pragma unroll
+                for (int i = 0; i < C::NV; ++i) s.x[i] = s.x[i] + s.d[i];
+                C::residuals(s.x, s.par, s.r, true, v[1 + st], st == 0 ? m[2] : v[3], wm);
+            }
+            if (mask) {
+                const uint32_t pos_off = __builtin_amdgcn_readfirstlane(a.blob[a.o_slots + 4 * ((size_t)wave_global * SEQ::N + index) + 2]);
+#pragma unroll
+                for (int ci = 0; ci < C::NC; ++ci) {
+                    const uint32_t at = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(table, lane * 4, (int)((pos_off + (uint32_t)ci * C::STRIDE) * 4u), 0);
+                    mask[at] = 0;
+                }
+            }
+            if constexpr (IO == 2) {
 #pragma unroll
                 for (int i = 0; i < C::NV; ++i) *reinterpret_cast<lds_f64_t*>(reinterpret_cast<char*>(out_lds) + s.ids[i]) = s.x[i];
-            }
-        } else if constexpr (STAGE) {  // (the values wait in LDS -- this lane's own words, `out_lds` is the wavefront's -- for the stores below)
+            } else if constexpr (STAGE) {  // (the values wait in LDS -- this lane's own words, `out_lds` is the wavefront's -- for the stores below)
 #pragma unroll
-            for (int i = 0; i < C::NV; ++i) out_lds[(var0 + i) * 64 + lane] = s.x[i];
-            var0 += C::NV;
-        } else {
-            if (s.active) {
+                for (int i = 0; i < C::NV; ++i) out_lds[(var0 + i) * 64 + lane] = s.x[i];
+            } else {
 #pragma unroll
                 for (int i = 0; i < C::NV; ++i) store_at(xo, s.ids[i], s.x[i]);
             }
         }
+        var0 += C::NV;
         __builtin_amdgcn_sched_barrier(0);
     });
     // the values this leads to ("every constraint satisfied", lib.rs:305-327: largest < EPS is part of the verdict) -- the
@@ -1288,8 +1310,7 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
         using C = typename class_of<decltype(cls)>::type;
 #pragma unroll
         for (int i = 0; i < C::NV; ++i) {
-            const double x = out_lds[(var0 + i) * 64 + lane];
-            if (s.active) store_at(xo, s.ids[i], x);
+            if (s.ids[0] != kNoInstance) store_at(xo, s.ids[i], out_lds[(var0 + i) * 64 + lane]);
         }
         var0 += C::NV;
     });
@@ -1299,7 +1320,7 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = i < 3 ? reduce_wave_to_last_lane(v[i], OpSum()) : reduce_wave_to_last_lane(v[i], OpMax());
-    unsigned int flags = (__ballot(lane_bad1) != 0 ? 1u : 0u) | (__ballot(lane_bad2) != 0 ? 2u : 0u) | (__ballot(lane_redo) != 0 ? 4u : 0u);
+    unsigned int flags = slot_flags | (__ballot(range.failed()) != 0 ? 4u : 0u);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const double tol = (k & 1) ? a.step_tolerance : a.residual_tolerance;
@@ -1390,7 +1411,7 @@ __device__ __forceinline__ void solve_kernel_fast(const JitArgs& a) {
     } else {
         if (blockIdx.x < a.batch) fast_fetch(seq, a, blockIdx.x);
     }
-    fast_factor(seq, a);
+    const unsigned int slot_flags = fast_factor(seq, a);
     auto drawn_system = [&](unsigned int d) { return (uint64_t)gridDim.x + (uint64_t)(d - a.ticket_base[ticket_c]) * 8u + ticket_c; };
     uint64_t sys = blockIdx.x, sys_n = sys + gridDim.x;
     if (tickets) {
@@ -1407,9 +1428,9 @@ __device__ __forceinline__ void solve_kernel_fast(const JitArgs& a) {
         double v[4];
         unsigned int wave_flags;
         if constexpr (CONTIG)
-            wave_flags = fast_wave<2>(seq, a, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds + kp * PIECE, row_lds + (kp ^ 1u) * PIECE, first_byte, piece_bytes);
+            wave_flags = fast_wave<2>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds + kp * PIECE, row_lds + (kp ^ 1u) * PIECE, first_byte, piece_bytes);
         else
-            wave_flags = fast_wave<1>(seq, a, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds);
+            wave_flags = fast_wave<1>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds);
         uint64_t sys_nn = sys_n + gridDim.x;
         if (tickets && tid == 0) {
             asm volatile("" : "+v"(drawn));
@@ -1505,7 +1526,7 @@ __device__ __forceinline__ void solve_kernel_grid_fast(const JitArgs& a) {
             fast_fetch(seq, a, grid_slot);
         }
     }
-    fast_factor(seq, a);
+    const unsigned int slot_flags = fast_factor(seq, a);
     constexpr int GROUPS = NWAVES * 16;      // a turn at the totals: thread = (value tid & 3, group tid >> 2)
     __shared__ double fast_part[2][4 * 16];  // [parity of k][value][wavefront]: the wavefronts' partials
     __shared__ int fast_pflag[2][16];
@@ -1558,9 +1579,9 @@ __device__ __forceinline__ void solve_kernel_grid_fast(const JitArgs& a) {
             double v[4];
             unsigned int wave_flags;
             if constexpr (CONTIG)
-                wave_flags = fast_wave<2>(seq, a, sys, sys_n, sys_n < a.batch, wave_global, lane, v, row_lds + kp * PIECE, row_lds + (kp ^ 1u) * PIECE, first_byte, piece_bytes);
+                wave_flags = fast_wave<2>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave_global, lane, v, row_lds + kp * PIECE, row_lds + (kp ^ 1u) * PIECE, first_byte, piece_bytes);
             else
-                wave_flags = fast_wave<IO>(seq, a, sys, sys_n, sys_n < a.batch, wave_global, lane, v, IO == 1 ? row_lds : nullptr);
+                wave_flags = fast_wave<IO>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave_global, lane, v, IO == 1 ? row_lds : nullptr);
             stamp();  // 1: both steps taken, stores issued
             if (lane == 63) {
 #pragma unroll
