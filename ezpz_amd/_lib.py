@@ -58,6 +58,11 @@ class CLaunchPolicy(C.Structure):
                 ("front_small_call_wgs_per_round", C.c_uint32)]
 
 
+class CViewport(C.Structure):
+    _fields_ = [("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double),
+                ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
 # every symbol include/ezpz_amd.h declares
 EXPORTS = [
     "ezpz_default_config", "ezpz_device_count", "ezpz_error_string", "ezpz_system_create", "ezpz_system_destroy",
@@ -80,6 +85,7 @@ EXPORTS = [
     "ezpz_debug_call_trace", "ezpz_launch_policy", "ezpz_debug_front_plan", "ezpz_debug_set_stamps", "ezpz_debug_jit_compilations", "ezpz_debug_freedom_exits",
     "ezpz_mixed_create", "ezpz_mixed_destroy", "ezpz_mixed_total_values", "ezpz_mixed_offsets", "ezpz_mixed_solve_device",
     "ezpz_mixed_solve", "ezpz_system_solve_batch_mixed", "ezpz_multi_solve_batch_mixed",
+    "ezpz_system_residual_field", "ezpz_system_residual_field_device", "ezpz_residual_colormap", "ezpz_residual_overlay",
 ]
 
 _lib = None
@@ -178,6 +184,14 @@ def lib():
     L.ezpz_analyze.argtypes = [vp, sz, sz, C.POINTER(CSystemInfo), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.ezpz_system_eval_batch.restype = C.c_int
     L.ezpz_system_eval_batch.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.ezpz_system_residual_field.restype = C.c_int
+    L.ezpz_system_residual_field.argtypes = [vp, vp, u32, u32, C.c_int64, C.POINTER(CViewport), vp, vp, C.POINTER(C.c_uint64)]
+    L.ezpz_system_residual_field_device.restype = C.c_int
+    L.ezpz_system_residual_field_device.argtypes = [vp, vp, u32, u32, C.c_int64, C.POINTER(CViewport), vp, vp, vp, vp]
+    L.ezpz_residual_colormap.restype = None
+    L.ezpz_residual_colormap.argtypes = [vp, sz, vp]
+    L.ezpz_residual_overlay.restype = C.c_int
+    L.ezpz_residual_overlay.argtypes = [vp, C.POINTER(CViewport), C.c_double, C.c_double, C.c_double, C.c_double]
     L.ezpz_system_jacobian_pattern.restype = C.c_int
     L.ezpz_system_jacobian_pattern.argtypes = [vp, vp, vp]
     L.ezpz_system_solve_batch_device.restype = C.c_int

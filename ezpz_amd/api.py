@@ -737,6 +737,13 @@ class System:
         J[:, rows[:zj], cols[:zj]] = jv[:, :zj]
         return r[:, :m], J, deg
 
+    def residual_field(self, x_base, var_x: int, var_y: int, viewport, constraint: Optional[int] = None,
+                       want: Sequence[str] = ("mag", "rgb"), overlay=None):
+        """The residual magnitude as a 2-D field while variables var_x / var_y sweep `viewport` (residual_viz.residual_field)."""
+        from . import residual_viz
+
+        return residual_viz.residual_field(self, x_base, var_x, var_y, viewport, constraint, want, overlay)
+
     def freedom_batch(self, x: np.ndarray):
         """FreedomAnalysis (find_dof.rs) of each value vector.  Returns (mask [batch, n] uint8, participation)."""
         n = self.n_vars

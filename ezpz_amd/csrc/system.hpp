@@ -272,6 +272,10 @@ struct EzpzSystem {
     DevBuf<uint8_t> mask_dev;
     DevBuf<uint64_t> log_dev;
     DevBuf<double> gws_dev;
+    // residual fields (residual_field.hip): the first launch's list and sums; the host entry's base values and images
+    DevBuf<unsigned char> field_scratch;
+    DevBuf<double> field_x, field_mag;
+    DevBuf<uint8_t> field_rgb;
     // the pipelined host-to-host path (registered caller buffers): one stream per stage -- copies in, kernels, copies
     // out -- and a ring of device buffers, each with an event per stage
     struct Pipe {

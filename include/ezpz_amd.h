@@ -232,6 +232,37 @@ int ezpz_system_eval_batch(EzpzSystem* sys, const double* x, size_t batch, doubl
                            uint32_t* degenerate_count_out);
 int ezpz_system_jacobian_pattern(const EzpzSystem* sys, uint32_t* rows, uint32_t* cols);
 
+/* ---- residual field (ezpz/src/residual_viz.rs, feature `residual-viz`) -----------------------------------
+ * The residual magnitude as a 2-D scalar field while two variables of the system sweep a viewport: pixel (px, py) of a
+ * width x height image is the point x = x_min + (x_max - x_min) * (px + 0.5) / width, likewise y (residual_viz.rs:58-62;
+ * row 0 = y_min), put into variables var_x / var_y of the value vector x_base (n_vars values, caller's numbering).
+ * `constraint` is a position in the system's constraint list -- the magnitude is then the absolute value of its residual,
+ * or sqrt(r0*r0 + r1*r1) for a kind of two rows (:240, :294) -- or -1 for all constraints: sqrt of the sum of squares, the
+ * constraints that use a swept variable summed per pixel in list order onto the sum of all others at x_base, which is
+ * computed once per call.  Residuals are unweighted, as the reference draws them; a degenerate guard leaves 0 and the
+ * pixel is counted in degenerate_pixels_out (optional; with -1 a guard among the constraints no pixel changes counts
+ * every pixel).  Outputs, at least one of them: mag_out [height][width] doubles, rgb_out [height][width][3] bytes of the
+ * reference's colour map (:72-81, the function of ezpz_residual_colormap).  The _device form takes device pointers and only
+ * enqueues on `stream`; both keep their list of constraints in scratch memory of the EzpzSystem: calls on one system
+ * must not overlap in time.  The vector stores need width % 4 == 0, mag on 16 bytes and rgb on 4; anything else is
+ * stored pixel by pixel, same values.
+ * ezpz_residual_colormap and ezpz_residual_overlay run on the host and need no device: the colour of n magnitudes, and
+ * draw_solver_overlay (:186-200) on an rgb image of the viewport's size -- an arrow over half the way from the example point
+ * to the solution, a red disc at the example, a green one at the solution. */
+typedef struct EzpzViewport {
+    double x_min, x_max, y_min, y_max;
+    uint32_t width, height;
+} EzpzViewport;
+int ezpz_system_residual_field(EzpzSystem* sys, const double* x_base, uint32_t var_x, uint32_t var_y, int64_t constraint,
+                               const EzpzViewport* viewport, double* mag_out, uint8_t* rgb_out,
+                               uint64_t* degenerate_pixels_out);
+int ezpz_system_residual_field_device(EzpzSystem* sys, const double* x_base_dev, uint32_t var_x, uint32_t var_y,
+                                      int64_t constraint, const EzpzViewport* viewport, double* mag_dev, uint8_t* rgb_dev,
+                                      uint64_t* degenerate_pixels_dev, void* stream);
+void ezpz_residual_colormap(const double* mag, size_t n, uint8_t* rgb);
+int ezpz_residual_overlay(uint8_t* rgb, const EzpzViewport* viewport, double example_x, double example_y,
+                          double solution_x, double solution_y);
+
 /* ---- numeric phase -------------------------------------------------------------------------------
  * Replaces Model::solve_levenberg_marquardt (ezpz/src/solver/newton.rs:29-145) followed by the
  * unsatisfied check of solve_inner (ezpz/src/lib.rs:305-327), for `batch` independent systems that
