@@ -86,6 +86,7 @@ EXPORTS = [
     "ezpz_mixed_create", "ezpz_mixed_destroy", "ezpz_mixed_total_values", "ezpz_mixed_offsets", "ezpz_mixed_solve_device",
     "ezpz_mixed_solve", "ezpz_system_solve_batch_mixed", "ezpz_multi_solve_batch_mixed",
     "ezpz_system_residual_field", "ezpz_system_residual_field_device", "ezpz_residual_colormap", "ezpz_residual_overlay",
+    "ezpz_constraint_has_param", "ezpz_system_solve_batch_params_device", "ezpz_system_solve_batch_params",
 ]
 
 _lib = None
@@ -198,6 +199,12 @@ def lib():
     L.ezpz_system_solve_batch_device.argtypes = [vp, vp, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32, vp]
     L.ezpz_system_solve_batch.restype = C.c_int
     L.ezpz_system_solve_batch.argtypes = [vp, vp, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32]
+    L.ezpz_constraint_has_param.restype = C.c_int
+    L.ezpz_constraint_has_param.argtypes = [vp]
+    L.ezpz_system_solve_batch_params_device.restype = C.c_int
+    L.ezpz_system_solve_batch_params_device.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32, vp]
+    L.ezpz_system_solve_batch_params.restype = C.c_int
+    L.ezpz_system_solve_batch_params.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32]
     L.ezpz_solve_inner.restype = C.c_int
     L.ezpz_solve_inner.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(CConfig), vp, vp, vp, sz, C.POINTER(COutcome)]
     L.ezpz_solve.restype = C.c_int

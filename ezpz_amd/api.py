@@ -773,6 +773,53 @@ class System:
             raise NonLinearSystemError(rc)
 
 
+    def _positions(self, positions) -> np.ndarray:
+        p = np.asarray(positions)
+        if p.ndim != 1 or (p.size and not np.issubdtype(p.dtype, np.integer)) or (p.size and (p.min() < 0 or p.max() > 0xFFFFFFFF)):
+            raise ValueError("positions: a 1-D sequence of constraint positions (non-negative integers)")
+        return np.ascontiguousarray(p, dtype=np.uint32)
+
+    def solve_batch_params(self, x0: np.ndarray, positions, params: np.ndarray, config: Optional[Config] = None,
+                           want_mask: bool = False):
+        """`ezpz_system_solve_batch_params`: one topology, a dimension set per system.  params [batch, len(positions)] replaces
+        records[positions[j]]["param"] for system b (in that field's units); constraints not listed keep their values.
+        Returns what solve_batch returns."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, max(self.n_vars, 1))
+        batch = x0.shape[0]
+        pos = self._positions(positions)
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.size != batch * len(pos) or (params.ndim == 2 and params.shape != (batch, len(pos))) or params.ndim > 2:
+            raise ValueError(f"params: expected shape ({batch}, {len(pos)}), got {params.shape}")
+        cfg = (config or Config())._c()
+        x = np.empty_like(x0)
+        st = np.zeros(batch, dtype=STATUS_DTYPE)
+        mask = np.zeros((batch, max(len(self.records), 1)), dtype=np.uint8) if want_mask else None
+        rc = lib().ezpz_system_solve_batch_params(self._h, x0.ctypes.data, pos.ctypes.data if len(pos) else None, len(pos),
+                                                  params.ctypes.data if len(pos) else None, batch, C.byref(cfg), x.ctypes.data,
+                                                  st.ctypes.data, mask.ctypes.data if want_mask else None, None, 0)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return x, st, mask
+
+    def solve_batch_params_device(self, x0_ptr: int, positions, params_ptr: int, batch: int, x_out_ptr: int, status_ptr: int,
+                                  mask_ptr: int = 0, stream: int = 0, config: Optional[Config] = None) -> None:
+        """Device pointers and a hipStream_t handle, like solve_batch_device; `positions` is a host sequence and params_ptr
+        addresses [batch, len(positions)] doubles on the device."""
+        pos = self._positions(positions)
+        cfg = (config or Config())._c()
+        rc = lib().ezpz_system_solve_batch_params_device(self._h, x0_ptr, pos.ctypes.data if len(pos) else None, len(pos),
+                                                         params_ptr or None, batch, C.byref(cfg), x_out_ptr, status_ptr,
+                                                         mask_ptr or None, None, 0, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+
+def constraint_has_param(record) -> bool:
+    """`ezpz_constraint_has_param`: whether the residual of this constraint record (its kind and tag) reads `param`."""
+    rec = stack_records([record])
+    return bool(lib().ezpz_constraint_has_param(rec.ctypes.data))
+
+
 class MultiSystem:
     """One analysed topology resident on several devices of the node (`ezpz_multi_*`): a batch is sharded contiguously
     over them, one host worker thread per device, every shard over its own device's host link.  `device_mask` bit d =

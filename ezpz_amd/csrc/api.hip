@@ -22,6 +22,8 @@ int ezpz_launch_policy(int compute_units, EzpzLaunchPolicy* out) {
     return EZPZ_OK;
 }
 
+int ezpz_constraint_has_param(const EzpzConstraint* c) { return c && kind_has_param(c->kind, c->tag) ? 1 : 0; }
+
 int ezpz_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {
@@ -84,6 +86,8 @@ int ezpz_system_create(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, int
     call_stamp(COLD_ANALYSED);
     if (rc != EZPZ_OK) return rc;
     if (!have_device) return EZPZ_ERR_NO_DEVICE;
+    s->host_has_param.resize(n_cs);
+    for (size_t i = 0; i < n_cs; ++i) s->host_has_param[i] = kind_has_param(cs[i].kind, cs[i].tag) ? 1 : 0;
     EZPZ_ON_DEVICE(device);
     if (!s->program_deferred.load()) {
         HIP_TRY(hipMalloc(&s->dev_program, blob.size()));

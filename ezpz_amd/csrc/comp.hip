@@ -14,9 +14,9 @@ namespace ezpz {
 
 namespace {
 
-template <bool LIN>
+template <bool LIN, bool PAR>
 int launch_build(const CompPlan& plan, const CompArgs& args, int device, int cus, size_t lds_limit, hipStream_t stream) {
-    auto kernel = comp_solve_kernel<LIN>;
+    auto kernel = comp_solve_kernel<LIN, PAR>;
     static std::atomic<bool> raised[16];  // per kernel build and device (see launch_kernel in launch.hip)
     if (plan.lds_bytes > 48 * 1024 && !raised[device & 15].load(std::memory_order_acquire)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -65,8 +65,15 @@ int comp_launch(const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch
     a.scratch_row0 = plan.rows_persistent;
     a.scratch_rows = plan.scratch_rows;
     a.red_row0 = plan.rows_persistent + plan.n_waves * plan.scratch_rows;
-    return plan.linear ? launch_build<true>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream))
-                       : launch_build<false>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream));
+    if (L.params) {  // (ezpz_system_solve_batch_params: the builds whose lanes take their parameters per system)
+        a.params = L.params;
+        a.par_overlay = L.par_overlay;
+        a.n_param = L.n_param;
+        return plan.linear ? launch_build<true, true>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream))
+                           : launch_build<false, true>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream));
+    }
+    return plan.linear ? launch_build<true, false>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream))
+                       : launch_build<false, false>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream));
 }
 
 uint64_t batch_launch_waves(int cus) {

@@ -48,6 +48,11 @@ struct CompArgs {
     uint32_t scratch_row0, scratch_rows;  // LDS rows: first scratch row, rows per wavefront
     uint32_t red_row0;                    // LDS row of the reduction scratch (2 x 3 x 16 doubles), flag words, warning counters
     DoneWord done;                        // one-call launches: the completion word (dev_types.hpp)
+    // PAR builds: every system's own values for the parameters the call drives, and the overlay that says which lane's
+    // constraint takes which of them (CompLaunch::params / par_overlay)
+    const double* params;
+    const uint32_t* par_overlay;
+    uint32_t n_param;
 };
 
 namespace dev {
@@ -134,7 +139,7 @@ struct CompRed {
 // The chunk descriptor (CompChunk, 32 words) in scalar registers.
 struct CompChunkRegs {
     uint32_t count, nv, m, ncons, n_ops, ops_off, cons_off, row0;
-    uint32_t o_d, o_r0, o_r1, o_j, o_wm, s_l, stride, ids_off, par_off, pos_off;
+    uint32_t o_d, o_r0, o_r1, o_j, o_wm, s_l, stride, ids_off, par_off, pos_off, ovl_off;
 };
 __device__ __forceinline__ CompChunkRegs comp_load_chunk(comp_cptr p) {
     const CompRec8 h0 = comp_load8(p), h1 = comp_load8(p + 8), h2 = comp_load8(p + 16);
@@ -143,7 +148,7 @@ __device__ __forceinline__ CompChunkRegs comp_load_chunk(comp_cptr p) {
     c.n_ops = h0.w[4], c.ops_off = h0.w[5], c.cons_off = h0.w[6], c.row0 = h0.w[7];
     c.o_d = h1.w[0], c.o_r0 = h1.w[1], c.o_r1 = h1.w[2], c.o_j = h1.w[3], c.o_wm = h1.w[4];
     c.s_l = h1.w[5], c.stride = h1.w[6], c.ids_off = h1.w[7];
-    c.par_off = h2.w[0], c.pos_off = h2.w[1];
+    c.par_off = h2.w[0], c.pos_off = h2.w[1], c.ovl_off = h2.w[2];
     return c;
 }
 
@@ -172,7 +177,10 @@ __device__ __forceinline__ DevCon comp_make_con(const CompRec8& a, const CompRec
 // LIN: every class is linear with constant Jacobian (no Jacobian storage, no warnings);
 // otherwise the general build (all 25 kinds, Jacobian values in LDS).  Up to 8 wavefronts per workgroup, two
 // workgroups per CU when the state allows it.
-template <bool LIN>
+// PAR: the build of ezpz_system_solve_batch_params: a lane's parameter is its system's own value where the call's overlay
+// names one (each value has exactly one reader -- the lane of its component -- so it is read where the caller left it), else
+// the table's; the other builds are untouched.
+template <bool LIN, bool PAR = false>
 __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using namespace dev;
@@ -203,6 +211,15 @@ __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
     for (uint64_t sys = blockIdx.x; sys < a.batch; sys += gridDim.x, parity ^= 1u) {
         const double* x0 = a.x0 + sys * a.n_row;
         int* nwarn = nwarn2 + parity;
+        // constraint ci's parameter for this lane (`par`, `ovl`: the chunk's tables at this lane)
+        auto param_of = [&](const double* par, const uint32_t* ovl, uint32_t ci, uint32_t stride) {
+            double p = par[(size_t)ci * stride];
+            if constexpr (PAR) {
+                const uint32_t slot = ovl[(size_t)ci * stride];
+                if (slot != 0xFFFFFFFFu) p = a.params[sys * a.n_param + slot];
+            }
+            return p;
+        };
         auto log_warning = [&](uint32_t pass, uint32_t pos) {  // Warning::Degenerate, every evaluation (solver.rs:340-346)
             const int idx = atomicAdd(nwarn, 1);
             if (a.warn_log && (uint32_t)idx < a.warn_cap) a.warn_log[sys * a.warn_cap + idx] = ((uint64_t)pass << 32) | pos;
@@ -217,12 +234,13 @@ __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
             unsigned long long wmask = 0;
             const double* par = reinterpret_cast<const double*>(a.prog + K.par_off) + lane;
             const uint32_t* posp = a.prog + K.pos_off + lane;
-            double p_next = K.ncons ? par[0] : 0.0;
+            const uint32_t* ovl = PAR ? a.par_overlay + K.ovl_off + lane : nullptr;
+            double p_next = K.ncons ? param_of(par, ovl, 0, K.stride) : 0.0;
             for (uint32_t ci = 0; ci < K.ncons; ++ci) {
                 const CompRec8 ra = comp_load8(prog + K.cons_off + ci * kCompConWords);
                 const CompRec8 rb = comp_load8(prog + K.cons_off + ci * kCompConWords + 8);
                 const double param = p_next;
-                if (ci + 1 < K.ncons) p_next = par[(size_t)(ci + 1) * K.stride];
+                if (ci + 1 < K.ncons) p_next = param_of(par, ovl, ci + 1, K.stride);
                 const DevCon c = comp_make_con(ra, rb, param);
                 double r0, r1;
                 const bool deg = con_residual<LIN>(c, xs, r0, r1);
@@ -267,12 +285,13 @@ __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
             if constexpr (!LIN) {
                 const double* par = reinterpret_cast<const double*>(a.prog + K.par_off) + lane;
                 const uint32_t* posp = a.prog + K.pos_off + lane;
-                double p_next = K.ncons ? par[0] : 0.0;
+                const uint32_t* ovl = PAR ? a.par_overlay + K.ovl_off + lane : nullptr;
+                double p_next = K.ncons ? param_of(par, ovl, 0, K.stride) : 0.0;
                 for (uint32_t ci = 0; ci < K.ncons; ++ci) {
                     const CompRec8 ra = comp_load8(prog + K.cons_off + ci * kCompConWords);
                     const CompRec8 rb = comp_load8(prog + K.cons_off + ci * kCompConWords + 8);
                     const double param = p_next;
-                    if (ci + 1 < K.ncons) p_next = par[(size_t)(ci + 1) * K.stride];
+                    if (ci + 1 < K.ncons) p_next = param_of(par, ovl, ci + 1, K.stride);
                     const DevCon c = comp_make_con(ra, rb, param);
                     JacWriter<RowRef> w;
                     w.jv = P + K.o_j;

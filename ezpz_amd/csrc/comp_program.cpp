@@ -42,7 +42,7 @@ struct Component {
 struct ClassLayout {  // what every chunk of a class shares (copied into its CompChunk)
     uint32_t nv = 0, m = 0, zj = 0, ncons = 0, n_ops = 0, ops_off = 0, cons_off = 0;
     uint32_t rows_p = 0, o_d = 0, o_r0 = 0, o_r1 = 0, o_j = 0, o_wm = 0, s_l = 0;
-    uint32_t ninst_pad = 0, ids_off = 0, par_off = 0, pos_off = 0;
+    uint32_t ninst_pad = 0, ids_off = 0, par_off = 0, pos_off = 0, ovl_off = 0;
 };
 
 struct Class {
@@ -721,6 +721,9 @@ bool comp_plan_build(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, const
         for (uint32_t ci = 0; ci < ncons; ++ci)
             for (uint32_t i = 0; i < ninst; ++i)
                 blob[H.pos_off + (size_t)ci * H.ninst_pad + i] = comps[cl.instances[i]].cons[Q.cons[ci].pos];
+        // (the overlay of a call with driven parameters is a table of its own, laid out like this one: comp_param_overlay)
+        H.ovl_off = plan.ovl_words;
+        plan.ovl_words += ncons * H.ninst_pad;
         if (blob.size() > (64u << 20)) return false;
 
         plan.zj += (uint64_t)zj * ninst;
@@ -792,6 +795,7 @@ bool comp_plan_build(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, const
             ch.ids_off = H.ids_off + chunks[c].inst0;
             ch.par_off = H.par_off + 2 * chunks[c].inst0;
             ch.pos_off = H.pos_off + chunks[c].inst0;
+            ch.ovl_off = H.ovl_off + chunks[c].inst0;
             const uint32_t* p = reinterpret_cast<const uint32_t*>(&ch);
             blob.insert(blob.end(), p, p + sizeof(CompChunk) / 4);
             row += chunks[c].rows;
@@ -1399,6 +1403,21 @@ bool batch_plan_build(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, Batc
         std::fputc('\n', stderr);
     }
     return true;
+}
+
+// The interpreter's overlay for a call that drives parameters (ezpz_system_solve_batch_params): a table laid out like the
+// chunks' parameter tables -- [constraint of the class][instance], CompChunk::ovl_off -- that holds, for the constraint a lane
+// evaluates, its place in the call's list (slot_of_pos[caller's position]) or kNoParamSlot.  The parameter tables themselves, and
+// everything the plan derives from the topology, stay as they are: no value of a parameter went into classes or programs.
+void comp_param_overlay(const CompPlan& plan, const uint32_t* slot_of_pos, std::vector<uint32_t>& out) {
+    out.assign(std::max<uint32_t>(plan.ovl_words, 1), 0xFFFFFFFFu);
+    const CompChunk* chunks = reinterpret_cast<const CompChunk*>(plan.blob.data() + plan.o_chunks);
+    for (uint32_t c = 0; c < plan.n_chunks; ++c) {
+        const CompChunk& ch = chunks[c];
+        for (uint32_t ci = 0; ci < ch.ncons; ++ci)
+            for (uint32_t l = 0; l < ch.count; ++l)
+                out[ch.ovl_off + (size_t)ci * ch.stride + l] = slot_of_pos[plan.blob[ch.pos_off + (size_t)ci * ch.stride + l]];
+    }
 }
 
 }  // namespace ezpz

@@ -73,7 +73,8 @@ struct CompChunk {
     uint32_t ids_off;               // u32 [nv][stride]     caller's variable id      (word offsets, first instance
     uint32_t par_off;               // f64 [ncons][stride]  constraint parameter       of the chunk folded in)
     uint32_t pos_off;               // u32 [ncons][stride]  caller's constraint position
-    uint32_t pad[14];
+    uint32_t ovl_off;               // u32 [ncons][stride]  place among a call's driven parameters, in the call's OWN table (CompLaunch::par_overlay)
+    uint32_t pad[13];
 };
 static_assert(sizeof(CompChunk) == 32 * 4, "CompChunk layout");
 
@@ -86,6 +87,7 @@ struct CompPlan {
     bool unit_weights = true;
     uint32_t rows_persistent = 0, scratch_rows = 0;  // LDS rows: all chunks' state; per wavefront scratch
     uint32_t lds_bytes = 0;
+    uint32_t ovl_words = 0;       // words of a driven-parameter overlay (comp_param_overlay)
     uint32_t n_vars = 0, n_cons = 0, n_rows = 0;
     uint32_t max_levels = 0;
     uint64_t zj = 0, za = 0, zl = 0;  // totals over all components (EzpzSystemInfo)
@@ -130,7 +132,13 @@ struct CompLaunch {
     // lane-per-system kernel only: the systems of one topology inside a ragged batch, in place (jit_kernel.hip.hpp: LaneArgs)
     const uint64_t* row_offset = nullptr;
     const uint32_t* sys_of = nullptr;
+    // interpreter only (ezpz_system_solve_batch_params): params[sys * n_param + slot] replaces the table's parameter wherever
+    // par_overlay (comp_param_overlay) names a slot; null: the plan's own parameters
+    const double* params = nullptr;
+    const uint32_t* par_overlay = nullptr;
+    uint32_t n_param = 0;
 };
+void comp_param_overlay(const CompPlan& plan, const uint32_t* slot_of_pos, std::vector<uint32_t>& out);
 int comp_launch(const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch& launch, int device, int cus,
                 size_t lds_limit, void* stream);
 

@@ -50,6 +50,31 @@ static constexpr KindInfo kKinds[25] = {
 };
 // clang-format on
 
+// Whether the residual of a constraint of this kind and tag reads EzpzConstraint::param (constraint_eval.hip.hpp: every
+// `c.param` of con_residual; con_jacobian reads it for the same kinds): the ten kinds with a length or a value, and the three
+// angle kinds unless their tag says parallel or perpendicular (rot_for takes the rotation from the tag alone then).
+inline bool kind_has_param(uint32_t kind, uint32_t tag) {
+    switch (kind) {
+    case EZPZ_DISTANCE:
+    case EZPZ_VERTICAL_DISTANCE:
+    case EZPZ_HORIZONTAL_DISTANCE:
+    case EZPZ_FIXED:
+    case EZPZ_CIRCLE_RADIUS:
+    case EZPZ_ARC_RADIUS:
+    case EZPZ_POINT_LINE_DISTANCE:
+    case EZPZ_VERTICAL_POINT_LINE_DISTANCE:
+    case EZPZ_HORIZONTAL_POINT_LINE_DISTANCE:
+    case EZPZ_ARC_LENGTH:
+        return true;
+    case EZPZ_LINES_AT_ANGLE:
+    case EZPZ_ARC_ANGLE:
+    case EZPZ_POINTS_AT_ANGLE:
+        return tag != EZPZ_ANGLE_PARALLEL && tag != EZPZ_ANGLE_PERPENDICULAR;
+    default:
+        return false;
+    }
+}
+
 // The nine kinds whose residual is linear in the variables (constant Jacobian, no guard, no libm call).
 inline bool kind_is_linear(uint32_t kind) {
     switch (kind) {

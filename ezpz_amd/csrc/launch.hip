@@ -3,46 +3,11 @@
 // translation unit that instantiates the list-walk / record-walk kernels (lm_kernel.hip.hpp).
 #include "system.hpp"
 
-#include "lm_kernel.hip.hpp"
+#include "list_walk_launch.hip.hpp"
 
 using namespace ezpz;
 
 namespace {
-
-template <int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool DENSE = false, int REC = 0>
-int launch_kernel(EzpzSystem& s, const SolveArgs& args, uint32_t grid, hipStream_t stream) {
-    auto kernel = lm_solve_kernel<TEAM, MODE, LDSWS, PLDS, LIN, false, DENSE, REC>;
-    // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel, not to the system: raised once per kernel
-    // build and device, to everything the device allows, so that systems of different sizes sharing a build never
-    // lower each other's limit
-    static std::atomic<bool> raised[16];
-    if (s.lds_bytes > 48 * 1024 && !raised[s.device & 15].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)s.lim.lds_bytes));
-        raised[s.device & 15].store(true, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(s.block_threads), s.lds_bytes, stream, args);
-    HIP_TRY(hipGetLastError());
-    return EZPZ_OK;
-}
-
-// Every team shape comes in two builds: all 25 kinds, or the nine linear kinds only (`linear_only` topologies).
-template <int TEAM, int MODE, bool LDSWS, bool PLDS>
-int launch_variant(EzpzSystem& s, const SolveArgs& args, uint32_t grid, hipStream_t stream) {
-    if (s.linear_only) return launch_kernel<TEAM, MODE, LDSWS, PLDS, true>(s, args, grid, stream);
-    return launch_kernel<TEAM, MODE, LDSWS, PLDS, false>(s, args, grid, stream);
-}
-
-template <int TEAM>
-int launch_sub(EzpzSystem& s, const SolveArgs& args, uint32_t grid, hipStream_t stream) {
-    if constexpr (TEAM == 4) {  // <= 8 variables: dense factor layout, solved in registers (always staged)
-        if (s.counts.dense)
-            return s.linear_only ? launch_kernel<TEAM, MODE_SUB, true, true, true, true>(s, args, grid, stream)
-                                 : launch_kernel<TEAM, MODE_SUB, true, true, false, true>(s, args, grid, stream);
-    }
-    return s.prog_in_lds ? launch_variant<TEAM, MODE_SUB, true, true>(s, args, grid, stream)
-                         : launch_variant<TEAM, MODE_SUB, true, false>(s, args, grid, stream);
-}
 
 std::mutex g_grid_mu;
 hipEvent_t g_grid_event[16] = {};  // per device: completion of the last launch of this process whose workgroups wait for each other
@@ -54,17 +19,6 @@ bool stream_capturing(hipStream_t stream) {
         capturing = hipStreamCaptureStatusNone;
     }
     return capturing != hipStreamCaptureStatusNone;
-}
-
-// The system's workspace in global memory -- the lanes kernel's, the list walk's when its workspace or its Jacobian lives there -- is
-// one per system object: `launch` runs behind the last launch that used it, whatever stream that was, and leaves its own completion
-// behind when it succeeds.
-template <class Launch>
-int on_workspace(EzpzSystem& s, hipStream_t stream, Launch&& launch) {
-    HIP_TRY(s.lanes_done ? hipStreamWaitEvent(stream, s.lanes_done, 0) : hipEventCreateWithFlags(&s.lanes_done, hipEventDisableTiming));
-    const int rc = launch();
-    if (rc == EZPZ_OK) HIP_TRY(hipEventRecord(s.lanes_done, stream));
-    return rc;
 }
 
 }  // namespace
@@ -252,22 +206,6 @@ int launch_jit_grid(EzpzSystem& s, CompLaunch L, hipStream_t stream) {
                            [&] { return jit_launch(s, L, stream, slots, lists ? fast_slots : 0); });
 }
 
-CompLaunch comp_launch_args(const SolveArgs& args) {
-    CompLaunch L{};
-    L.x0 = args.x0;
-    L.x_out = args.x_out;
-    L.status = args.status;
-    L.unsat_mask = args.unsat_mask;
-    L.warn_log = args.warn_log;
-    L.warn_cap = args.warn_cap;
-    L.batch = args.batch;
-    L.max_iterations = args.max_iterations;
-    L.residual_tolerance = args.residual_tolerance;
-    L.step_tolerance = args.step_tolerance;
-    L.initial_lambda = args.initial_lambda;
-    L.done = args.done;
-    return L;
-}
 
 // The list-walk teams of a system (lm_kernel.hip.hpp), whatever their shape: sub-wavefront teams, workgroups with their
 // workspace in LDS or in global memory, grid teams.  (launch() holds the system's launch lock.)
@@ -275,72 +213,12 @@ int launch_list_walk(EzpzSystem& s, SolveArgs& args, hipStream_t stream) {
     // a resident launch (DoneWord::request) is one workgroup that keeps nothing another launch of this system waits for:
     // not a grid team, not a shape whose workspace or Jacobian lives in the system's one global scratch
     if (s.grid_wgs > 1 || args.batch != 1 || (s.mode != MODE_SUB && (!s.lds_ws || (s.rec && s.rec_jglobal)))) args.done.request = nullptr;
-    uint32_t grid;
-    if (s.mode == MODE_SUB) {
-        const uint32_t tpb = s.block_threads / s.team_size;
-        uint64_t blocks = (args.batch + tpb - 1) / tpb;
-        grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)s.lim.cus * 32);
-        switch (s.team_size) {
-        case 1: return launch_sub<1>(s, args, grid, stream);
-        case 2: return launch_sub<2>(s, args, grid, stream);
-        case 4: return launch_sub<4>(s, args, grid, stream);
-        case 8: return launch_sub<8>(s, args, grid, stream);
-        case 16: return launch_sub<16>(s, args, grid, stream);
-        case 32: return launch_sub<32>(s, args, grid, stream);
-        default: return launch_sub<64>(s, args, grid, stream);
-        }
-    }
-    if (s.grid_wgs > 1) {
+    if (s.mode != MODE_SUB && s.grid_wgs > 1) {
         // (a grid team starts every system from its guesses: its shared warning counter has no resumed value)
         if (args.resume) return EZPZ_ERR_INVALID_ARGUMENT;
         return s.linear_only ? launch_grid_kernel<true>(s, args, stream) : launch_grid_kernel<false>(s, args, stream);
     }
-    const uint32_t per_cu = s.lds_ws ? (uint32_t)std::max<size_t>(1, s.lim.lds_bytes / std::max<size_t>(s.lds_bytes, 1))
-                                     : 2048u / s.block_threads;
-    // Workgroups: twice what the device holds at once where a workgroup serves several systems side by side (sub-wavefront teams)
-    // or owns a workspace in global memory; a workgroup per system -- up to 32 times what the device holds -- where it solves one
-    // system at a time in its LDS: the dispatcher then hands a free place the next system, whatever the systems before it took
-    // (a jittered batch's systems take 4 to 10 iterations) and whoever else occupies places on the device -- sketch150 x 32 768
-    // at x1 / x2 / x4 / x8 / x32: 3.58 / 3.62 / 3.70 / 3.82 / 3.91 M solves/s; starting a workgroup costs a few microseconds
-    // against the ~250 of a system.
-    // (a list of systems on the device -- the lanes' stragglers: `batch` is the list's capacity, the systems are a few hundred)
-    const uint32_t rounds = (s.lds_ws && s.mode != MODE_SUB && !args.sys_list) ? 32u : 2u;
-    grid = (uint32_t)std::min<uint64_t>(args.batch, (uint64_t)s.lim.cus * std::min<uint32_t>(per_cu, 8) * rounds);
-    if (s.rec && s.rec_jglobal)  // (a workgroup's Jacobian values in global memory: at most 256 MiB of them per system object)
-        grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(grid, (1ull << 25) / ((s.counts.zj + 2) & ~1ull)));
-    if (!s.lds_ws) {
-        // the workspace in global memory is one per system object (like the lanes kernel's)
-        int rc = s.gws_dev.ensure((size_t)grid * s.ws_doubles);
-        if (rc != EZPZ_OK) return rc;
-        args.gws = s.gws_dev.p;
-        return on_workspace(s, stream, [&] {
-            return s.mode == MODE_PART ? launch_variant<64, MODE_PART, false, false>(s, args, grid, stream)
-                   : !s.rec            ? launch_variant<64, MODE_WGB, false, false>(s, args, grid, stream)
-                   : s.linear_only     ? launch_kernel<64, MODE_WGB, false, false, true, false, 2>(s, args, grid, stream)
-                                       : launch_kernel<64, MODE_WGB, false, false, false, false, 2>(s, args, grid, stream);
-        });
-    }
-    const bool staged = s.prog_in_lds;
-    if (s.mode == MODE_PART)
-        return staged ? launch_variant<64, MODE_PART, true, true>(s, args, grid, stream)
-                      : launch_variant<64, MODE_PART, true, false>(s, args, grid, stream);
-    if (!s.rec)
-        return staged ? launch_variant<64, MODE_WGB, true, true>(s, args, grid, stream)
-                      : launch_variant<64, MODE_WGB, true, false>(s, args, grid, stream);
-    // one connected system, its linear solve as a record walk
-    auto walk = [&] {
-        if (s.linear_only)
-            return staged ? launch_kernel<64, MODE_WGB, true, true, true, false, 1>(s, args, grid, stream)
-                          : launch_kernel<64, MODE_WGB, true, false, true, false, 1>(s, args, grid, stream);
-        return staged ? launch_kernel<64, MODE_WGB, true, true, false, false, 1>(s, args, grid, stream)
-                      : launch_kernel<64, MODE_WGB, true, false, false, false, 1>(s, args, grid, stream);
-    };
-    if (!s.rec_jglobal) return walk();
-    // the Jacobian's values of every workgroup in global memory: one array per system object, like the workspace
-    int rc = s.gws_dev.ensure((size_t)grid * ((s.counts.zj + 2) & ~1u));
-    if (rc != EZPZ_OK) return rc;
-    args.gws = s.gws_dev.p;
-    return on_workspace(s, stream, walk);
+    return list_walk_one_workgroup<false>(s, args, s.lds_bytes, stream);
 }
 
 // launch() asks its routes in turn; each serves the call (EZPZ_OK), fails it (an error), or leaves it to the next (kNextRoute).
@@ -496,6 +374,34 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
     if (!sys || (batch && (!x_out_dev || !status_dev))) return EZPZ_ERR_INVALID_ARGUMENT;
     if (batch && sys->counts.n_vars && !x0_dev) return EZPZ_ERR_INVALID_ARGUMENT;
     EZPZ_ON_DEVICE(sys->device);
+    SolveArgs a = solve_args_for(sys, x0_dev, batch, cfg, x_out_dev, status_dev, unsat_mask_dev, warn_log_dev, warn_cap);
+    a.done = done;
+    const int rc = launch(*sys, a, static_cast<hipStream_t>(stream));
+    if (resident) *resident = rc == EZPZ_OK && a.done.request != nullptr;
+    return rc;
+}
+
+// The same call as the component, lane and wavefront kernels take it.
+CompLaunch comp_launch_args(const SolveArgs& args) {
+    CompLaunch L{};
+    L.x0 = args.x0;
+    L.x_out = args.x_out;
+    L.status = args.status;
+    L.unsat_mask = args.unsat_mask;
+    L.warn_log = args.warn_log;
+    L.warn_cap = args.warn_cap;
+    L.batch = args.batch;
+    L.max_iterations = args.max_iterations;
+    L.residual_tolerance = args.residual_tolerance;
+    L.step_tolerance = args.step_tolerance;
+    L.initial_lambda = args.initial_lambda;
+    L.done = args.done;
+    return L;
+}
+
+// The argument block of the list-walk kernels for a call on `sys` (device pointers; no completion word).
+SolveArgs solve_args_for(EzpzSystem* sys, const double* x0_dev, size_t batch, const EzpzConfig* cfg, double* x_out_dev,
+                         EzpzStatus* status_dev, uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap) {
     SolveArgs a{};
     a.p = sys->view;
     a.x0 = x0_dev;
@@ -517,7 +423,6 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
     a.stamps = g_stamps;
     a.unit_weights = sys->unit_weights ? 1u : 0u;
     a.grid_wgs = 1;  // (gws, the grid team's scratch, the list of systems and the resumed states: none)
-    a.done = done;
     if (sys->rec) {
         const unsigned char* base = static_cast<const unsigned char*>(sys->dev_program);
         a.rec_desc = reinterpret_cast<const uint2*>(base + sys->rec_desc_off);
@@ -538,9 +443,7 @@ int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch,
         a.rec_jstride = (sys->counts.zj + 2) & ~1u;  // (the values, the zero of padding pairs)
     }
     fill_cfg(a, cfg);
-    const int rc = launch(*sys, a, static_cast<hipStream_t>(stream));
-    if (resident) *resident = rc == EZPZ_OK && a.done.request != nullptr;
-    return rc;
+    return a;
 }
 
 // The systems of one topology inside a heterogeneous batch, solved IN PLACE by the lane-per-system kernel (mixed.hip): lane i

@@ -102,7 +102,14 @@ struct SolveArgs {
     const uint4* rec_asm_slots;
     uint32_t rec_asm_kc, rec_asm_ks;
     DoneWord done;  // one-call launches: the completion word (dev_types.hpp), else null
+    // driven parameters (PAR builds of lm_solve_kernel: ezpz_system_solve_batch_params): params[sys * n_param + slot] replaces the
+    // parameter of every constraint ci of the table with par_slot[ci] == slot; par_lds_off: where a team keeps its system's values
+    // in LDS (doubles from the start; 0: they are read from `params`)
+    const double* params;
+    const uint32_t* par_slot;
+    uint32_t n_param, par_lds_off;
 };
+constexpr uint32_t kNoParamSlot = 0xFFFFFFFFu;
 
 // a round's descriptor (per wavefront): chunks to load (0 = the wavefront has no item), log2 of the lanes per list, ...
 constexpr uint32_t REC_NCH_MASK = 7u, REC_LG_SHIFT = 3u, REC_BARRIER = 1u << 7, REC_BWD = 1u << 8;

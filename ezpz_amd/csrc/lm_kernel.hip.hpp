@@ -426,6 +426,7 @@ struct ConRef<1, PROG> {
     DevCon c;
     __device__ __forceinline__ ConRef(const PROG& P, uint32_t ci, bool) : c(load_con(P.cons + ci)) {}
     __device__ __forceinline__ const DevCon& get() const { return c; }
+    __device__ __forceinline__ void set_param(double v) { c.param = v; }  // (a driven parameter, PAR builds)
     __device__ __forceinline__ uint32_t pos(const PROG&, uint32_t) const { return c.pos; }
     __device__ __forceinline__ uint4 jloc(const PROG&) const { return *reinterpret_cast<const uint4*>(c.jloc); }
 };
@@ -435,6 +436,7 @@ struct ConRef<2, PROG> {
     __device__ __forceinline__ ConRef(const PROG& P, uint32_t ci, bool unit_weights)
         : c(load_packed(P.pcons, P.con_weight, ci, unit_weights)) {}
     __device__ __forceinline__ const DevCon& get() const { return c; }
+    __device__ __forceinline__ void set_param(double v) { c.param = v; }
     __device__ __forceinline__ uint32_t pos(const PROG& P, uint32_t ci) const { return P.con_pos[ci]; }
     __device__ __forceinline__ uint4 jloc(const PROG& P) const { return P.patterns[c.nslots]; }
 };
@@ -446,7 +448,14 @@ struct ConRef<2, PROG> {
 // Cholesky and the substitutions are plain loops over rows and columns instead of level-by-level list walks.
 // Occupancy hints: sub-wavefront teams are compiled for 4 workgroups per CU (128 VGPRs; measured against 3 and 2:
 // +8 % on some topologies, -7 % on others), the register-resident dense solve for 2 (184 VGPRs, no spills: +12 %).
-template <int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool GRID = false, bool DENSE = false, int RECF = 0>
+// PAR: the build of ezpz_system_solve_batch_params -- every system of the batch brings its own values for the constraint
+// parameters the call drives (SolveArgs::params, n_param doubles per system; SolveArgs::par_slot: per constraint of the
+// table, its place among them or kNoParamSlot).  A team copies its system's values once, beside the load of x -- into LDS
+// where the launch found room for them (SolveArgs::par_lds_off; coalesced, one copy per team, two per wavefront-partitioned
+// workgroup, whose wavefronts may be a system apart), else they are read where the caller left them -- and every sweep that
+// builds a constraint's DevCon puts the driven value into it.  A template flag, not a run-time branch: the other builds
+// stay instruction for instruction what they were, and the PAR builds compile in a translation unit of their own.
+template <int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool GRID = false, bool DENSE = false, int RECF = 0, bool PAR = false>
 __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1024 : 512), MODE == MODE_SUB ? (DENSE ? 2 : 4) : 1)
     lm_solve_kernel(const SolveArgs a) {
     // RECF: the record walk's form -- 0 none, 1 state in LDS (16-bit addresses), 2 state in global memory (32-bit addresses)
@@ -455,6 +464,7 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
     static_assert(!DENSE || (MODE == MODE_SUB && TEAM == 4), "the register-resident dense solve is for teams of four");
     static_assert(!REC || (MODE == MODE_WGB && !GRID && !DENSE && (RECF == 1) == LDSWS), "the record walk is for one barrier workgroup");
     static_assert(!GRID || (MODE == MODE_PART && LDSWS && PLDS), "grid teams are partitioned teams with staged lists");
+    static_assert(!PAR || !GRID, "driven parameters are served by one-workgroup teams");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using namespace dev;
     Team<TEAM, MODE, GRID> tm;
@@ -501,9 +511,16 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
     // constraint records: in place from LDS (sub-wavefront teams with a staged program), 32-byte packed records from
     // L2 (workgroup teams with staged lists; the host packs the table exactly when PLDS holds), else the wide record
     constexpr int LIST_CHUNK = (MODE == MODE_SUB) ? 4 : 2;
-    constexpr int CON_FORM = PLDS ? (MODE == MODE_SUB ? 0 : 2) : 1;
+    // (PAR: never in place -- the record is copied, from LDS or L2, and the copy takes the driven value)
+    constexpr int CON_FORM = PLDS ? (MODE == MODE_SUB ? (PAR ? 1 : 0) : 2) : 1;
     using CRef = ConRef<CON_FORM, Prog<idx_t>>;
     const bool unit_w = a.unit_weights != 0;
+    // driven parameters: this team's copy in LDS (null: read from the caller's rows), and the current system's values
+    double* par_lds = nullptr;
+    const double* par_vals = nullptr;
+    if constexpr (PAR) {
+        if (a.par_lds_off) par_lds = smem + a.par_lds_off + (MODE == MODE_SUB ? (size_t)team_in_block * a.n_param : 0);
+    }
 
     // ---- grid team geometry (one system on several workgroups, each keeping its share of the state in LDS) ----------
     const uint32_t grid_wgs = GRID_OK ? a.grid_wgs : 1u;
@@ -658,6 +675,17 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
             }
         } else {
             for (uint32_t i = tlane; i < n; i += tsize) ws[o_x + i] = x0[P.var_of[i]];
+        }
+        if constexpr (PAR) {
+            const double* src = a.params + sys * a.n_param;
+            par_vals = src;
+            if (par_lds) {  // (uniform per launch: a scalar branch)
+                // (a partitioned workgroup's wavefronts may be one system apart -- never two: the rendezvous below -- so its
+                // systems alternate between two copies)
+                double* dst = par_lds + (MODE == MODE_PART ? (size_t)sys_parity * a.n_param : 0);
+                for (uint32_t i = tlane; i < a.n_param; i += tsize) dst[i] = src[i];
+                par_vals = dst;
+            }
         }
         const bool grid_team = GRID_OK && grid_wgs > 1;
         if (grid_team) {
@@ -1587,7 +1615,11 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
             // 300 variables -16 %: the copies cost issue slots where four workgroups share a CU.  Not kept.)
             auto sweep = [&](auto&& f) __attribute__((always_inline)) {
                 for (uint32_t ci = con0 + tm.lane; ci < con1; ci += tm.stride) {
-                    const CRef cref(P, ci, unit_w);
+                    CRef cref(P, ci, unit_w);
+                    if constexpr (PAR) {
+                        const uint32_t slot = a.par_slot[ci];
+                        if (slot != kNoParamSlot) cref.set_param(par_vals[slot]);
+                    }
                     f(cref, ci);
                 }
             };

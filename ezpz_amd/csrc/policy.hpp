@@ -18,7 +18,7 @@ namespace ezpz {
 // Diagnostics on stderr, one switch for all of them: EZPZ_DEBUG=<topic>[,<topic>...] or EZPZ_DEBUG=all -- topics: hip (failing
 // runtime calls), comp (why a system got no component plan), jit (compilation logs, the wavefront kernel's elimination), lanes
 // (the lanes-across-the-batch operation stream), front (the frontal plan), dense (dense phases), rec (the record walk), h2h (the
-// host-to-host pipeline).  (Round 5 had eight environment switches for this.)
+// host-to-host pipeline), params (whether a driven-parameter launch staged its values in LDS).  (Round 5 had eight environment switches for this.)
 inline bool debug_topic(const char* topic) {
     const char* e = std::getenv("EZPZ_DEBUG");
     if (!e || !*e) return false;

@@ -408,6 +408,8 @@ int analyze_into(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, uint32_t 
         if (!kind_is_linear(d.kind)) s.linear_only = false;
     }
     s.host_var_of = P.var_of;
+    s.host_con_pos.resize(P.cons.size());
+    for (size_t ci = 0; ci < P.cons.size(); ++ci) s.host_con_pos[ci] = P.cons[ci].pos;
     s.host_row_of = P.row_of;
     s.host_slot_row = P.slot_row;
     s.host_slot_col = P.slot_col;

@@ -272,6 +272,7 @@ struct EzpzSystem {
     DevBuf<uint8_t> mask_dev;
     DevBuf<uint64_t> log_dev;
     DevBuf<double> gws_dev;
+    DevBuf<double> par_dev;  // ezpz_system_solve_batch_params: the call's parameters
     // residual fields (residual_field.hip): the first launch's list and sums; the host entry's base values and images
     DevBuf<unsigned char> field_scratch;
     DevBuf<double> field_x, field_mag;
@@ -292,6 +293,21 @@ struct EzpzSystem {
         }
     } pipe;
     std::vector<uint32_t> host_var_of, host_row_of, host_slot_row, host_slot_col;  // internal -> caller numbering
+    // ezpz_system_solve_batch_params (params.hip): whether the constraint at each caller position reads its parameter, the caller
+    // position of every constraint of the program's table, and what the last call's `positions` list was turned into (kept for a
+    // caller that repeats its list; touched under launch_mu): the list, the table-order side array of the list-walk teams, the
+    // interpreter's overlay (comp_program.cpp: comp_param_overlay)
+    std::vector<uint8_t> host_has_param;
+    std::vector<uint32_t> host_con_pos;
+    struct DrivenParams {
+        std::vector<uint32_t> positions;
+        bool valid = false, for_comp = false;
+        DevBuf<uint32_t> slots;
+        hipEvent_t uploaded = nullptr;  // the last launch that read `slots`: a new list overwrites them behind it
+        ~DrivenParams() {
+            if (uploaded) (void)hipEventDestroy(uploaded);
+        }
+    } driven;
     // FreedomAnalysis program (built on first use) and its scratch
     struct Freedom {
         bool built = false;
@@ -410,6 +426,11 @@ extern unsigned long long* g_stamps;  // diagnostic builds only (tools/stamps.py
 int solve_batch_device_impl(EzpzSystem* sys, const double* x0_dev, size_t batch, const EzpzConfig* cfg, double* x_out_dev,
                             EzpzStatus* status_dev, uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, void* stream,
                             const DoneWord& done, bool* resident = nullptr);
+
+// (the list-walk kernels' argument block for a call on `sys`, without a completion word; the same call as the other kernels take it)
+SolveArgs solve_args_for(EzpzSystem* sys, const double* x0_dev, size_t batch, const EzpzConfig* cfg, double* x_out_dev,
+                         EzpzStatus* status_dev, uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap);
+CompLaunch comp_launch_args(const SolveArgs& args);
 
 // The whole call's systems while a host entry of this thread feeds them to launch() in pieces (pipeline.cpp): the launch shape is
 // chosen once per call, not per piece -- a short last piece does not change shape (0: the piece is the call).

@@ -301,6 +301,34 @@ int ezpz_system_solve_batch_device(EzpzSystem* sys, const double* x0_dev, size_t
 int ezpz_system_solve_batch(EzpzSystem* sys, const double* x0, size_t batch, const EzpzConfig* cfg, double* x_out,
                             EzpzStatus* status, uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
 
+/* ---- batches with per-system constraint parameters (new: driven dimensions -- one sketch, many dimension sets) ------------
+ * ezpz_system_solve_batch[_device] with the parameters of some constraints taken per system instead of from the `cs` the
+ * system was created with: `positions` (host memory, n_param of them, distinct, any order) are positions in that `cs`, and
+ * params[b][j] (AoS [batch][n_param]) replaces cs[positions[j]].param for system b -- in the units of that field: degrees for
+ * an angle tagged EZPZ_ANGLE_OTHER_DEG.  A constraint that is not listed keeps its value.  System b gets exactly what
+ * ezpz_system_solve_batch[_device] gives on a system created from `cs` with those parameters substituted: values, EzpzStatus,
+ * unsatisfied mask, warning log (block systems bit for bit; other systems bit for bit what that system's list-walk teams of
+ * the same team_size give).  n_param == 0 is the plain entry.  Only finite parameters are supported.
+ * ezpz_constraint_has_param (host only, no device): 1 where the residual of the constraint's kind and tag reads `param` -- the
+ * ten kinds documented with "param" above, and the three angle kinds unless tagged parallel or perpendicular -- else 0.
+ * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: a position >= n_cs, a position listed twice, a
+ * position whose constraint has no parameter, n_param > 0 with positions or params NULL -- and a system that one solve spreads
+ * over several workgroups (EzpzSystemInfo.grid_workgroups > 1 of its list-walk shape), which this entry declines.
+ * The entry has its own route: the component interpreter for block systems, else the list-walk teams; never the run-time
+ * compiled kernels (a specialised system is served all the same), the lanes across the batch or the fronts.
+ * Thread safety and the aliasing of x0 / x_out: as for ezpz_system_solve_batch_device; launches of this entry on one
+ * EzpzSystem run one behind the other whatever streams they were enqueued on.  The _device form only enqueues on
+ * `stream`, except that a `positions` list other than the system's last one is turned into its device table first: the call then
+ * waits for the system's earlier launches of this entry and copies synchronously (repeat the list, and calls only enqueue). */
+int ezpz_constraint_has_param(const EzpzConstraint* c);
+int ezpz_system_solve_batch_params_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                          const double* params_dev, size_t batch, const EzpzConfig* cfg, double* x_out_dev,
+                                          EzpzStatus* status_dev, uint8_t* unsat_mask_dev, uint64_t* warn_log_dev,
+                                          uint32_t warn_cap, void* stream);
+int ezpz_system_solve_batch_params(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
+                                   const double* params, size_t batch, const EzpzConfig* cfg, double* x_out, EzpzStatus* status,
+                                   uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
+
 /* ---- solve_inner, ezpz/src/lib.rs:265-356: one tier, one system -----------------------------------
  * lint (warnings.rs:34-60) + Model::new + LM + unsatisfied list.  orig_ids (may be NULL) are the
  * ConstraintEntry.id values reported in `unsat_ids` and lint warnings. */
