@@ -58,6 +58,12 @@ class CLaunchPolicy(C.Structure):
                 ("front_small_call_wgs_per_round", C.c_uint32)]
 
 
+class CSensitivityPlan(C.Structure):
+    _fields_ = [("n_components", C.c_uint32), ("n_active", C.c_uint32), ("n_small", C.c_uint32), ("n_lds", C.c_uint32),
+                ("n_workspace", C.c_uint32), ("max_component_vars", C.c_uint32), ("max_envelope", C.c_uint32),
+                ("lds_bytes", C.c_uint32), ("workspace_bytes", C.c_uint64)]
+
+
 class CViewport(C.Structure):
     _fields_ = [("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double),
                 ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -87,6 +93,8 @@ EXPORTS = [
     "ezpz_mixed_solve", "ezpz_system_solve_batch_mixed", "ezpz_multi_solve_batch_mixed",
     "ezpz_system_residual_field", "ezpz_system_residual_field_device", "ezpz_residual_colormap", "ezpz_residual_overlay",
     "ezpz_constraint_has_param", "ezpz_system_solve_batch_params_device", "ezpz_system_solve_batch_params",
+    "ezpz_constraint_param_derivative", "ezpz_system_param_sensitivity_plan", "ezpz_system_param_sensitivity_device",
+    "ezpz_system_param_sensitivity",
 ]
 
 _lib = None
@@ -205,6 +213,14 @@ def lib():
     L.ezpz_system_solve_batch_params_device.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32, vp]
     L.ezpz_system_solve_batch_params.restype = C.c_int
     L.ezpz_system_solve_batch_params.argtypes = [vp, vp, vp, sz, vp, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32]
+    L.ezpz_constraint_param_derivative.restype = C.c_int
+    L.ezpz_constraint_param_derivative.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
+    L.ezpz_system_param_sensitivity_plan.restype = C.c_int
+    L.ezpz_system_param_sensitivity_plan.argtypes = [vp, vp, sz, C.POINTER(CSensitivityPlan)]
+    L.ezpz_system_param_sensitivity_device.restype = C.c_int
+    L.ezpz_system_param_sensitivity_device.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp, vp]
+    L.ezpz_system_param_sensitivity.restype = C.c_int
+    L.ezpz_system_param_sensitivity.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp]
     L.ezpz_solve_inner.restype = C.c_int
     L.ezpz_solve_inner.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(CConfig), vp, vp, vp, sz, C.POINTER(COutcome)]
     L.ezpz_solve.restype = C.c_int

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSystemInfo, CWarning, lib
+from ._lib import CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -812,6 +812,63 @@ class System:
                                                          mask_ptr or None, None, 0, stream or None)
         if rc != 0:
             raise NonLinearSystemError(rc)
+
+
+    def param_sensitivity(self, x: np.ndarray, positions, params: Optional[np.ndarray] = None, lam: Optional[float] = None,
+                          want_degenerate: bool = False):
+        """`ezpz_system_param_sensitivity`: S[b, j, :] = -(JtJ + lam I)^-1 Jt dr/dp_j at the values x [batch, n_vars] (normally a
+        solve's answer) with params [batch, len(positions)] overlaid as solve_batch_params overlays them (None: the system's own
+        values); per unit of the `param` field.  lam defaults to Config().initial_lambda.  Returns (S [batch, k, n_vars], status
+        [batch] uint32: 1 where the factorisation failed and S[b] is NaN) -- and the degenerate counts with want_degenerate."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, max(self.n_vars, 1))
+        batch = x.shape[0]
+        pos = self._positions(positions)
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float64)
+            if params.size != batch * len(pos) or (params.ndim == 2 and params.shape != (batch, len(pos))) or params.ndim > 2:
+                raise ValueError(f"params: expected shape ({batch}, {len(pos)}), got {params.shape}")
+        lam = Config().initial_lambda if lam is None else float(lam)
+        S = np.zeros((batch, len(pos), self.n_vars))
+        st = np.zeros(batch, dtype=np.uint32)
+        deg = np.zeros(batch, dtype=np.uint32) if want_degenerate else None
+        rc = lib().ezpz_system_param_sensitivity(self._h, x.ctypes.data, pos.ctypes.data if len(pos) else None, len(pos),
+                                                 params.ctypes.data if params is not None and len(pos) else None, batch, lam,
+                                                 S.ctypes.data if S.size else None, st.ctypes.data,
+                                                 deg.ctypes.data if want_degenerate else None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return (S, st, deg) if want_degenerate else (S, st)
+
+    def param_sensitivity_device(self, x_ptr: int, positions, params_ptr: int, batch: int, S_ptr: int, status_ptr: int,
+                                 lam: Optional[float] = None, degenerate_ptr: int = 0, stream: int = 0) -> None:
+        """Device pointers and a hipStream_t handle; enqueue only (a `positions` list other than the last one is planned and
+        uploaded first).  params_ptr 0: the system's own values."""
+        pos = self._positions(positions)
+        lam = Config().initial_lambda if lam is None else float(lam)
+        rc = lib().ezpz_system_param_sensitivity_device(self._h, x_ptr or None, pos.ctypes.data if len(pos) else None, len(pos),
+                                                        params_ptr or None, batch, lam, S_ptr or None, status_ptr or None,
+                                                        degenerate_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+    def param_sensitivity_plan(self, positions) -> dict:
+        """`ezpz_system_param_sensitivity_plan`: which launch shape the components of this list take (host only)."""
+        pos = self._positions(positions)
+        p = CSensitivityPlan()
+        rc = lib().ezpz_system_param_sensitivity_plan(self._h, pos.ctypes.data if len(pos) else None, len(pos), C.byref(p))
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return {f: getattr(p, f) for f, _ in CSensitivityPlan._fields_}
+
+
+def constraint_param_derivative(record, x):
+    """`ezpz_constraint_param_derivative`: (g [rows] = weight * d residual / d param at the values x indexed by the record's
+    ids, degenerate flag); an empty g for a constraint without a parameter.  Host only."""
+    rec = stack_records([record])
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    g, deg = np.zeros(2), C.c_int(0)
+    rows = lib().ezpz_constraint_param_derivative(rec.ctypes.data, x.ctypes.data, g.ctypes.data, C.byref(deg))
+    return g[:rows], bool(deg.value)
 
 
 def constraint_has_param(record) -> bool:

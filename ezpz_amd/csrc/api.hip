@@ -88,6 +88,7 @@ int ezpz_system_create(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, int
     if (!have_device) return EZPZ_ERR_NO_DEVICE;
     s->host_has_param.resize(n_cs);
     for (size_t i = 0; i < n_cs; ++i) s->host_has_param[i] = kind_has_param(cs[i].kind, cs[i].tag) ? 1 : 0;
+    s->host_cs.assign(cs, cs + n_cs);
     EZPZ_ON_DEVICE(device);
     if (!s->program_deferred.load()) {
         HIP_TRY(hipMalloc(&s->dev_program, blob.size()));

@@ -299,6 +299,10 @@ struct EzpzSystem {
     // interpreter's overlay (comp_program.cpp: comp_param_overlay)
     std::vector<uint8_t> host_has_param;
     std::vector<uint32_t> host_con_pos;
+    // ezpz_system_param_sensitivity (sensitivity.hip): the constraints as the caller gave them, and the plan of the last call's
+    // `positions` list with its device tables and workspace (built on first use; touched under launch_mu)
+    std::vector<EzpzConstraint> host_cs;
+    std::shared_ptr<void> sens;
     struct DrivenParams {
         std::vector<uint32_t> positions;
         bool valid = false, for_comp = false;

@@ -329,6 +329,57 @@ int ezpz_system_solve_batch_params(EzpzSystem* sys, const double* x0, const uint
                                    const double* params, size_t batch, const EzpzConfig* cfg, double* x_out, EzpzStatus* status,
                                    uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
 
+/* ---- dimension sensitivities: dx/d(param) of a batch, on the device ------------------------------------------
+ * For system b the caller passes values x_b (normally a solve's answer) and a parameter row p_b.  r(x, p) is the weighted
+ * residual vector in the reference's row order with p overlaid exactly as ezpz_system_solve_batch_params overlays it,
+ * J = dr/dx, g_j = dr/dp_j (non-zero only on the rows of constraint positions[j]; in the units of the `param` field -- per
+ * degree where the tag says degrees; it carries the row's weight).  Then
+ *     S_b[j, :] = -(JtJ + lambda I)^-1 Jt g_j            S: AoS [batch][n_param][n_vars], the caller's variable order
+ * the linearisation of the first step the reference's loop (solver/newton.rs) takes from x_b after p_j moves: d(solution)/dp_j on a
+ * well-determined system, the damped minimum-norm response on an under-determined one.  A constraint that is degenerate at x_b
+ * contributes zero rows to J (the Jacobian's guards) and to g (the residual's guards), as the evaluators do; the constraints
+ * of the evaluated components whose guard fired are counted in degenerate_count_out[b] (optional).  JtJ + lambda I is block
+ * diagonal over the connected components of the variable-constraint graph: only the components that hold a listed constraint
+ * are evaluated, and every other entry of S is +0.0.  A factorisation that meets a pivot that is not positive and finite sets
+ * status_out[b] = 1 (else 0) and fills the whole S_b with NaN; other systems are unaffected.
+ * S is bit-identical from run to run, whatever the batch size and the system's place in the batch.
+ * ezpz_constraint_param_derivative (host only, no device): g of one constraint, g_out[row] = weight * d residual_row / d param
+ * at the values x (indexed by c->ids); *degenerate (optional) = 1 where the residual's guard fired (g_out is 0 then).  Returns
+ * the number of rows (1 or 2), 0 for a constraint without a parameter (ezpz_constraint_has_param) or NULL arguments.
+ * params == NULL: the system's own values.  n_param == 0: status (and the host form's degenerate counts) are zeroed, nothing
+ * else is written.
+ * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: the argument errors of the params entries (a position
+ * >= n_cs, listed twice, or whose constraint has no parameter; positions NULL with n_param > 0; x, S_out or status_out NULL with
+ * batch > 0) -- and a listed constraint in a component of more than EZPZ_SENSITIVITY_MAX_COMPONENT_VARS variables, or in a
+ * component of the workspace shape with so many listed constraints that x, two doubles per listed constraint and 12 bytes per
+ * variable exceed 64 KB of LDS (some 2800 listed constraints in a component of 1024 variables).
+ * The _device form takes device pointers and only enqueues on `stream`: no host synchronisation and no allocation, except
+ * that a `positions` list other than the system's last one is planned and uploaded first (repeat the list, and calls only
+ * enqueue).  Launches of this entry on one EzpzSystem run one behind the other whatever their streams (they share the plan's
+ * workspace).  ezpz_system_param_sensitivity_plan: which launch shape each component of that list takes (host only).  It is
+ * DIAGNOSTIC: the tests use it to prove which shape ran; EzpzSensitivityPlan follows the kernels and may change or grow with
+ * them -- it is not part of the stable surface. */
+#define EZPZ_SENSITIVITY_MAX_COMPONENT_VARS 1024u
+typedef struct EzpzSensitivityPlan {
+    uint32_t n_components;       /* connected components of the system */
+    uint32_t n_active;           /* ... that hold a listed constraint */
+    uint32_t n_small;            /* active components on one lane per (system, component) */
+    uint32_t n_lds;              /* ... on one workgroup with the factor in LDS */
+    uint32_t n_workspace;        /* ... on one workgroup with the factor in a global-memory workspace */
+    uint32_t max_component_vars; /* over the active components */
+    uint32_t max_envelope;       /* entries of the largest factor (row envelope, diagonal included) */
+    uint32_t lds_bytes;          /* per workgroup of the LDS shape */
+    uint64_t workspace_bytes;    /* per resident workgroup of the workspace shape */
+} EzpzSensitivityPlan;
+int ezpz_constraint_param_derivative(const EzpzConstraint* c, const double* x, double g_out[2], int* degenerate);
+int ezpz_system_param_sensitivity_plan(EzpzSystem* sys, const uint32_t* positions, size_t n_param, EzpzSensitivityPlan* out);
+int ezpz_system_param_sensitivity_device(EzpzSystem* sys, const double* x_dev, const uint32_t* positions, size_t n_param,
+                                         const double* params_dev, size_t batch, double lambda, double* S_out_dev,
+                                         uint32_t* status_dev, uint32_t* degenerate_count_dev, void* stream);
+int ezpz_system_param_sensitivity(EzpzSystem* sys, const double* x, const uint32_t* positions, size_t n_param,
+                                  const double* params, size_t batch, double lambda, double* S_out, uint32_t* status_out,
+                                  uint32_t* degenerate_count_out);
+
 /* ---- solve_inner, ezpz/src/lib.rs:265-356: one tier, one system -----------------------------------
  * lint (warnings.rs:34-60) + Model::new + LM + unsatisfied list.  orig_ids (may be NULL) are the
  * ConstraintEntry.id values reported in `unsat_ids` and lint warnings. */
