@@ -1093,11 +1093,23 @@ typedef int bufword2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_at(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)0xFFFFFFFFu, 0x00020000);  // raw, no swizzle, 4 GB
 }
+// POLICY: the cache policy of the access (the buffer instructions' aux operand).  kCached, the default, allocates the line in L2 and
+// the Infinity Cache; kStreamOnce (`nt`) is for bytes that a launch touches exactly once -- a row of x0 or x_out when the batch is far
+// larger than the caches, so that a line kept would only push out one that is used again.  What it buys and where it loses is
+// measured, not assumed (tools/row_copy_bench.hip, profiles/row_stream_roof.txt): +2.5 ... 5 % on full 16-byte lines with BOTH the
+// loads and the stores non-temporal (+2.7 ... 8.7 % with the rows drawn as solve_kernel_fast draws them; the headline +6 ... 7 %,
+// profiles/fast_stream_ab.txt), -3 % with the loads alone, and -28 % on the 8-byte strided pattern -- which is why only the
+// full-line stream of solve_kernel_fast asks for it, and everything small and reused (the tables in JitArgs::blob, status, redo list,
+// masks, tickets) stays cached.  The price: a batch small enough to stay in the Infinity Cache from one launch to the next (8192 rows
+// of 16 KB, the same buffers every launch) is no longer served from it -- the copy kernel loses 20 % there.
+constexpr int kCached = 0, kStreamOnce = 2;
+template <int POLICY = kCached>
 __device__ __forceinline__ double load_at(__amdgpu_buffer_rsrc_t row, uint32_t byte_offset) {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(row, (int)byte_offset, 0, 0));
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(row, (int)byte_offset, 0, POLICY));
 }
+template <int POLICY = kCached>
 __device__ __forceinline__ void store_at(__amdgpu_buffer_rsrc_t row, uint32_t byte_offset, double v) {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(bufword2_t, v), row, (int)byte_offset, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(bufword2_t, v), row, (int)byte_offset, 0, POLICY);
 }
 
 // ---- what the kernels that do not wait for the LM control's verdicts share (solve_kernel_fast, solve_kernel_grid_fast) -----------
@@ -1149,16 +1161,16 @@ __device__ __forceinline__ void fast_fetch(SEQ& seq, const JitArgs& a, const uin
 typedef int bufword4_t __attribute__((ext_vector_type(4)));
 typedef bufword4_t __attribute__((may_alias)) lds_b128_t;  // (the piece is written as 16-byte words and read as doubles, and the other way round)
 typedef double __attribute__((may_alias)) lds_f64_t;
-template <int PIECES>
+template <int PIECES, int POLICY = kCached>
 __device__ __forceinline__ void piece_load(bufword4_t (&q)[PIECES], const __amdgpu_buffer_rsrc_t row, const uint32_t first_byte, const uint32_t bytes, const int lane) {
 #pragma unroll
     for (int p = 0; p < PIECES; ++p) {
         const uint32_t at = 1024u * p + 16u * lane;
         q[p] = bufword4_t{0, 0, 0, 0};
         if (at + 16u <= bytes) {
-            q[p] = __builtin_amdgcn_raw_buffer_load_b128(row, (int)(first_byte + at), 0, 0);
+            q[p] = __builtin_amdgcn_raw_buffer_load_b128(row, (int)(first_byte + at), 0, POLICY);
         } else if (at + 8u <= bytes) {
-            const bufword2_t h = __builtin_amdgcn_raw_buffer_load_b64(row, (int)(first_byte + at), 0, 0);
+            const bufword2_t h = __builtin_amdgcn_raw_buffer_load_b64(row, (int)(first_byte + at), 0, POLICY);
             q[p].x = h.x, q[p].y = h.y;
         }
     }
@@ -1168,16 +1180,16 @@ __device__ __forceinline__ void piece_to_lds(const bufword4_t (&q)[PIECES], doub
 #pragma unroll
     for (int p = 0; p < PIECES; ++p) *reinterpret_cast<lds_b128_t*>(reinterpret_cast<char*>(buf) + 1024 * p + 16 * lane) = q[p];
 }
-template <int PIECES>
+template <int PIECES, int POLICY = kCached>
 __device__ __forceinline__ void piece_store(const double* buf, const __amdgpu_buffer_rsrc_t row, const uint32_t first_byte, const uint32_t bytes, const int lane) {
 #pragma unroll
     for (int p = 0; p < PIECES; ++p) {
         const uint32_t at = 1024u * p + 16u * lane;
         const bufword4_t q = *reinterpret_cast<const lds_b128_t*>(reinterpret_cast<const char*>(buf) + at);
         if (at + 16u <= bytes)
-            __builtin_amdgcn_raw_buffer_store_b128(q, row, (int)(first_byte + at), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(q, row, (int)(first_byte + at), 0, POLICY);
         else if (at + 8u <= bytes)
-            __builtin_amdgcn_raw_buffer_store_b64(bufword2_t{q.x, q.y}, row, (int)(first_byte + at), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(bufword2_t{q.x, q.y}, row, (int)(first_byte + at), 0, POLICY);
     }
 }
 // Returns what the factorisations alone say about every system of the launch, as fast_wave's flag bits -- bit 0 / 1: a pivot of the
@@ -1226,8 +1238,8 @@ __device__ __forceinline__ bool fast_exceeds(unsigned int flags, int k) {  // !(
 // IO: how the values travel -- 0: every slot loads the next system's guesses and stores its values itself; 1: the values wait in LDS
 // (`out_lds`) and are stored back to back; 2: the wavefront owns a contiguous piece of the row (`first_byte`, `bytes`): this
 // system's values are in `out_lds`, the slots read and write them there, the next system's piece is loaded as full lines at the top
-// and put into `next_lds` at the end, this one's is stored as full lines.
-template <int IO, class SEQ>
+// and put into `next_lds` at the end, this one's is stored as full lines.  POLICY: of the row's loads and stores (load_at's note).
+template <int IO, int POLICY = kCached, class SEQ>
 __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, const unsigned int slot_flags, const uint64_t sys, const uint64_t sys_n, const bool next,
                                                   const uint32_t wave_global, const int lane, double (&v)[4], double* const out_lds,
                                                   double* const next_lds = nullptr, const uint32_t first_byte = 0, const uint32_t bytes = 0) {
@@ -1238,7 +1250,7 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
     const __amdgpu_buffer_rsrc_t x0n = row_at(a.x0 + (next ? sys_n : sys) * a.n_row);
     bufword4_t ahead[IO == 2 ? PIECES : 1];
     if constexpr (IO == 2) {
-        if (next) piece_load<PIECES>(ahead, x0n, first_byte, bytes, lane);
+        if (next) piece_load<PIECES, POLICY>(ahead, x0n, first_byte, bytes, lane);
     }
     uint8_t* mask = a.unsat_mask ? a.unsat_mask + sys * a.n_cons : nullptr;
     const __amdgpu_buffer_rsrc_t table = row_at(a.blob);
@@ -1260,7 +1272,7 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
             for (int i = 0; i < C::NV; ++i) s.x[i] = s.xn[i];
             if (next) {
 #pragma unroll
-                for (int i = 0; i < C::NV; ++i) s.xn[i] = load_at(x0n, s.ids[0] != kNoInstance ? s.ids[i] : 0u);
+                for (int i = 0; i < C::NV; ++i) s.xn[i] = load_at<POLICY>(x0n, s.ids[0] != kNoInstance ? s.ids[i] : 0u);
             }
         }
         if (fast_has_instance(s)) {
@@ -1293,7 +1305,7 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
                 for (int i = 0; i < C::NV; ++i) out_lds[(var0 + i) * 64 + lane] = s.x[i];
             } else {
 #pragma unroll
-                for (int i = 0; i < C::NV; ++i) store_at(xo, s.ids[i], s.x[i]);
+                for (int i = 0; i < C::NV; ++i) store_at<POLICY>(xo, s.ids[i], s.x[i]);
             }
         }
         var0 += C::NV;
@@ -1310,12 +1322,12 @@ __device__ __forceinline__ unsigned int fast_wave(SEQ& seq, const JitArgs& a, co
         using C = typename class_of<decltype(cls)>::type;
 #pragma unroll
         for (int i = 0; i < C::NV; ++i) {
-            if (s.ids[0] != kNoInstance) store_at(xo, s.ids[i], out_lds[(var0 + i) * 64 + lane]);
+            if (s.ids[0] != kNoInstance) store_at<POLICY>(xo, s.ids[i], out_lds[(var0 + i) * 64 + lane]);
         }
         var0 += C::NV;
     });
     if constexpr (IO == 2) {
-        piece_store<PIECES>(out_lds, xo, first_byte, bytes, lane);
+        piece_store<PIECES, POLICY>(out_lds, xo, first_byte, bytes, lane);
         if (next) piece_to_lds<PIECES>(ahead, next_lds, lane);
     }
 #pragma unroll
@@ -1405,7 +1417,7 @@ __device__ __forceinline__ void solve_kernel_fast(const JitArgs& a) {
     if constexpr (CONTIG) {
         if (blockIdx.x < a.batch) {
             bufword4_t q[(SEQ::NVS + 1) / 2];
-            piece_load<(SEQ::NVS + 1) / 2>(q, row_at(a.x0 + (uint64_t)blockIdx.x * a.n_row), first_byte, piece_bytes, lane);
+            piece_load<(SEQ::NVS + 1) / 2, kStreamOnce>(q, row_at(a.x0 + (uint64_t)blockIdx.x * a.n_row), first_byte, piece_bytes, lane);
             piece_to_lds<(SEQ::NVS + 1) / 2>(q, row_lds, lane);
         }
     } else {
@@ -1428,8 +1440,8 @@ __device__ __forceinline__ void solve_kernel_fast(const JitArgs& a) {
         double v[4];
         unsigned int wave_flags;
         if constexpr (CONTIG)
-            wave_flags = fast_wave<2>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds + kp * PIECE, row_lds + (kp ^ 1u) * PIECE, first_byte, piece_bytes);
-        else
+            wave_flags = fast_wave<2, kStreamOnce>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds + kp * PIECE, row_lds + (kp ^ 1u) * PIECE, first_byte, piece_bytes);
+        else  // (8-byte accesses lose a quarter of their rate under kStreamOnce: load_at's note)
             wave_flags = fast_wave<1>(seq, a, slot_flags, sys, sys_n, sys_n < a.batch, wave, lane, v, row_lds);
         uint64_t sys_nn = sys_n + gridDim.x;
         if (tickets && tid == 0) {
