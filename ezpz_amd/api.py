@@ -504,9 +504,10 @@ def _split_guesses(guesses):
 
 
 def solve_records(records, guesses, config: Optional[Config] = None, warn_cap: int = 4096,
-                  analysis: bool = False) -> RawResult:
+                  analysis: bool = False, inner: bool = False, orig_ids=None) -> RawResult:
     """`ezpz_solve` (or `ezpz_solve_analysis`) on a record array; never raises for solver errors (error code in the
-    result)."""
+    result).  inner=True: `ezpz_solve_inner` (lib.rs:265-356) on the records as they stand -- one tier, no side inferred --
+    with `orig_ids` (optional, one per record) as the ids it reports."""
     a = stack_records(records)
     ids, vals = _split_guesses(guesses)
     n = len(vals)
@@ -520,7 +521,11 @@ def solve_records(records, guesses, config: Optional[Config] = None, warn_cap: i
             C.cast(warns, C.c_void_p), warn_cap, C.byref(out))
     under = np.zeros(max(n, 1), dtype=np.uint32)
     n_under = C.c_uint64(0)
-    if analysis:
+    if inner:
+        assert not analysis, "ezpz_solve_inner has no FreedomAnalysis"
+        oid = None if orig_ids is None else np.ascontiguousarray(orig_ids, dtype=np.uint64)
+        lib().ezpz_solve_inner(args[0], oid.ctypes.data if oid is not None and len(oid) else None, *args[1:])
+    elif analysis:
         lib().ezpz_solve_analysis(*args, under.ctypes.data, C.byref(n_under))
     else:
         lib().ezpz_solve(*args)

@@ -1,10 +1,11 @@
 // Host orchestration the reference keeps above its numeric core, restated on the C ABI (api.hip, launch.hip, pipeline.cpp) (no device code
-// here: everything numeric goes through ezpz_system_solve_batch / ezpz_system_freedom_batch) --
-//   solve_inner                 reference ezpz/src/lib.rs:265-356
-//   solve_with_priority_inner   reference ezpz/src/lib.rs:148-263 (solve, solve_analysis)
+// here: everything numeric goes through system_solve_one / ezpz_system_solve_batch / ezpz_system_freedom_batch) --
+//   solve_inner                 reference ezpz/src/lib.rs:265-356   (solve_tier; ezpz_solve_inner)
+//   solve_with_priority_inner   reference ezpz/src/lib.rs:148-263   (solve_impl; ezpz_solve, ezpz_solve_analysis, ezpz_solve_batch)
 //   lint                        reference ezpz/src/warnings.rs:34-60
 //   set_from_initial_values     reference ezpz/src/constraints.rs:146-193
-// plus the per-process cache of analysed topologies and the batch form of solve().
+// Every entry works from the request plan of its request (tiers, lint, validation, analysed topologies): the plans are the one
+// per-process cache of this file.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -35,59 +36,6 @@ extern "C" size_t ezpz_debug_call_trace(uint64_t* buf, size_t cap) {
 
 // ---- solve_inner / solve: host orchestration ---------------------------------------------------------------------
 namespace {
-
-// Small LRU of analysed topologies keyed by the request bytes, so that repeated solve() calls on one
-// problem (what ezpz-cli's 100-run loop does, main.rs:96-98) skip the symbolic phase.
-struct CacheEntry {
-    uint64_t hash;
-    std::vector<unsigned char> key;
-    size_t n_vars;
-    int device;
-    bool one_solve;  // built for the latency of one solve (solve()) or for batch throughput (solve_batch())
-    std::shared_ptr<EzpzSystem> sys;
-};
-std::mutex g_cache_mu;
-std::list<CacheEntry> g_cache;
-constexpr size_t kCacheMax = 16;
-
-// The system comes back shared: solve() is callable from many threads at once (like the reference's), and an entry
-// another thread evicts must outlive the solves still running on it.  Systems live on the calling thread's current
-// HIP device.
-int cached_system(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, bool one_solve,
-                  std::shared_ptr<EzpzSystem>* out, int32_t* ec, int64_t* ev) {
-    const uint64_t h = topology_hash(cs, n_cs, n_vars);
-    const size_t bytes = n_cs * sizeof(EzpzConstraint);
-    const int device = ezpz_current_device();
-    if (device < 0) return EZPZ_ERR_NO_DEVICE;
-    {
-        std::lock_guard<std::mutex> lock(g_cache_mu);
-        for (auto it = g_cache.begin(); it != g_cache.end(); ++it) {
-            if (it->hash == h && it->n_vars == n_vars && it->device == device && it->one_solve == one_solve &&
-                it->key.size() == bytes &&
-                std::memcmp(it->key.data(), cs, bytes) == 0) {
-                g_cache.splice(g_cache.begin(), g_cache, it);
-                *out = g_cache.front().sys;
-                return EZPZ_OK;
-            }
-        }
-    }
-    // the symbolic phase runs outside the lock; two threads racing on a new topology both build it, one entry wins
-    EzpzSystem* raw = nullptr;
-    int rc = ezpz_system_create(cs, n_cs, n_vars, device, one_solve ? EZPZ_TEAM_AUTO_LATENCY : 0, &raw, ec, ev);
-    if (rc != EZPZ_OK) return rc;
-    CacheEntry e;
-    e.hash = h;
-    e.key.assign(reinterpret_cast<const unsigned char*>(cs), reinterpret_cast<const unsigned char*>(cs) + bytes);
-    e.n_vars = n_vars;
-    e.device = device;
-    e.one_solve = one_solve;
-    e.sys = std::shared_ptr<EzpzSystem>(raw, [](EzpzSystem* p) { ezpz_system_destroy(p); });
-    *out = e.sys;
-    std::lock_guard<std::mutex> lock(g_cache_mu);
-    g_cache.push_front(std::move(e));
-    while (g_cache.size() > kCacheMax) g_cache.pop_back();
-    return EZPZ_OK;
-}
 
 struct WarnSink {
     EzpzWarning* buf;
@@ -121,6 +69,17 @@ void lint(const EzpzConstraint* cs, const uint64_t* orig_ids, size_t n, WarnSink
     }
 }
 
+bool has_undefined_side(const EzpzConstraint& c) {
+    return (c.kind == EZPZ_LINE_TANGENT_TO_CIRCLE || c.kind == EZPZ_CIRCLE_TANGENT_TO_CIRCLE) && c.tag == EZPZ_SIDE_UNDEFINED;
+}
+
+// Whether every id the side test of `c` reads (its datums' ids, constraints.rs:146-193) has a value among `n_values` values by id.
+bool side_ids_below(const EzpzConstraint& c, size_t n_values) {
+    for (int k = 0; k < kind_num_ids(c.kind); ++k)
+        if (c.ids[k] >= n_values) return false;
+    return true;
+}
+
 // constraints.rs:146-193
 void set_from_initial_values(EzpzConstraint& c, const double* iv) {
     auto X = [&](int k) { return iv[c.ids[k]]; };
@@ -143,13 +102,11 @@ extern "C" {
 
 void ezpz_multi_cache_clear(void);  // multi.cpp: the handles behind ezpz_system_solve_batch_multi
 
-void ezpz_request_plans_clear(void);  // (below: the request plans of ezpz_solve)
+void ezpz_request_plans_clear(void);  // (below: the request plans of ezpz_solve*)
 
 void ezpz_cache_clear(void) {
     ezpz_multi_cache_clear();
     ezpz_request_plans_clear();
-    std::lock_guard<std::mutex> lock(g_cache_mu);
-    g_cache.clear();
 }
 
 int ezpz_resolve_sides(EzpzConstraint* cs, size_t n_cs, const double* values, size_t n_vars) {
@@ -157,169 +114,11 @@ int ezpz_resolve_sides(EzpzConstraint* cs, size_t n_cs, const double* values, si
     const std::vector<double> iv(values, values + n_vars);
     for (size_t i = 0; i < n_cs; ++i) {
         EzpzConstraint& c = cs[i];
-        const bool undefined_side = (c.kind == EZPZ_LINE_TANGENT_TO_CIRCLE || c.kind == EZPZ_CIRCLE_TANGENT_TO_CIRCLE) &&
-                                    c.tag == EZPZ_SIDE_UNDEFINED;
-        if (!undefined_side) continue;
-        for (int k = 0; k < kind_num_ids(c.kind); ++k)
-            if (c.ids[k] >= n_vars) return EZPZ_ERR_MISSING_GUESS;
+        if (!has_undefined_side(c)) continue;
+        if (!side_ids_below(c, n_vars)) return EZPZ_ERR_MISSING_GUESS;
         set_from_initial_values(c, iv.data());
     }
     return EZPZ_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-int solve_inner_impl(const EzpzConstraint* cs, const uint64_t* orig_ids, size_t n_cs, const uint32_t* var_ids,
-                     const double* guesses, size_t n_guesses, const EzpzConfig* cfg, double* x_out,
-                     uint64_t* unsat_ids, EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out,
-                     uint32_t* under_out, uint64_t* n_under_out) {
-    if (!out) return EZPZ_ERR_INVALID_ARGUMENT;
-    if (n_under_out) *n_under_out = 0;
-    std::memset(out, 0, sizeof(*out));
-    out->num_vars = n_guesses;
-    uint64_t num_eqs = 0;
-    for (size_t i = 0; i < n_cs; ++i) num_eqs += (uint64_t)residual_dim(cs[i].kind);
-    out->num_eqs = num_eqs;
-    WarnSink sink{warn_buf, warn_cap, 0};
-    lint(cs, orig_ids, n_cs, sink);
-    out->n_warnings = sink.count;
-    EzpzConfig dcfg;
-    if (!cfg) {
-        ezpz_default_config(&dcfg);
-        cfg = &dcfg;
-    }
-    // validate_variables (solver.rs:142-189): every id a constraint's rows mention must appear among the
-    // guess ids.  Values are then addressed by id (Layout::index_of, solver.rs:107-109), so an id that is
-    // present but >= n_guesses cannot be placed in the matrix (faer CreationError in the reference).
-    bool dense = true;
-    for (size_t i = 0; i < n_guesses && var_ids; ++i)
-        if (var_ids[i] != i) dense = false;
-    if (!dense) {
-        uint32_t max_id = 0;
-        for (size_t i = 0; i < n_guesses; ++i) max_id = std::max(max_id, var_ids[i]);
-        std::vector<uint8_t> present((size_t)max_id + 1, 0);
-        for (size_t i = 0; i < n_guesses; ++i) present[var_ids[i]] = 1;
-        for (size_t i = 0; i < n_cs; ++i) {
-            if (cs[i].kind >= EZPZ_NUM_KINDS) continue;
-            const KindInfo& K = kKinds[cs[i].kind];
-            for (int r = 0; r < K.n_rows; ++r)
-                for (int e = 0; e < K.n_nz[r]; ++e) {
-                    uint32_t v = cs[i].ids[K.nz[r][e]];
-                    if (v > max_id || !present[v]) {
-                        out->error = EZPZ_ERR_MISSING_GUESS;
-                        out->err_constraint_id = (int32_t)(orig_ids ? orig_ids[i] : i);
-                        out->err_variable = v;
-                        return out->error;
-                    }
-                }
-        }
-    }
-    std::shared_ptr<EzpzSystem> sys_ref;
-    int32_t ec = -1;
-    int64_t ev = -1;
-    int rc = cached_system(cs, n_cs, n_guesses, true, &sys_ref, &ec, &ev);
-    call_stamp(CALL_PLAN);
-    EzpzSystem* sys = sys_ref.get();
-    if (rc != EZPZ_OK) {
-        if (rc == EZPZ_ERR_MISSING_GUESS && !dense) rc = EZPZ_ERR_MATRIX;  // id has a guess but no column
-        out->error = rc;
-        if (rc == EZPZ_ERR_MISSING_GUESS) {
-            out->err_constraint_id = (int32_t)((orig_ids && ec >= 0) ? orig_ids[ec] : ec);
-            out->err_variable = ev;
-        }
-        return rc;
-    }
-    if (num_eqs == 0 && cfg->max_iterations > 0) {  // newton.rs:54
-        out->error = EZPZ_ERR_EMPTY_SYSTEM;
-        return out->error;
-    }
-    // Every evaluation sweep may warn about every constraint: size the log so nothing is dropped.
-    // (only the sixteen non-linear kinds have a degenerate guard)
-    uint64_t n_guarded = 0;
-    for (size_t i = 0; i < n_cs; ++i) n_guarded += kind_is_linear(cs[i].kind) ? 0 : 1;
-    uint64_t want_log = n_guarded * (2 + 2 * std::min<uint64_t>(cfg->max_iterations, 1u << 20));
-    uint32_t log_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(want_log, 1), 1u << 22);
-    std::unique_ptr<uint64_t[]> log_store(new uint64_t[log_cap]);  // uninitialised: only written entries are read
-    uint64_t* log = log_store.get();
-    std::vector<uint8_t> mask(std::max<size_t>(n_cs, 1));
-    std::vector<double> x(std::max<size_t>(n_guesses, 1));
-    EzpzStatus st{};
-    call_stamp(CALL_SIDES);
-    rc = ezpz_system_solve_batch(sys, guesses, 1, cfg, x.data(), &st, mask.data(), log, log_cap);
-    if (rc != EZPZ_OK) {
-        out->error = rc;
-        return rc;
-    }
-    // Degenerate warnings in the reference's chronological order: sweep number, then constraint position;
-    // about_constraint is the position inside this tier's slice (solver.rs:327,:343).
-    uint32_t nlog = std::min<uint32_t>(st.n_warnings, log_cap);
-    std::sort(log, log + nlog);
-    for (uint32_t i = 0; i < nlog; ++i) sink.push((int32_t)(log[i] & 0xFFFFFFFFu), EZPZ_WARN_DEGENERATE);
-    sink.count += st.n_warnings - nlog;
-    out->n_warnings = sink.count;
-    uint64_t n_unsat = 0;
-    for (size_t i = 0; i < n_cs; ++i) {
-        if (mask[i]) {
-            if (unsat_ids) unsat_ids[n_unsat] = orig_ids ? orig_ids[i] : i;
-            ++n_unsat;
-        }
-    }
-    out->n_unsatisfied = n_unsat;
-    uint32_t lowest = 0;  // lib.rs:340-344
-    for (size_t i = 0; i < n_cs; ++i) lowest = std::max(lowest, cs[i].priority);
-    out->priority_solved = lowest;
-    out->iterations = st.iterations;
-    out->converged = (int32_t)st.converged;
-    out->final_lambda = st.final_lambda;
-    out->final_residual_inf = st.final_residual_inf;
-    if (under_out) {  // lib.rs:328-338: A::analyze(model); an error fails the tier
-        std::vector<uint8_t> free_mask(std::max<size_t>(n_guesses, 1));
-        rc = ezpz_system_freedom_batch(sys, x.data(), 1, free_mask.data(), nullptr);
-        if (rc != EZPZ_OK) {
-            out->error = rc;
-            return rc;
-        }
-        uint64_t k = 0;
-        for (size_t v = 0; v < n_guesses; ++v)
-            if (free_mask[v]) under_out[k++] = (uint32_t)v;
-        *n_under_out = k;
-    }
-    if (x_out && n_guesses) std::memcpy(x_out, x.data(), n_guesses * sizeof(double));
-    call_stamp(CALL_FINISHED);
-    return EZPZ_OK;
-}
-
-int solve_impl(const EzpzConstraint* reqs_in, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
-               size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids, EzpzWarning* warn_buf,
-               size_t warn_cap, EzpzOutcome* out, uint32_t* under_out, uint64_t* n_under_out);
-
-}  // namespace
-
-extern "C" {
-
-int ezpz_solve_inner(const EzpzConstraint* cs, const uint64_t* orig_ids, size_t n_cs, const uint32_t* var_ids,
-                     const double* guesses, size_t n_guesses, const EzpzConfig* cfg, double* x_out,
-                     uint64_t* unsat_ids, EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out) {
-    return solve_inner_impl(cs, orig_ids, n_cs, var_ids, guesses, n_guesses, cfg, x_out, unsat_ids, warn_buf,
-                            warn_cap, out, nullptr, nullptr);
-}
-
-int ezpz_solve(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
-               size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids, EzpzWarning* warn_buf,
-               size_t warn_cap, EzpzOutcome* out) {
-    return solve_impl(reqs, n_reqs, var_ids, guesses, n_guesses, cfg, x_out, unsat_ids, warn_buf, warn_cap, out,
-                      nullptr, nullptr);
-}
-
-int ezpz_solve_analysis(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
-                        size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids,
-                        EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out, uint32_t* under_out,
-                        uint64_t* n_under_out) {
-    if (!under_out || !n_under_out) return EZPZ_ERR_INVALID_ARGUMENT;
-    return solve_impl(reqs, n_reqs, var_ids, guesses, n_guesses, cfg, x_out, unsat_ids, warn_buf, warn_cap, out,
-                      under_out, n_under_out);
 }
 
 }  // extern "C"
@@ -344,6 +143,7 @@ struct TierPlan {
     int64_t validate_variable = -1;
     struct Analysed {
         std::vector<uint8_t> tags;  // the inferred sides this topology was analysed for (order of RequestPlan::undefined)
+        bool latency = true;        // launch shapes for the latency of one solve, or for batch throughput (ezpz_solve_batch)
         std::shared_ptr<EzpzSystem> sys;
         int rc = EZPZ_OK;
         int32_t ec = -1;
@@ -356,6 +156,7 @@ struct RequestPlan {
     std::vector<unsigned char> key;  // the request bytes
     uint64_t hash = 0;
     size_t n_reqs = 0, n_guesses = 0;
+    bool inner = false;             // solve_inner's plan of these bytes (ezpz_solve_inner): ONE tier of every request, no side inferred
     bool dense_ids = true;          // guess ids are 0..n-1 in order (or the caller passed none)
     std::vector<uint32_t> var_ids;  // otherwise
     size_t max_id = 0;
@@ -379,45 +180,36 @@ bool ids_are_dense(const uint32_t* var_ids, size_t n) {
     return true;
 }
 
-bool plan_matches(const RequestPlan& p, const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, size_t n_guesses,
-                  int device) {
-    if (p.n_reqs != n_reqs || p.n_guesses != n_guesses || p.device != device) return false;
+bool plan_matches(const RequestPlan& p, bool inner, const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids,
+                  size_t n_guesses, int device) {
+    if (p.inner != inner || p.n_reqs != n_reqs || p.n_guesses != n_guesses || p.device != device) return false;
     if (p.dense_ids ? !ids_are_dense(var_ids, n_guesses)
                     : (!var_ids || std::memcmp(p.var_ids.data(), var_ids, n_guesses * sizeof(uint32_t)) != 0))
         return false;
     return std::memcmp(p.key.data(), reqs, n_reqs * sizeof(EzpzConstraint)) == 0;
 }
 
-bool has_undefined_side(const EzpzConstraint& c) {
-    return (c.kind == EZPZ_LINE_TANGENT_TO_CIRCLE || c.kind == EZPZ_CIRCLE_TANGENT_TO_CIRCLE) && c.tag == EZPZ_SIDE_UNDEFINED;
-}
-
-std::shared_ptr<RequestPlan> build_plan(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, size_t n_guesses,
-                                        int device, uint64_t hash) {
+std::shared_ptr<RequestPlan> build_plan(bool inner, const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids,
+                                        size_t n_guesses, int device, uint64_t hash) {
     auto plan = std::make_shared<RequestPlan>();
     RequestPlan& p = *plan;
     p.key.assign(reinterpret_cast<const unsigned char*>(reqs), reinterpret_cast<const unsigned char*>(reqs) + n_reqs * sizeof(EzpzConstraint));
     p.hash = hash;
     p.n_reqs = n_reqs;
     p.n_guesses = n_guesses;
+    p.inner = inner;
     p.device = device;
     p.generation = g_plans_generation.load();
     p.dense_ids = ids_are_dense(var_ids, n_guesses);
     if (!p.dense_ids) p.var_ids.assign(var_ids, var_ids + n_guesses);
     for (size_t i = 0; i < n_guesses; ++i) p.max_id = std::max<size_t>(p.max_id, var_ids ? var_ids[i] : i);
-    for (size_t i = 0; i < n_reqs; ++i) {
-        const EzpzConstraint& c = reqs[i];
-        if (!has_undefined_side(c)) continue;
-        bool ok = n_guesses > 0;
-        const int cnt = c.kind == EZPZ_LINE_TANGENT_TO_CIRCLE ? 7 : 6;
-        for (int k = 0; k < cnt; ++k)
-            if (c.ids[k] > p.max_id) ok = false;  // the reference would panic on this index; the side stays Undefined
-        if (ok) p.undefined.push_back((uint32_t)i);
-    }
+    for (size_t i = 0; i < n_reqs && !inner; ++i)  // (an id without a value: the reference would panic on this index; the side stays Undefined)
+        if (has_undefined_side(reqs[i]) && n_guesses > 0 && side_ids_below(reqs[i], p.max_id + 1)) p.undefined.push_back((uint32_t)i);
     std::vector<uint32_t> prios;  // distinct priorities, ascending (lib.rs:199-203)
     for (size_t i = 0; i < n_reqs; ++i) prios.push_back(reqs[i].priority);
     std::sort(prios.begin(), prios.end());
     prios.erase(std::unique(prios.begin(), prios.end()), prios.end());
+    if (inner) prios.assign(1, prios.empty() ? 0 : prios.back());  // lib.rs:340-344: the list as it stands, whatever its priorities
     std::vector<uint8_t> present;
     if (!p.dense_ids) {
         present.assign(p.max_id + 1, 0);
@@ -473,21 +265,22 @@ std::shared_ptr<RequestPlan> build_plan(const EzpzConstraint* reqs, size_t n_req
 }
 
 // The plan of this request: the calling thread's previous one, one of the process's, or a new one.
-std::shared_ptr<RequestPlan> find_plan(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, size_t n_guesses, int device) {
+std::shared_ptr<RequestPlan> find_plan(bool inner, const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, size_t n_guesses,
+                                       int device) {
     const uint64_t gen = g_plans_generation.load(std::memory_order_relaxed);
-    if (t_last_plan && t_last_plan->generation == gen && plan_matches(*t_last_plan, reqs, n_reqs, var_ids, n_guesses, device))
+    if (t_last_plan && t_last_plan->generation == gen && plan_matches(*t_last_plan, inner, reqs, n_reqs, var_ids, n_guesses, device))
         return t_last_plan;
     const uint64_t h = topology_hash(reqs, n_reqs, n_guesses);
     {
         std::lock_guard<std::mutex> lock(g_plans_mu);
         for (auto it = g_plans.begin(); it != g_plans.end(); ++it) {
-            if ((*it)->hash == h && plan_matches(**it, reqs, n_reqs, var_ids, n_guesses, device)) {
+            if ((*it)->hash == h && plan_matches(**it, inner, reqs, n_reqs, var_ids, n_guesses, device)) {
                 g_plans.splice(g_plans.begin(), g_plans, it);
                 return t_last_plan = g_plans.front();
             }
         }
     }
-    std::shared_ptr<RequestPlan> plan = build_plan(reqs, n_reqs, var_ids, n_guesses, device, h);  // (outside the lock)
+    std::shared_ptr<RequestPlan> plan = build_plan(inner, reqs, n_reqs, var_ids, n_guesses, device, h);  // (outside the lock)
     call_stamp(COLD_PLAN_BUILT);
     std::lock_guard<std::mutex> lock(g_plans_mu);
     if (plan->generation == g_plans_generation.load()) {
@@ -497,19 +290,23 @@ std::shared_ptr<RequestPlan> find_plan(const EzpzConstraint* reqs, size_t n_reqs
     return t_last_plan = plan;
 }
 
-// The analysed topology of one tier for one choice of inferred sides (Model::new, solver.rs:192-300; cached).
-int analysed_for(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const uint8_t* tags, std::shared_ptr<EzpzSystem>* out,
-                 int32_t* ec, int64_t* ev) {
+// The analysed topology of one tier for one choice of inferred sides (Model::new, solver.rs:192-300; cached), with launch shapes
+// for the latency of one solve or for batch throughput.  Only the sides of the tier's own requests tell topologies apart.
+int analysed_for(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const uint8_t* tags, bool latency,
+                 std::shared_ptr<EzpzSystem>* out, int32_t* ec, int64_t* ev) {
     const size_t nu = p.undefined.size();
     {
         std::lock_guard<std::mutex> lock(p.mu);
-        for (TierPlan::Analysed& a : t.analysed)
-            if (a.tags.size() == nu && (nu == 0 || std::memcmp(a.tags.data(), tags, nu) == 0)) {
+        for (TierPlan::Analysed& a : t.analysed) {
+            bool same = a.latency == latency;
+            for (size_t u = 0; same && u < nu; ++u) same = a.tags[u] == tags[u] || reqs[p.undefined[u]].priority > t.lowest;
+            if (same) {
                 *out = a.sys;
                 *ec = a.ec;
                 *ev = a.ev;
                 return a.rc;
             }
+        }
     }
     // the symbolic phase runs outside the lock; two threads racing on a new topology both build it, one entry wins
     std::vector<EzpzConstraint> tier;
@@ -535,8 +332,9 @@ int analysed_for(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const 
     }
     TierPlan::Analysed a;
     if (nu) a.tags.assign(tags, tags + nu);
+    a.latency = latency;
     EzpzSystem* raw = nullptr;
-    a.rc = ezpz_system_create(cs, n_cs, p.n_guesses, p.device, EZPZ_TEAM_AUTO_LATENCY, &raw, &a.ec, &a.ev);
+    a.rc = ezpz_system_create(cs, n_cs, p.n_guesses, p.device, latency ? EZPZ_TEAM_AUTO_LATENCY : 0, &raw, &a.ec, &a.ev);
     if (a.rc == EZPZ_OK) a.sys = std::shared_ptr<EzpzSystem>(raw, [](EzpzSystem* s) { ezpz_system_destroy(s); });
     if (a.rc == EZPZ_ERR_HIP || a.rc == EZPZ_ERR_NO_DEVICE) {  // not a property of the request: not remembered
         *ec = a.ec;
@@ -568,32 +366,36 @@ T* grown(std::vector<T>& v, size_t n) {
 }
 
 // solve_inner (lib.rs:265-356) of one tier of a planned request.  unsat_ids / warn_buf / x_out may be the caller's own.
-int solve_tier(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const uint8_t* tags, const double* guesses,
-               const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids, EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out,
-               uint32_t* under_out, uint64_t* n_under_out) {
+// Lint warnings, the unsatisfied list and err_constraint_id name a request by its position in the caller's list, or by
+// orig_ids[position] where the caller has ids of its own (ConstraintEntry.id).
+int solve_tier(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const uint64_t* orig_ids, const uint8_t* tags,
+               const double* guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids, EzpzWarning* warn_buf, size_t warn_cap,
+               EzpzOutcome* out, uint32_t* under_out, uint64_t* n_under_out) {
+    auto listed = [&](size_t position) { return orig_ids ? orig_ids[position] : (uint64_t)position; };
+    auto member = [&](size_t i) { return listed(t.whole ? i : t.members[i]); };
     std::memset(out, 0, sizeof(*out));
     if (n_under_out) *n_under_out = 0;
     out->num_vars = p.n_guesses;
     out->num_eqs = t.num_eqs;
     WarnSink sink{warn_buf, warn_cap, 0};
-    for (const EzpzWarning& w : t.lint) sink.push(w.about_constraint, w.content);
+    for (const EzpzWarning& w : t.lint) sink.push((int32_t)listed((size_t)w.about_constraint), w.content);
     out->n_warnings = sink.count;
     if (t.validate_rc != EZPZ_OK) {
         out->error = t.validate_rc;
-        out->err_constraint_id = t.validate_constraint;
+        out->err_constraint_id = (int32_t)listed((size_t)t.validate_constraint);
         out->err_variable = t.validate_variable;
         return out->error;
     }
     std::shared_ptr<EzpzSystem> sys_ref;
     int32_t ec = -1;
     int64_t ev = -1;
-    int rc = analysed_for(p, t, reqs, tags, &sys_ref, &ec, &ev);
+    int rc = analysed_for(p, t, reqs, tags, /*latency=*/true, &sys_ref, &ec, &ev);
     call_stamp(CALL_SIDES);
     if (rc != EZPZ_OK) {
         if (rc == EZPZ_ERR_MISSING_GUESS && !p.dense_ids) rc = EZPZ_ERR_MATRIX;  // id has a guess but no column
         out->error = rc;
         if (rc == EZPZ_ERR_MISSING_GUESS) {
-            out->err_constraint_id = (int32_t)((!t.whole && ec >= 0) ? t.members[(size_t)ec] : ec);
+            out->err_constraint_id = ec >= 0 ? (int32_t)member((size_t)ec) : ec;
             out->err_variable = ev;
         }
         return rc;
@@ -633,7 +435,7 @@ int solve_tier(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const ui
     if (st.n_unsatisfied) {
         for (size_t i = 0; i < n_cs; ++i)
             if (mask[i]) {
-                if (unsat_ids) unsat_ids[n_unsat] = t.whole ? i : t.members[i];
+                if (unsat_ids) unsat_ids[n_unsat] = member(i);
                 ++n_unsat;
             }
     }
@@ -659,23 +461,25 @@ int solve_tier(RequestPlan& p, TierPlan& t, const EzpzConstraint* reqs, const ui
     return EZPZ_OK;
 }
 
-int solve_impl(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
-               size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids, EzpzWarning* warn_buf,
-               size_t warn_cap, EzpzOutcome* out, uint32_t* under_out, uint64_t* n_under_out) {
+// solve_with_priority_inner (lib.rs:148-263); with `inner`, solve_inner (lib.rs:265-356) of the list as it stands: the plan
+// has one tier and no side to infer, and orig_ids (may be null) are the caller's ids of the requests.
+int solve_impl(bool inner, const EzpzConstraint* reqs, const uint64_t* orig_ids, size_t n_reqs, const uint32_t* var_ids,
+               const double* guesses, size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids,
+               EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out, uint32_t* under_out, uint64_t* n_under_out) {
     if (!out) return EZPZ_ERR_INVALID_ARGUMENT;
     call_stamp(CALL_ENTER);
     if (n_under_out) *n_under_out = 0;  // A::no_constraints(), lib.rs:157,250
-    if (n_reqs == 0) {  // lib.rs:155-170
+    if (n_reqs == 0 && !inner) {  // lib.rs:155-170
         std::memset(out, 0, sizeof(*out));
         if (x_out && n_guesses) std::memcpy(x_out, guesses, n_guesses * sizeof(double));
         out->converged = 1;
         out->num_vars = n_guesses;
         return EZPZ_OK;
     }
-    if (!reqs || (n_guesses && !guesses)) return EZPZ_ERR_INVALID_ARGUMENT;
+    if ((n_reqs && !reqs) || (n_guesses && !guesses)) return EZPZ_ERR_INVALID_ARGUMENT;
     // (without a device the plan is still built: request errors are reported before the absence of a device)
     const int device = ezpz_current_device();
-    const std::shared_ptr<RequestPlan> plan = find_plan(reqs, n_reqs, var_ids, n_guesses, device);
+    const std::shared_ptr<RequestPlan> plan = find_plan(inner, reqs, n_reqs, var_ids, n_guesses, device);
     RequestPlan& p = *plan;
     call_stamp(CALL_PLAN);
     // the sides the guesses decide: initial_values[id] = guess (lib.rs:172-180), set_from_initial_values (lib.rs:183-186)
@@ -697,7 +501,7 @@ int solve_impl(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_id
         tags = tg;
     }
     if (p.tiers.size() == 1) {  // one tier (the common call): straight into the caller's buffers
-        const int rc = solve_tier(p, p.tiers[0], reqs, tags, guesses, cfg, x_out ? x_out : grown(t_scratch.x_try, std::max<size_t>(n_guesses, 1)),
+        const int rc = solve_tier(p, p.tiers[0], reqs, orig_ids, tags, guesses, cfg, x_out ? x_out : grown(t_scratch.x_try, std::max<size_t>(n_guesses, 1)),
                                   unsat_ids, warn_buf, warn_cap, out, under_out, n_under_out);
         call_stamp(CALL_RETURN);
         return rc;
@@ -719,7 +523,7 @@ int solve_impl(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_id
     };
     for (TierPlan& t : p.tiers) {  // cumulative subsets, each from the original guesses (lib.rs:205-246)
         EzpzOutcome o;
-        const int rc = solve_tier(p, t, reqs, tags, guesses, cfg, x_try, unsat_try, warn_try, warn_cap, &o, under_try, &n_under_try);
+        const int rc = solve_tier(p, t, reqs, orig_ids, tags, guesses, cfg, x_try, unsat_try, warn_try, warn_cap, &o, under_try, &n_under_try);
         if (rc == EZPZ_OK) {
             if (o.n_unsatisfied > 0 && have_res) break;  // lib.rs:232-234
             adopt(o);
@@ -745,16 +549,39 @@ int solve_impl(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_id
 
 }  // namespace
 
-extern "C" void ezpz_request_plans_clear(void) {
+extern "C" {
+
+void ezpz_request_plans_clear(void) {
     std::lock_guard<std::mutex> lock(g_plans_mu);
     g_plans_generation.fetch_add(1);  // (other threads' last plans go stale with it)
     g_plans.clear();
     t_last_plan.reset();
 }
 
-extern "C" {
+int ezpz_solve_inner(const EzpzConstraint* cs, const uint64_t* orig_ids, size_t n_cs, const uint32_t* var_ids,
+                     const double* guesses, size_t n_guesses, const EzpzConfig* cfg, double* x_out,
+                     uint64_t* unsat_ids, EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out) {
+    return solve_impl(true, cs, orig_ids, n_cs, var_ids, guesses, n_guesses, cfg, x_out, unsat_ids, warn_buf, warn_cap, out,
+                      nullptr, nullptr);
+}
 
-int ezpz_solve_batch(const EzpzConstraint* reqs_in, size_t n_reqs, size_t n_vars, const double* x0, size_t batch,
+int ezpz_solve(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
+               size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids, EzpzWarning* warn_buf,
+               size_t warn_cap, EzpzOutcome* out) {
+    return solve_impl(false, reqs, nullptr, n_reqs, var_ids, guesses, n_guesses, cfg, x_out, unsat_ids, warn_buf, warn_cap, out,
+                      nullptr, nullptr);
+}
+
+int ezpz_solve_analysis(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
+                        size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids,
+                        EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out, uint32_t* under_out,
+                        uint64_t* n_under_out) {
+    if (!under_out || !n_under_out) return EZPZ_ERR_INVALID_ARGUMENT;
+    return solve_impl(false, reqs, nullptr, n_reqs, var_ids, guesses, n_guesses, cfg, x_out, unsat_ids, warn_buf, warn_cap, out,
+                      under_out, n_under_out);
+}
+
+int ezpz_solve_batch(const EzpzConstraint* reqs, size_t n_reqs, size_t n_vars, const double* x0, size_t batch,
                      const EzpzConfig* cfg, double* x_out, EzpzStatus* status, uint32_t* priority_solved,
                      uint8_t* unsat_mask, int32_t* err_constraint, int64_t* err_variable) {
     if ((batch && (!x_out || !status)) || (batch && n_vars && !x0)) return EZPZ_ERR_INVALID_ARGUMENT;
@@ -768,22 +595,15 @@ int ezpz_solve_batch(const EzpzConstraint* reqs_in, size_t n_reqs, size_t n_vars
         }
         return EZPZ_OK;
     }
+    if (!reqs) return EZPZ_ERR_INVALID_ARGUMENT;
+    // tiers, the requests with a side to infer and the analysed topologies: the request's plan, shared with ezpz_solve
+    // (without a device the plan is still built: request errors are reported before the absence of a device)
+    const std::shared_ptr<RequestPlan> plan = find_plan(false, reqs, n_reqs, nullptr, n_vars, ezpz_current_device());
+    RequestPlan& p = *plan;
+    const std::vector<uint32_t>& undefined = p.undefined;
     // ---- per-system side inference, systems grouped by the sides they infer ------------------------------------------
-    std::vector<size_t> undefined;  // requests whose side is inferred
-    for (size_t i = 0; i < n_reqs; ++i) {
-        const EzpzConstraint& c = reqs_in[i];
-        if ((c.kind == EZPZ_LINE_TANGENT_TO_CIRCLE || c.kind == EZPZ_CIRCLE_TANGENT_TO_CIRCLE) &&
-            c.tag == EZPZ_SIDE_UNDEFINED) {
-            bool ok = true;
-            const int cnt = c.kind == EZPZ_LINE_TANGENT_TO_CIRCLE ? 7 : 6;
-            for (int k = 0; k < cnt; ++k)
-                if (c.ids[k] >= n_vars) ok = false;
-            if (ok) undefined.push_back(i);
-        }
-    }
     std::map<std::vector<uint8_t>, std::vector<size_t>> groups;
     {
-        std::vector<double> iv(n_vars);
         std::vector<uint8_t> key(undefined.size());
         if (undefined.empty()) {  // one group: every system, in order
             std::vector<size_t>& all = groups[key];
@@ -791,74 +611,57 @@ int ezpz_solve_batch(const EzpzConstraint* reqs_in, size_t n_reqs, size_t n_vars
             for (size_t b = 0; b < batch; ++b) all[b] = b;
         } else {
             for (size_t b = 0; b < batch; ++b) {
-                std::memcpy(iv.data(), x0 + b * n_vars, n_vars * sizeof(double));
                 for (size_t u = 0; u < undefined.size(); ++u) {
-                    EzpzConstraint c = reqs_in[undefined[u]];
-                    set_from_initial_values(c, iv.data());
+                    EzpzConstraint c = reqs[undefined[u]];
+                    set_from_initial_values(c, x0 + b * n_vars);
                     key[u] = c.tag;
                 }
                 groups[key].push_back(b);
             }
         }
     }
-    std::vector<uint32_t> prios;
-    for (size_t i = 0; i < n_reqs; ++i) prios.push_back(reqs_in[i].priority);
-    std::sort(prios.begin(), prios.end());
-    prios.erase(std::unique(prios.begin(), prios.end()), prios.end());
-
-    std::vector<EzpzConstraint> reqs(reqs_in, reqs_in + n_reqs), subset;
-    std::vector<size_t> subset_ids;
     std::vector<double> xin, xres;
     std::vector<EzpzStatus> stres;
     std::vector<uint8_t> maskres;
     for (auto& g : groups) {
-        for (size_t u = 0; u < undefined.size(); ++u) reqs[undefined[u]].tag = g.first[u];
         std::vector<size_t> active = g.second;
         std::vector<char> have_res(batch, 0);
         bool first_tier = true;
-        for (uint32_t curr_max_priority : prios) {
+        for (TierPlan& t : p.tiers) {  // cumulative subsets, each from the original guesses (lib.rs:205-246)
             if (active.empty()) break;
-            subset.clear();
-            subset_ids.clear();
-            uint32_t lowest = 0;
-            for (size_t i = 0; i < n_reqs; ++i)
-                if (reqs[i].priority <= curr_max_priority) {
-                    subset.push_back(reqs[i]);
-                    subset_ids.push_back(i);
-                    lowest = std::max(lowest, reqs[i].priority);
-                }
+            auto position = [&](size_t k) { return t.whole ? k : (size_t)t.members[k]; };  // of the tier's k-th request in `reqs`
             std::shared_ptr<EzpzSystem> sys_ref;
             int32_t ec = -1;
             int64_t ev = -1;
-            int rc = cached_system(subset.data(), subset.size(), n_vars, batch == 1, &sys_ref, &ec, &ev);
+            int rc = analysed_for(p, t, reqs, g.first.data(), /*latency=*/batch == 1, &sys_ref, &ec, &ev);
             EzpzSystem* sys = sys_ref.get();
             if (rc != EZPZ_OK) {
                 if (first_tier) {  // lib.rs:239-244: no earlier tier to fall back to
-                    if (err_constraint) *err_constraint = ec >= 0 ? (int32_t)subset_ids[(size_t)ec] : -1;
+                    if (err_constraint) *err_constraint = ec >= 0 ? (int32_t)position((size_t)ec) : -1;
                     if (err_variable) *err_variable = ev;
                     return rc;
                 }
                 break;  // every system of the group keeps its previous tier
             }
-            const size_t na = active.size(), ns = subset.size();
+            const size_t na = active.size(), ns = t.whole ? n_reqs : t.members.size();
             if (first_tier && na == batch) {
                 // The whole batch in one group, first tier (the common call: no side to infer, one priority): the systems
                 // are 0..batch-1 in order and every result is kept (lib.rs:232-234 only drops an unsatisfied *later*
                 // tier), so the solve reads the caller's guesses and writes the caller's outputs -- no gather, no scatter.
-                const bool direct_mask = unsat_mask && ns == n_reqs;  // subset_ids is the identity
+                const bool direct_mask = unsat_mask && ns == n_reqs;  // position() is the identity
                 if (unsat_mask && !direct_mask) maskres.assign(na * std::max<size_t>(ns, 1), 0);
                 rc = ezpz_system_solve_batch(sys, x0, na, cfg, x_out, status,
                                              unsat_mask ? (direct_mask ? unsat_mask : maskres.data()) : nullptr, nullptr, 0);
                 if (rc != EZPZ_OK) return rc;
                 if (priority_solved)
-                    for (size_t b = 0; b < batch; ++b) priority_solved[b] = lowest;
+                    for (size_t b = 0; b < batch; ++b) priority_solved[b] = t.lowest;
                 if (unsat_mask && !direct_mask) {
                     std::memset(unsat_mask, 0, batch * n_reqs);
                     for (size_t b = 0; b < batch; ++b)
-                        for (size_t k = 0; k < ns; ++k) unsat_mask[b * n_reqs + subset_ids[k]] = maskres[b * ns + k];
+                        for (size_t k = 0; k < ns; ++k) unsat_mask[b * n_reqs + position(k)] = maskres[b * ns + k];
                 }
                 std::fill(have_res.begin(), have_res.end(), 1);
-                if (prios.size() > 1) {
+                if (p.tiers.size() > 1) {
                     std::vector<size_t> still;
                     for (size_t b = 0; b < batch; ++b)
                         if (status[b].n_unsatisfied == 0) still.push_back(b);
@@ -884,10 +687,10 @@ int ezpz_solve_batch(const EzpzConstraint* reqs_in, size_t n_reqs, size_t n_vars
                 if (unsat && have_res[b]) continue;  // lib.rs:232-234: keep the previous, satisfied tier
                 std::memcpy(x_out + b * n_vars, xres.data() + a * n_vars, n_vars * sizeof(double));
                 status[b] = stres[a];
-                if (priority_solved) priority_solved[b] = lowest;
+                if (priority_solved) priority_solved[b] = t.lowest;
                 if (unsat_mask) {
                     std::memset(unsat_mask + b * n_reqs, 0, n_reqs);
-                    for (size_t k = 0; k < ns; ++k) unsat_mask[b * n_reqs + subset_ids[k]] = maskres[a * ns + k];
+                    for (size_t k = 0; k < ns; ++k) unsat_mask[b * n_reqs + position(k)] = maskres[a * ns + k];
                 }
                 have_res[b] = 1;
                 if (!unsat) still.push_back(b);

@@ -517,9 +517,10 @@ int ezpz_resolve_sides(EzpzConstraint* cs, size_t n_cs, const double* values, si
 int ezpz_system_specialize(EzpzSystem* sys, int wait);
 long ezpz_specialized_source(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, int compile, char* buf, size_t cap);
 
-/* ezpz_solve / ezpz_solve_inner keep a small cache of analysed topologies keyed by the request bytes, so that
+/* ezpz_solve, ezpz_solve_analysis, ezpz_solve_inner and ezpz_solve_batch keep one small cache of request plans keyed by
+ * the request bytes (tiers, lint, validation, the analysed topology of every tier and choice of inferred sides), so that
  * repeated solves of one problem (ezpz-cli's 100-run loop, main.rs:96-98) skip the symbolic phase.  This drops
- * it (used to time cold solves). */
+ * it, and the handles behind ezpz_system_solve_batch_multi (used to time cold solves). */
 void ezpz_cache_clear(void);
 
 /* The launch-shape thresholds (csrc/policy.hpp has each number's measurement): what decides which kernel serves a call,

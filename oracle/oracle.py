@@ -401,9 +401,10 @@ def _split_guesses(guesses):
 
 
 def solve(reqs, guesses, config: Optional[Config] = None, linsolve: int = LINSOLVE_DENSE,
-          warn_cap: int = 4096, analysis: bool = False) -> Outcome:
+          warn_cap: int = 4096, analysis: bool = False, inner: bool = False, orig_ids=None) -> Outcome:
     """`ezpz::solve` (lib.rs:80-87) or, with analysis=True, `ezpz::solve_analysis` (lib.rs:134-146) on the CPU
-    oracle.  guesses: [(id, value), ...] or a float array."""
+    oracle; with inner=True `solve_inner` (lib.rs:265-356) on the records as they stand, `orig_ids` (optional) being the
+    ids it reports.  guesses: [(id, value), ...] or a float array."""
     cfg = (config or Config())._c()
     a = stack(reqs)
     ids, vals = _split_guesses(guesses)
@@ -417,7 +418,10 @@ def solve(reqs, guesses, config: Optional[Config] = None, linsolve: int = LINSOL
     args = (a.ctypes.data if len(a) else None, len(a), ids.ctypes.data if n else None,
             vals.ctypes.data if n else None, n, C.byref(cfg), linsolve, x_out.ctypes.data,
             unsat.ctypes.data, C.cast(warns, C.c_void_p), warn_cap, C.byref(out))
-    if analysis:
+    if inner:
+        oid = None if orig_ids is None else np.ascontiguousarray(orig_ids, dtype=np.uint64)
+        lib().orc_solve_inner(args[0], oid.ctypes.data if oid is not None and len(oid) else None, *args[1:])
+    elif analysis:
         lib().orc_solve_analysis(*args, under.ctypes.data, C.byref(n_under))
     else:
         lib().orc_solve(*args)

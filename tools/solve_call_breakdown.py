@@ -3,7 +3,7 @@ benchmark: ezpz-cli/src/main.rs:86-100, ezpz/benches/solver_bench.rs:15-24): per
 (the library's own stamps, ezpz_debug_call_trace), the kernel's duration on the device (HIP events around launches on
 device buffers, the same kernel the call used) and the first call of the process.
 
-usage (GPU box): python tools/solve_call_breakdown.py > profiles/r04_solve_call_breakdown.txt
+usage (GPU box): python tools/solve_call_breakdown.py [case name ...] > profiles/r04_solve_call_breakdown.txt
 The kernel durations come from a kernel trace of the same systems:
     rocprofv3 --kernel-trace -d gpurun_out/scb -o scb --output-format csv -- python3 tools/solve_call_breakdown.py --launch-only
     python tools/solve_call_breakdown.py --from-trace gpurun_out/scb/.../scb_kernel_trace.csv   (appends the per-case table)"""
@@ -51,13 +51,16 @@ CASES = [("tiny", lambda: case("tiny")), ("nonsquare", lambda: case("nonsquare")
          ("two rectangles dependent", two_rectangles_dependent), ("arc_radius", lambda: case("arc_radius")),
          ("massive 800 x 800", lambda: massive(200)), ("massive 2000 x 2000", lambda: massive(500)),
          ("massive 2400 x 2400", lambda: massive(600))]
+INNER_CASES = ("square", "massive 2000 x 2000")  # also timed through ezpz_solve_inner (no side to infer, one priority: the same solve)
 
 
-def main():
+def main(only=()):
     L = E.lib()
     first = True
     print("# python tools/solve_call_breakdown.py -- one ezpz_solve call per iteration, stages in microseconds (mean of the warm calls)")
     for name, build in CASES:
+        if only and name not in only:
+            continue
         reqs, guesses = build()
         recs = O.stack(reqs)
         ids = np.ascontiguousarray([g[0] for g in guesses], dtype=np.uint32)
@@ -122,6 +125,14 @@ def main():
         print("   warm: " + " | ".join(f"{STAGES[k]} {v / reps:.1f}" for k, v in sorted(acc.items())))
         order = [20, 21, 22, 23, 2, 3, 4, 5, 6, 7, 8, 9, 10]
         print("   cold: " + " | ".join(f"{STAGES[k]} {cold_acc[k]:.1f}" for k in order if k in cold_acc))
+        if name in INNER_CASES:
+            inner = lambda: L.ezpz_solve_inner(args[0], None, *args[1:])
+            for _ in range(450):
+                assert inner() == 0
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                inner()
+            print(f"   ezpz_solve_inner: warm call {(time.perf_counter() - t0) / reps * 1e6:6.1f} us (ctypes included)")
     print(f"# device: {E.device_count()} x HIP device; stamps cost ~0.03 us each")
 
 
@@ -180,4 +191,4 @@ if __name__ == "__main__":
     elif "--from-trace" in sys.argv:
         from_trace(sys.argv[sys.argv.index("--from-trace") + 1])
     else:
-        main()
+        main(sys.argv[1:])
