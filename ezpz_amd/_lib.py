@@ -64,6 +64,13 @@ class CSensitivityPlan(C.Structure):
                 ("lds_bytes", C.c_uint32), ("workspace_bytes", C.c_uint64)]
 
 
+class CSweepPlan(C.Structure):
+    _fields_ = [("route", C.c_uint32), ("in_kernel", C.c_uint32), ("params_in_lds", C.c_uint32), ("lds_bytes", C.c_uint32)]
+
+
+SWEEP_ROUTES = ("interpreter", "sub-wavefront teams", "partitioned workgroup", "barrier workgroup", "record walk")  # EZPZ_SWEEP_*
+
+
 class CViewport(C.Structure):
     _fields_ = [("x_min", C.c_double), ("x_max", C.c_double), ("y_min", C.c_double), ("y_max", C.c_double),
                 ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -95,6 +102,7 @@ EXPORTS = [
     "ezpz_constraint_has_param", "ezpz_system_solve_batch_params_device", "ezpz_system_solve_batch_params",
     "ezpz_constraint_param_derivative", "ezpz_system_param_sensitivity_plan", "ezpz_system_param_sensitivity_device",
     "ezpz_system_param_sensitivity",
+    "ezpz_system_sweep_params_plan", "ezpz_system_sweep_params_device", "ezpz_system_sweep_params",
 ]
 
 _lib = None
@@ -221,6 +229,12 @@ def lib():
     L.ezpz_system_param_sensitivity_device.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp, vp]
     L.ezpz_system_param_sensitivity.restype = C.c_int
     L.ezpz_system_param_sensitivity.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp]
+    L.ezpz_system_sweep_params_plan.restype = C.c_int
+    L.ezpz_system_sweep_params_plan.argtypes = [vp, vp, sz, C.POINTER(CSweepPlan)]
+    L.ezpz_system_sweep_params_device.restype = C.c_int
+    L.ezpz_system_sweep_params_device.argtypes = [vp, vp, vp, sz, vp, sz, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32, vp]
+    L.ezpz_system_sweep_params.restype = C.c_int
+    L.ezpz_system_sweep_params.argtypes = [vp, vp, vp, sz, vp, sz, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32]
     L.ezpz_solve_inner.restype = C.c_int
     L.ezpz_solve_inner.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(CConfig), vp, vp, vp, sz, C.POINTER(COutcome)]
     L.ezpz_solve.restype = C.c_int

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSystemInfo, CWarning, lib
+from ._lib import SWEEP_ROUTES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -818,6 +818,64 @@ class System:
         if rc != 0:
             raise NonLinearSystemError(rc)
 
+
+    def sweep_params(self, x0: np.ndarray, positions, params: np.ndarray, config: Optional[Config] = None, want_mask: bool = False,
+                     warn_log: Optional[np.ndarray] = None):
+        """`ezpz_system_sweep_params`: a chain of driven solves per system.  x0 [batch, n_vars] are the sweeps' starts, params
+        [steps, batch, len(positions)] their dimension sets step by step; step k of sweep b starts from step k - 1's answer.
+        Returns (x [steps, batch, n_vars], status [steps, batch], mask [steps, batch, n_cs] or None) -- exactly what `steps` chained
+        solve_batch_params calls give.  warn_log: a C-contiguous uint64 array [steps, batch, warn_cap] of the caller's that receives
+        the raw warning log (the first min(status["n_warnings"], warn_cap) entries of a row are written: pass << 32 | constraint
+        position; the others are left as they are)."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, max(self.n_vars, 1))
+        batch = x0.shape[0]
+        pos = self._positions(positions)
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if params.ndim != 3 or params.shape[1:] != (batch, len(pos)):
+            raise ValueError(f"params: expected shape (steps, {batch}, {len(pos)}), got {params.shape}")
+        steps = params.shape[0]
+        warn_cap = 0
+        if warn_log is not None:
+            if (not isinstance(warn_log, np.ndarray) or warn_log.dtype != np.uint64 or not warn_log.flags.c_contiguous
+                    or not warn_log.flags.writeable or warn_log.ndim != 3 or warn_log.shape[:2] != (steps, batch)):
+                raise ValueError(f"warn_log: expected a writeable C-contiguous uint64 array of shape ({steps}, {batch}, warn_cap)")
+            warn_cap = warn_log.shape[2]
+        cfg = (config or Config())._c()
+        x = np.empty((steps, batch, x0.shape[1]))
+        st = np.zeros((steps, batch), dtype=STATUS_DTYPE)
+        mask = np.zeros((steps, batch, max(len(self.records), 1)), dtype=np.uint8) if want_mask else None
+        rc = lib().ezpz_system_sweep_params(self._h, x0.ctypes.data, pos.ctypes.data if len(pos) else None, len(pos),
+                                            params.ctypes.data if len(pos) else None, steps, batch, C.byref(cfg), x.ctypes.data,
+                                            st.ctypes.data, mask.ctypes.data if want_mask else None,
+                                            warn_log.ctypes.data if warn_cap else None, warn_cap)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return x, st, mask
+
+    def sweep_params_device(self, x0_ptr: int, positions, params_ptr: int, steps: int, batch: int, x_out_ptr: int, status_ptr: int,
+                            mask_ptr: int = 0, stream: int = 0, config: Optional[Config] = None) -> None:
+        """Device pointers and a hipStream_t handle; enqueue only.  params_ptr addresses [steps, batch, len(positions)] doubles,
+        x_out_ptr [steps, batch, n_vars], status_ptr [steps, batch] statuses, mask_ptr [steps, batch, n_cs] bytes; x0_ptr
+        [batch, n_vars] may be x_out_ptr itself."""
+        pos = self._positions(positions)
+        cfg = (config or Config())._c()
+        rc = lib().ezpz_system_sweep_params_device(self._h, x0_ptr or None, pos.ctypes.data if len(pos) else None, len(pos),
+                                                   params_ptr or None, steps, batch, C.byref(cfg), x_out_ptr or None,
+                                                   status_ptr or None, mask_ptr or None, None, 0, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+    def sweep_params_plan(self, positions) -> dict:
+        """`ezpz_system_sweep_params_plan`: the route a sweep of this list takes (`route`, and its name as `route_name`), whether it is
+        one launch (`in_kernel`), `params_in_lds`, `lds_bytes`.  Diagnostic."""
+        pos = self._positions(positions)
+        p = CSweepPlan()
+        rc = lib().ezpz_system_sweep_params_plan(self._h, pos.ctypes.data if len(pos) else None, len(pos), C.byref(p))
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        out = {f: getattr(p, f) for f, _ in CSweepPlan._fields_}
+        out["route_name"] = SWEEP_ROUTES[p.route]
+        return out
 
     def param_sensitivity(self, x: np.ndarray, positions, params: Optional[np.ndarray] = None, lam: Optional[float] = None,
                           want_degenerate: bool = False):

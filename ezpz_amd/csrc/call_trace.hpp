@@ -25,6 +25,9 @@ enum CallStage : uint32_t {
     COLD_ANALYSED = 21,       // analyze_into: components / classes / elimination order / lists (Model::new's counterpart)
     COLD_UPLOADED = 22,       // device allocations + program upload
     COLD_KERNEL_FOUND = 23,   // the specialised kernel's registry entry (source text compared)
+    // ezpz_system_sweep_params_device (sweep.hip)
+    SWEEP_TABLE_UPLOADED = 30,  // a `positions` list other than the system's last one: waited for earlier launches, copied its table
+    SWEEP_LAUNCHED = 31,        // the one launch of the sweep enqueued
 };
 
 struct CallTrace {

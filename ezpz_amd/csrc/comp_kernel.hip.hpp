@@ -53,6 +53,9 @@ struct CompArgs {
     const double* params;
     const uint32_t* par_overlay;
     uint32_t n_param;
+    // SWP builds (ezpz_system_sweep_params): `batch` sweeps of `steps` solves each; row k * batch + q of params, x_out, status,
+    // unsat_mask and warn_log belongs to step k of sweep q, row q of x0 is where the sweep starts
+    uint32_t steps;
 };
 
 namespace dev {
@@ -172,6 +175,16 @@ __device__ __forceinline__ DevCon comp_make_con(const CompRec8& a, const CompRec
     return c;
 }
 
+// The next item of a workgroup's walk: the next system of its stride -- or, in a sweep build, the next step of its sweep first.
+template <bool SWP>
+__device__ __forceinline__ void comp_next_item(uint64_t& q, uint32_t& step, uint32_t steps, uint64_t stride) {
+    if constexpr (SWP) {
+        if (++step < steps) return;
+        step = 0;
+    }
+    q += stride;
+}
+
 }  // namespace dev
 
 // LIN: every class is linear with constant Jacobian (no Jacobian storage, no warnings);
@@ -180,7 +193,11 @@ __device__ __forceinline__ DevCon comp_make_con(const CompRec8& a, const CompRec
 // PAR: the build of ezpz_system_solve_batch_params: a lane's parameter is its system's own value where the call's overlay
 // names one (each value has exactly one reader -- the lane of its component -- so it is read where the caller left it), else
 // the table's; the other builds are untouched.
-template <bool LIN, bool PAR = false>
+// SWP: the build of ezpz_system_sweep_params (implies PAR; instantiated in sweep.hip only): the workgroup that takes sweep q
+// runs its CompArgs::steps solves back to back as items of the same loop -- a lane loads its component's values from x0 at step 0
+// only and keeps them in its rows from one step to the next (they are the bits it just stored to x_out); the parameter row, the
+// output rows, the warning counter and the LM state are an item's own, as they are a system's.
+template <bool LIN, bool PAR = false, bool SWP = false>
 __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using namespace dev;
@@ -208,8 +225,11 @@ __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
     const unsigned long long born = wall_clock64();
     DoneWord done = a.done;
     do {
-    for (uint64_t sys = blockIdx.x; sys < a.batch; sys += gridDim.x, parity ^= 1u) {
-        const double* x0 = a.x0 + sys * a.n_row;
+    static_assert(!SWP || PAR, "a sweep drives parameters");
+    uint32_t step = 0;  // (sweep builds: the step of sweep q this item is)
+    for (uint64_t q = blockIdx.x; q < a.batch; comp_next_item<SWP>(q, step, a.steps, gridDim.x), parity ^= 1u) {
+        const uint64_t sys = SWP ? (uint64_t)step * a.batch + q : q;  // the row of everything but x0
+        const double* x0 = a.x0 + q * a.n_row;
         int* nwarn = nwarn2 + parity;
         // constraint ci's parameter for this lane (`par`, `ovl`: the chunk's tables at this lane)
         auto param_of = [&](const double* par, const uint32_t* ovl, uint32_t ci, uint32_t stride) {
@@ -315,7 +335,8 @@ __global__ void __launch_bounds__(512) comp_solve_kernel(const CompArgs a) {
             const bool active = (uint32_t)lane < K.count;
             const uint32_t* ids = a.prog + K.ids_off + lane;
             // (four values in flight at a time: the id and the value are two dependent trips to L2 / HBM)
-            for (uint32_t k0 = 0; k0 < K.nv; k0 += 4) {
+            // (a sweep behind its first step: the rows hold the previous step's answer)
+            for (uint32_t k0 = 0; (!SWP || step == 0) && k0 < K.nv; k0 += 4) {
                 uint32_t id[4];
                 double v[4];
 #pragma unroll

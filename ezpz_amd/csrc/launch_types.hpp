@@ -60,6 +60,10 @@ struct SolveArgs {
     uint32_t prog_lds_doubles;  // LDS doubles reserved for the staged program (PLDS), 0 otherwise
     uint32_t max_iterations;
     uint32_t unit_weights;  // every constraint weight == 1.0 (the common case): weighted r == unweighted r
+    // sweeps (SWP builds: ezpz_system_sweep_params): `batch` sweeps of `steps` solves each; row k * batch + q of params, x_out, status,
+    // unsat_mask and warn_log belongs to step k of sweep q, row q of x0 is where the sweep starts.  (Here, where the block had four
+    // bytes of padding: its layout, and with it every other build's code, is what it was.)
+    uint32_t steps;
     double residual_tolerance, step_tolerance, initial_lambda;
     unsigned long long* stamps;  // diagnostic builds (-DEZPZ_STAMPS) only: (id, s_memtime) pairs of block 0, lane 0
     GridScratch* grid_scratch;   // grid teams: one per system in flight

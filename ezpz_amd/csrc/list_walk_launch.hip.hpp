@@ -1,8 +1,9 @@
 // Which instantiation of lm_solve_kernel a launch of a system on ONE workgroup per system (or less) takes: sub-wavefront teams,
 // the wavefront-partitioned workgroup, the barrier workgroup with its workspace in LDS or in global memory, the record walk.
-// Included by the two translation units that instantiate those kernels: launch.hip (PAR = false: every entry point but one) and
-// params.hip (PAR = true: ezpz_system_solve_batch_params, whose systems bring their own constraint parameters) -- the two
-// sets of builds compile side by side.  (The caller holds the system's launch lock.)
+// Included by the three translation units that instantiate those kernels: launch.hip (PAR = false: every entry point but two),
+// params.hip (PAR = true: ezpz_system_solve_batch_params, whose systems bring their own constraint parameters) and sweep.hip
+// (PAR and SWP: ezpz_system_sweep_params, a chain of such solves per system in one launch; `batch` counts sweeps there) -- the
+// three sets of builds compile side by side.  (The caller holds the system's launch lock.)
 #pragma once
 #include "system.hpp"
 
@@ -11,9 +12,9 @@
 namespace ezpz {
 
 // `lds_bytes`: the launch's dynamic LDS -- the system's, plus the teams' parameter copies of a PAR launch.
-template <bool PAR, int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool DENSE = false, int REC = 0>
+template <bool PAR, bool SWP, int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool DENSE = false, int REC = 0>
 int launch_kernel(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
-    auto kernel = lm_solve_kernel<TEAM, MODE, LDSWS, PLDS, LIN, false, DENSE, REC, PAR>;
+    auto kernel = lm_solve_kernel<TEAM, MODE, LDSWS, PLDS, LIN, false, DENSE, REC, PAR, SWP>;
     // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel, not to the system: raised once per kernel
     // build and device, to everything the device allows, so that systems of different sizes sharing a build never
     // lower each other's limit
@@ -29,21 +30,21 @@ int launch_kernel(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t ld
 }
 
 // Every team shape comes in two builds: all 25 kinds, or the nine linear kinds only (`linear_only` topologies).
-template <bool PAR, int TEAM, int MODE, bool LDSWS, bool PLDS>
+template <bool PAR, bool SWP, int TEAM, int MODE, bool LDSWS, bool PLDS>
 int launch_variant(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
-    if (s.linear_only) return launch_kernel<PAR, TEAM, MODE, LDSWS, PLDS, true>(s, args, grid, lds_bytes, stream);
-    return launch_kernel<PAR, TEAM, MODE, LDSWS, PLDS, false>(s, args, grid, lds_bytes, stream);
+    if (s.linear_only) return launch_kernel<PAR, SWP, TEAM, MODE, LDSWS, PLDS, true>(s, args, grid, lds_bytes, stream);
+    return launch_kernel<PAR, SWP, TEAM, MODE, LDSWS, PLDS, false>(s, args, grid, lds_bytes, stream);
 }
 
-template <bool PAR, int TEAM>
+template <bool PAR, bool SWP, int TEAM>
 int launch_sub(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
     if constexpr (TEAM == 4) {  // <= 8 variables: dense factor layout, solved in registers (always staged)
         if (s.counts.dense)
-            return s.linear_only ? launch_kernel<PAR, TEAM, MODE_SUB, true, true, true, true>(s, args, grid, lds_bytes, stream)
-                                 : launch_kernel<PAR, TEAM, MODE_SUB, true, true, false, true>(s, args, grid, lds_bytes, stream);
+            return s.linear_only ? launch_kernel<PAR, SWP, TEAM, MODE_SUB, true, true, true, true>(s, args, grid, lds_bytes, stream)
+                                 : launch_kernel<PAR, SWP, TEAM, MODE_SUB, true, true, false, true>(s, args, grid, lds_bytes, stream);
     }
-    return s.prog_in_lds ? launch_variant<PAR, TEAM, MODE_SUB, true, true>(s, args, grid, lds_bytes, stream)
-                         : launch_variant<PAR, TEAM, MODE_SUB, true, false>(s, args, grid, lds_bytes, stream);
+    return s.prog_in_lds ? launch_variant<PAR, SWP, TEAM, MODE_SUB, true, true>(s, args, grid, lds_bytes, stream)
+                         : launch_variant<PAR, SWP, TEAM, MODE_SUB, true, false>(s, args, grid, lds_bytes, stream);
 }
 
 // The system's workspace in global memory -- the lanes kernel's, the list walk's when its workspace or its Jacobian lives there -- is
@@ -57,7 +58,7 @@ int on_workspace(EzpzSystem& s, hipStream_t stream, Launch&& launch) {
     return rc;
 }
 
-template <bool PAR>
+template <bool PAR, bool SWP = false>
 int list_walk_one_workgroup(EzpzSystem& s, SolveArgs& args, size_t lds_bytes, hipStream_t stream) {
     uint32_t grid;
     if (s.mode == MODE_SUB) {
@@ -65,13 +66,13 @@ int list_walk_one_workgroup(EzpzSystem& s, SolveArgs& args, size_t lds_bytes, hi
         uint64_t blocks = (args.batch + tpb - 1) / tpb;
         grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)s.lim.cus * 32);
         switch (s.team_size) {
-        case 1: return launch_sub<PAR, 1>(s, args, grid, lds_bytes, stream);
-        case 2: return launch_sub<PAR, 2>(s, args, grid, lds_bytes, stream);
-        case 4: return launch_sub<PAR, 4>(s, args, grid, lds_bytes, stream);
-        case 8: return launch_sub<PAR, 8>(s, args, grid, lds_bytes, stream);
-        case 16: return launch_sub<PAR, 16>(s, args, grid, lds_bytes, stream);
-        case 32: return launch_sub<PAR, 32>(s, args, grid, lds_bytes, stream);
-        default: return launch_sub<PAR, 64>(s, args, grid, lds_bytes, stream);
+        case 1: return launch_sub<PAR, SWP, 1>(s, args, grid, lds_bytes, stream);
+        case 2: return launch_sub<PAR, SWP, 2>(s, args, grid, lds_bytes, stream);
+        case 4: return launch_sub<PAR, SWP, 4>(s, args, grid, lds_bytes, stream);
+        case 8: return launch_sub<PAR, SWP, 8>(s, args, grid, lds_bytes, stream);
+        case 16: return launch_sub<PAR, SWP, 16>(s, args, grid, lds_bytes, stream);
+        case 32: return launch_sub<PAR, SWP, 32>(s, args, grid, lds_bytes, stream);
+        default: return launch_sub<PAR, SWP, 64>(s, args, grid, lds_bytes, stream);
         }
     }
     const uint32_t per_cu = s.lds_ws ? (uint32_t)std::max<size_t>(1, s.lim.lds_bytes / std::max<size_t>(lds_bytes, 1))
@@ -93,26 +94,26 @@ int list_walk_one_workgroup(EzpzSystem& s, SolveArgs& args, size_t lds_bytes, hi
         if (rc != EZPZ_OK) return rc;
         args.gws = s.gws_dev.p;
         return on_workspace(s, stream, [&] {
-            return s.mode == MODE_PART ? launch_variant<PAR, 64, MODE_PART, false, false>(s, args, grid, lds_bytes, stream)
-                   : !s.rec            ? launch_variant<PAR, 64, MODE_WGB, false, false>(s, args, grid, lds_bytes, stream)
-                   : s.linear_only     ? launch_kernel<PAR, 64, MODE_WGB, false, false, true, false, 2>(s, args, grid, lds_bytes, stream)
-                                       : launch_kernel<PAR, 64, MODE_WGB, false, false, false, false, 2>(s, args, grid, lds_bytes, stream);
+            return s.mode == MODE_PART ? launch_variant<PAR, SWP, 64, MODE_PART, false, false>(s, args, grid, lds_bytes, stream)
+                   : !s.rec            ? launch_variant<PAR, SWP, 64, MODE_WGB, false, false>(s, args, grid, lds_bytes, stream)
+                   : s.linear_only     ? launch_kernel<PAR, SWP, 64, MODE_WGB, false, false, true, false, 2>(s, args, grid, lds_bytes, stream)
+                                       : launch_kernel<PAR, SWP, 64, MODE_WGB, false, false, false, false, 2>(s, args, grid, lds_bytes, stream);
         });
     }
     const bool staged = s.prog_in_lds;
     if (s.mode == MODE_PART)
-        return staged ? launch_variant<PAR, 64, MODE_PART, true, true>(s, args, grid, lds_bytes, stream)
-                      : launch_variant<PAR, 64, MODE_PART, true, false>(s, args, grid, lds_bytes, stream);
+        return staged ? launch_variant<PAR, SWP, 64, MODE_PART, true, true>(s, args, grid, lds_bytes, stream)
+                      : launch_variant<PAR, SWP, 64, MODE_PART, true, false>(s, args, grid, lds_bytes, stream);
     if (!s.rec)
-        return staged ? launch_variant<PAR, 64, MODE_WGB, true, true>(s, args, grid, lds_bytes, stream)
-                      : launch_variant<PAR, 64, MODE_WGB, true, false>(s, args, grid, lds_bytes, stream);
+        return staged ? launch_variant<PAR, SWP, 64, MODE_WGB, true, true>(s, args, grid, lds_bytes, stream)
+                      : launch_variant<PAR, SWP, 64, MODE_WGB, true, false>(s, args, grid, lds_bytes, stream);
     // one connected system, its linear solve as a record walk
     auto walk = [&] {
         if (s.linear_only)
-            return staged ? launch_kernel<PAR, 64, MODE_WGB, true, true, true, false, 1>(s, args, grid, lds_bytes, stream)
-                          : launch_kernel<PAR, 64, MODE_WGB, true, false, true, false, 1>(s, args, grid, lds_bytes, stream);
-        return staged ? launch_kernel<PAR, 64, MODE_WGB, true, true, false, false, 1>(s, args, grid, lds_bytes, stream)
-                      : launch_kernel<PAR, 64, MODE_WGB, true, false, false, false, 1>(s, args, grid, lds_bytes, stream);
+            return staged ? launch_kernel<PAR, SWP, 64, MODE_WGB, true, true, true, false, 1>(s, args, grid, lds_bytes, stream)
+                          : launch_kernel<PAR, SWP, 64, MODE_WGB, true, false, true, false, 1>(s, args, grid, lds_bytes, stream);
+        return staged ? launch_kernel<PAR, SWP, 64, MODE_WGB, true, true, false, false, 1>(s, args, grid, lds_bytes, stream)
+                      : launch_kernel<PAR, SWP, 64, MODE_WGB, true, false, false, false, 1>(s, args, grid, lds_bytes, stream);
     };
     if (!s.rec_jglobal) return walk();
     // the Jacobian's values of every workgroup in global memory: one array per system object, like the workspace

@@ -286,6 +286,17 @@ __device__ __forceinline__ double dense8_solve(const WS& ws, uint32_t o_d, uint3
     return bad;
 }
 
+// The next item of a team's walk through its launch: the next system of its stride -- or, in a sweep build (SWP), the next step
+// of the sweep it is on, and only behind the last step the next sweep.
+template <bool SWP>
+__device__ __forceinline__ void next_item(uint64_t& q, uint32_t& step, uint32_t steps, uint64_t stride) {
+    if constexpr (SWP) {
+        if (++step < steps) return;
+        step = 0;
+    }
+    q += stride;
+}
+
 template <int TEAM, int MODE, bool GRID = false>
 struct Team {
     int lane;     // lane inside the unit that walks a phase (team for SUB, wave for PART, workgroup for WGB)
@@ -455,7 +466,15 @@ struct ConRef<2, PROG> {
 // workgroup, whose wavefronts may be a system apart), else they are read where the caller left them -- and every sweep that
 // builds a constraint's DevCon puts the driven value into it.  A template flag, not a run-time branch: the other builds
 // stay instruction for instruction what they were, and the PAR builds compile in a translation unit of their own.
-template <int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool GRID = false, bool DENSE = false, int RECF = 0, bool PAR = false>
+// SWP: the build of ezpz_system_sweep_params (implies PAR; instantiated in sweep.hip only) -- `batch` sweeps of
+// SolveArgs::steps driven solves each, step k starting from step k - 1's answer.  The team that takes sweep q runs its steps back
+// to back as items of the same loop: row k * batch + q of params, x_out, status, the mask and the log is step k's, x is loaded
+// from x0 at step 0 only -- behind a step the workspace already holds the bits that were just stored to x_out -- and everything
+// else (the driven values, the warning counter, the LM state) starts afresh per item exactly as it does per system.  A
+// partitioned workgroup's wavefronts stay at most one ITEM apart (the rendezvous behind the load), so its two copies of the
+// driven values alternate by item, and a wavefront that is a step ahead has touched only its own partition's values.
+template <int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool GRID = false, bool DENSE = false, int RECF = 0, bool PAR = false,
+          bool SWP = false>
 __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1024 : 512), MODE == MODE_SUB ? (DENSE ? 2 : 4) : 1)
     lm_solve_kernel(const SolveArgs a) {
     // RECF: the record walk's form -- 0 none, 1 state in LDS (16-bit addresses), 2 state in global memory (32-bit addresses)
@@ -465,6 +484,7 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
     static_assert(!REC || (MODE == MODE_WGB && !GRID && !DENSE && (RECF == 1) == LDSWS), "the record walk is for one barrier workgroup");
     static_assert(!GRID || (MODE == MODE_PART && LDSWS && PLDS), "grid teams are partitioned teams with staged lists");
     static_assert(!PAR || !GRID, "driven parameters are served by one-workgroup teams");
+    static_assert(!SWP || PAR, "a sweep drives parameters");  // (and takes no list of systems, no resumed state, no resident requests: sweep.hip)
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using namespace dev;
     Team<TEAM, MODE, GRID> tm;
@@ -642,28 +662,36 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
     DoneWord done = a.done;
     do {
     x_have = false;
-    for (uint64_t q = (uint64_t)grid_slot * teams_per_block + team_in_block; q < n_sys; q += n_teams, sys_parity ^= 1u) {
-        const uint64_t sys = a.sys_list ? (uint64_t)a.sys_list[q] : q;
+    uint32_t step = 0;  // (sweep builds: the step of sweep q this item is)
+    for (uint64_t q = (uint64_t)grid_slot * teams_per_block + team_in_block; q < n_sys;
+         next_item<SWP>(q, step, a.steps, n_teams), sys_parity ^= 1u) {
+        // (the row of everything a solve reads or writes per system; a sweep's values start from row q of x0)
+        const uint64_t sys = SWP ? (uint64_t)step * a.batch + q : a.sys_list ? (uint64_t)a.sys_list[q] : q;
+        const uint64_t x_row = SWP ? q : sys;
+        const bool load_x = !SWP || step == 0;
         // ---- load the initial values (AoS row, coalesced) ------------------------------------------------------------
 #ifdef EZPZ_STAMPS
         int stamp_n = 0;
 #endif
         EZPZ_STAMP(1);
-        const bool resuming = a.resume != nullptr;
-        const double* x0 = (resuming ? a.x_out : a.x0) + sys * n_row;
+        const bool resuming = !SWP && a.resume != nullptr;
+        const double* x0 = (resuming ? a.x_out : a.x0) + x_row * n_row;
         if constexpr (MODE == MODE_PART) {
             // each wavefront loads (and later stores) its own partition's variables only: a wavefront that is already
             // on the next system never touches values another one has not stored yet.  The first four values per lane
             // were fetched while the previous system was being solved (the HBM round trip of this load was 5 % of a
             // 2000 x 2000 solve, on the critical path of whichever wavefront finished last).
             constexpr uint32_t XPRE = 4;
+            if (load_x) {
 #pragma unroll
             for (uint32_t j = 0; j < XPRE; ++j) {
                 const uint32_t ci = call0 + tm.lane + j * 64;
                 if (ci < call1) ws[o_x + ci] = x_have ? x_pre[j] : x0[x_id[j]];
             }
             for (uint32_t ci = call0 + tm.lane + XPRE * 64; ci < call1; ci += tm.stride) ws[o_x + ci] = x0[P.var_of[ci]];
-            x_have = q + n_teams < n_sys;
+            }
+            // (a sweep: the next item loads values only when it is step 0 of the team's next sweep)
+            x_have = (!SWP || step + 1 == a.steps) && q + n_teams < n_sys;
             if (x_have) {
                 // (a resumed system continues from the values the lanes kernel left in x_out, like the load above)
                 const double* x1 = (resuming ? a.x_out : a.x0) + (a.sys_list ? (uint64_t)a.sys_list[q + n_teams] : q + n_teams) * n_row;
@@ -673,7 +701,7 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
                     x_pre[j] = ci < call1 ? x1[x_id[j]] : 0.0;
                 }
             }
-        } else {
+        } else if (load_x) {
             for (uint32_t i = tlane; i < n; i += tsize) ws[o_x + i] = x0[P.var_of[i]];
         }
         if constexpr (PAR) {
@@ -681,7 +709,7 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
             par_vals = src;
             if (par_lds) {  // (uniform per launch: a scalar branch)
                 // (a partitioned workgroup's wavefronts may be one system apart -- never two: the rendezvous below -- so its
-                // systems alternate between two copies)
+                // systems alternate between two copies; a sweep's steps are items of the same loop and alternate like them)
                 double* dst = par_lds + (MODE == MODE_PART ? (size_t)sys_parity * a.n_param : 0);
                 for (uint32_t i = tlane; i < a.n_param; i += tsize) dst[i] = src[i];
                 par_vals = dst;

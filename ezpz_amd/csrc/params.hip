@@ -7,47 +7,12 @@
 // run-time compiled kernels -- lane, wavefront, block classes hold parameters as literals or stage them once per launch -- and
 // never the lanes across the batch or the fronts, whose programs carry the parameters in their records: a system that has been
 // specialised, or whose plain calls take those shapes, is still served from here.
+#include "driven_params.hpp"
 #include "list_walk_launch.hip.hpp"
 
 using namespace ezpz;
 
 namespace {
-
-// EZPZ_PARAMS_LDS=0: the teams read the driven values where the caller left them, whatever room their LDS has (A/B runs;
-// tests/test_gpu_params.py runs that form in a child process).  EZPZ_DEBUG=params: which form a launch took, on stderr.
-bool params_lds_enabled() {
-    static const bool on = [] {
-        const char* e = std::getenv("EZPZ_PARAMS_LDS");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// What a `positions` list becomes on the device -- the list-walk teams' side array (per constraint of the table: its place in the
-// list, or none) or the interpreter's overlay -- kept on the system for a caller that repeats its list.  (launch_mu is held.)
-int driven_slots(EzpzSystem& s, const uint32_t* positions, size_t n_param, const std::vector<uint32_t>& slot_of_pos, bool for_comp) {
-    EzpzSystem::DrivenParams& d = s.driven;
-    if (d.valid && d.for_comp == for_comp && d.positions.size() == n_param && std::equal(positions, positions + n_param, d.positions.begin()))
-        return EZPZ_OK;
-    d.valid = false;
-    std::vector<uint32_t> table;
-    if (for_comp) {
-        comp_param_overlay(*s.comp, slot_of_pos.data(), table);
-    } else {
-        table.resize(std::max<size_t>(s.host_con_pos.size(), 1), kNoParamSlot);
-        for (size_t ci = 0; ci < s.host_con_pos.size(); ++ci) table[ci] = slot_of_pos[s.host_con_pos[ci]];
-    }
-    // (the launches that read the previous list's table have to be through with it: each waited for the one before it, so the
-    // last one's completion is everybody's)
-    if (d.uploaded) HIP_TRY(hipEventSynchronize(d.uploaded));
-    int rc = d.slots.ensure(table.size());
-    if (rc != EZPZ_OK) return rc;
-    HIP_TRY(hipMemcpy(d.slots.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    d.positions.assign(positions, positions + n_param);
-    d.for_comp = for_comp;
-    d.valid = true;
-    return EZPZ_OK;
-}
 
 int launch_params(EzpzSystem& s, SolveArgs& a, bool for_comp, hipStream_t stream) {
     if (for_comp) {
@@ -57,17 +22,11 @@ int launch_params(EzpzSystem& s, SolveArgs& a, bool for_comp, hipStream_t stream
         L.n_param = a.n_param;
         return comp_launch(*s.comp, s.dev_comp, L, s.device, s.lim.cus, s.lim.lds_bytes, stream);
     }
-    // The teams' copies of their system's values: one per team of a workgroup of sub-wavefront teams, two for a wavefront-
-    // partitioned workgroup (its wavefronts may be a system apart), one for a barrier workgroup -- behind everything else in
-    // the LDS, when that costs the CU no workgroup it would otherwise hold; else the values stay where the caller left them
-    const size_t copies = s.mode == MODE_SUB ? s.block_threads / s.team_size : s.mode == MODE_PART ? 2 : 1;
-    const size_t base = (s.lds_bytes + 15) & ~size_t(15), with = base + copies * (size_t)a.n_param * sizeof(double);
-    auto per_cu = [&](size_t bytes) {
-        const size_t cap = s.mode == MODE_SUB ? 4 : 8;  // (what the kernels' registers and launch_list_walk's grid ask of a CU at most)
-        return std::min<size_t>(cap, s.lim.lds_bytes / std::max<size_t>(bytes, 1));
-    };
-    const bool in_lds = params_lds_enabled() && with <= s.lim.lds_bytes && per_cu(with) == per_cu(s.lds_bytes);
-    a.par_lds_off = in_lds ? (uint32_t)(base / 8) : 0u;
+    const ParLds L = par_lds_plan(s, a.n_param);  // (driven_params.hpp)
+    const size_t copies = L.copies;
+    const bool in_lds = L.in_lds;
+    const size_t with = L.bytes;
+    a.par_lds_off = L.off;
     static const bool say = debug_topic("params");
     if (say)
         std::fprintf(stderr, "[ezpz params] %u values per system %s (team mode %d, %zu copies, LDS %zu -> %zu of %zu bytes)\n", a.n_param,
@@ -90,13 +49,8 @@ int ezpz_system_solve_batch_params_device(EzpzSystem* sys, const double* x0_dev,
     if (!positions || !params_dev || n_param > 0xFFFFFFFEull) return EZPZ_ERR_INVALID_ARGUMENT;
     if (batch && (!x_out_dev || !status_dev)) return EZPZ_ERR_INVALID_ARGUMENT;
     if (batch && sys->counts.n_vars && !x0_dev) return EZPZ_ERR_INVALID_ARGUMENT;
-    const size_t n_cs = sys->host_has_param.size();
-    std::vector<uint32_t> slot_of_pos(std::max<size_t>(n_cs, 1), kNoParamSlot);
-    for (size_t j = 0; j < n_param; ++j) {
-        const uint32_t pos = positions[j];
-        if (pos >= n_cs || slot_of_pos[pos] != kNoParamSlot || !sys->host_has_param[pos]) return EZPZ_ERR_INVALID_ARGUMENT;
-        slot_of_pos[pos] = (uint32_t)j;
-    }
+    std::vector<uint32_t> slot_of_pos;
+    if (int rc = driven_slot_map(*sys, positions, n_param, slot_of_pos)) return rc;
     const bool for_comp = sys->comp && sys->comp->interpretable;
     if (!for_comp) {
         if (int rc = ensure_program(sys)) return rc;

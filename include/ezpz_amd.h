@@ -329,6 +329,53 @@ int ezpz_system_solve_batch_params(EzpzSystem* sys, const double* x0, const uint
                                    const double* params, size_t batch, const EzpzConfig* cfg, double* x_out, EzpzStatus* status,
                                    uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
 
+/* ---- dimension sweeps: a chain of driven solves per system in one launch -------------------------------------
+ * `batch` sweeps of `steps` solves each on one topology: step k of sweep b takes params[k][b][:] for the constraints at
+ * `positions` and starts from step k - 1's answer; step 0 starts from x0[b] -- a dragged point, a swept length, an animated linkage
+ * staying on its solution branch.  Every per-step array is STEP-MAJOR:
+ *     params[steps][batch][n_param]   x_out[steps][batch][n_vars]   status[steps][batch]
+ *     unsat_mask[steps][batch][n_cs]  warn_log[steps][batch][warn_cap]            x0[batch][n_vars]
+ * so that step k of the whole batch is one contiguous batch in the layout of ezpz_system_solve_batch_params, and the sweep is BY
+ * DEFINITION this chain of calls of that entry:
+ *     step 0:  solve_batch_params(x0,           params[0]) -> x_out[0], status[0], unsat_mask[0], warn_log[0]
+ *     step k:  solve_batch_params(x_out[k - 1], params[k]) -> x_out[k], status[k], unsat_mask[k], warn_log[k]
+ * System b at step k gets the values, EzpzStatus, mask and warning log that chain gives, bit for bit, on every route the params
+ * entry has.  A step that does not converge changes nothing about the chain: the next step starts from whatever it left (holding
+ * the last good answer is the caller's business).  steps == 1 is the params entry, same bits.  steps == 0 or batch == 0: EZPZ_OK,
+ * nothing written.  n_param == 0 is legal: `steps` re-solves with the system's own values, each from the one before (the plain
+ * entry's, as a chain of launches).
+ * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: the argument errors of the params entry (a position
+ * >= n_cs, listed twice, or whose constraint has no parameter; positions or params NULL with n_param > 0; x_out, status or x0 NULL
+ * with work to do) -- and a system that one solve spreads over several workgroups (EzpzSystemInfo.grid_workgroups > 1 of its
+ * list-walk shape), which this entry declines like the params entry.  Sweeps through ezpz_multi_* and ezpz_mixed_* do not exist.
+ * Aliasing: x0 may be exactly x_out (step 0's block), as with the plain entry; any other overlap among the arrays is the caller's
+ * error, and the result then undefined.
+ * The _device form only enqueues on `stream` -- one launch where the plan says in_kernel, else the chain of `steps` launches --
+ * with the params entry's exception: a `positions` list other than the system's last one (of this entry or the params entry, they
+ * share the table) is turned into its device table first.  Sweeps and params calls on one EzpzSystem run one behind the other
+ * whatever their streams.  The host form stages through the system's buffers, sized steps x batch.
+ * ezpz_system_sweep_params_plan (host only): the route a sweep of this list takes and whether it is one launch.  DIAGNOSTIC, like
+ * EzpzSensitivityPlan: it follows the kernels and is not part of the stable surface. */
+#define EZPZ_SWEEP_INTERPRETER 0u           /* block system: the component interpreter */
+#define EZPZ_SWEEP_SUB_WAVEFRONT_TEAMS 1u   /* list-walk teams of 1 .. 64 lanes */
+#define EZPZ_SWEEP_PARTITIONED_WORKGROUP 2u /* one workgroup per sweep, a partition per wavefront */
+#define EZPZ_SWEEP_BARRIER_WORKGROUP 3u     /* one workgroup per sweep on one partition (workspace in LDS or global memory) */
+#define EZPZ_SWEEP_RECORD_WALK 4u           /* ... whose linear solve is a record walk */
+typedef struct EzpzSweepPlan {
+    uint32_t route;         /* EZPZ_SWEEP_* */
+    uint32_t in_kernel;     /* 1: one launch, the values never leave the team's workspace; 0: the chain of `steps` launches */
+    uint32_t params_in_lds; /* list-walk routes: a team stages its step's driven values in LDS */
+    uint32_t lds_bytes;     /* dynamic LDS per workgroup of the launch */
+} EzpzSweepPlan;
+int ezpz_system_sweep_params_plan(EzpzSystem* sys, const uint32_t* positions, size_t n_param, EzpzSweepPlan* out);
+int ezpz_system_sweep_params_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                    const double* params_dev, size_t steps, size_t batch, const EzpzConfig* cfg, double* x_out_dev,
+                                    EzpzStatus* status_dev, uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap,
+                                    void* stream);
+int ezpz_system_sweep_params(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const double* params,
+                             size_t steps, size_t batch, const EzpzConfig* cfg, double* x_out, EzpzStatus* status,
+                             uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
+
 /* ---- dimension sensitivities: dx/d(param) of a batch, on the device ------------------------------------------
  * For system b the caller passes values x_b (normally a solve's answer) and a parameter row p_b.  r(x, p) is the weighted
  * residual vector in the reference's row order with p overlaid exactly as ezpz_system_solve_batch_params overlays it,
