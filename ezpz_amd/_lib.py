@@ -69,6 +69,10 @@ class CSweepPlan(C.Structure):
 
 
 SWEEP_ROUTES = ("interpreter", "sub-wavefront teams", "partitioned workgroup", "barrier workgroup", "record walk")  # EZPZ_SWEEP_*
+SWEEP_FRONTS = len(SWEEP_ROUTES)  # EZPZ_SWEEP_FRONTS: the route a caller opts into (ezpz_system_set_params_route), behind the entry's own
+SWEEP_ROUTE_NAMES = SWEEP_ROUTES + ("fronts",)
+PARAMS_ROUTE_DEFAULT, PARAMS_ROUTE_FRONTS = 0, 1  # EZPZ_PARAMS_ROUTE_*
+PARAMS_ROUTES = {"default": PARAMS_ROUTE_DEFAULT, "fronts": PARAMS_ROUTE_FRONTS}
 
 
 class CViewport(C.Structure):
@@ -103,6 +107,7 @@ EXPORTS = [
     "ezpz_constraint_param_derivative", "ezpz_system_param_sensitivity_plan", "ezpz_system_param_sensitivity_device",
     "ezpz_system_param_sensitivity",
     "ezpz_system_sweep_params_plan", "ezpz_system_sweep_params_device", "ezpz_system_sweep_params",
+    "ezpz_system_set_params_route",
 ]
 
 _lib = None
@@ -229,6 +234,8 @@ def lib():
     L.ezpz_system_param_sensitivity_device.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp, vp]
     L.ezpz_system_param_sensitivity.restype = C.c_int
     L.ezpz_system_param_sensitivity.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp]
+    L.ezpz_system_set_params_route.restype = C.c_int
+    L.ezpz_system_set_params_route.argtypes = [vp, u32]
     L.ezpz_system_sweep_params_plan.restype = C.c_int
     L.ezpz_system_sweep_params_plan.argtypes = [vp, vp, sz, C.POINTER(CSweepPlan)]
     L.ezpz_system_sweep_params_device.restype = C.c_int

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import SWEEP_ROUTES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -784,6 +784,16 @@ class System:
             raise ValueError("positions: a 1-D sequence of constraint positions (non-negative integers)")
         return np.ascontiguousarray(p, dtype=np.uint32)
 
+    def set_params_route(self, route: str) -> None:
+        """`ezpz_system_set_params_route`: "fronts" makes solve_batch_params, sweep_params (and torch_ops.solve_params) of this
+        system run on the frontal shape -- only a system whose frontal plan serves every call (info()["front_max_batch"] ==
+        0xFFFFFFFF) accepts it; "default" restores the entry's own route."""
+        if route not in PARAMS_ROUTES:
+            raise ValueError(f"route: one of {sorted(PARAMS_ROUTES)}, got {route!r}")
+        rc = lib().ezpz_system_set_params_route(self._h, PARAMS_ROUTES[route])
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
     def solve_batch_params(self, x0: np.ndarray, positions, params: np.ndarray, config: Optional[Config] = None,
                            want_mask: bool = False):
         """`ezpz_system_solve_batch_params`: one topology, a dimension set per system.  params [batch, len(positions)] replaces
@@ -874,7 +884,7 @@ class System:
         if rc != 0:
             raise NonLinearSystemError(rc)
         out = {f: getattr(p, f) for f, _ in CSweepPlan._fields_}
-        out["route_name"] = SWEEP_ROUTES[p.route]
+        out["route_name"] = SWEEP_ROUTE_NAMES[p.route]
         return out
 
     def param_sensitivity(self, x: np.ndarray, positions, params: Optional[np.ndarray] = None, lam: Optional[float] = None,

@@ -17,13 +17,20 @@ inline bool params_lds_enabled() {
 
 // What a `positions` list becomes on the device -- the list-walk teams' side array (per constraint of the table: its place in the
 // list, or none) or the interpreter's overlay -- kept on the system for a caller that repeats its list.  (launch_mu is held.)
-inline int driven_slots(EzpzSystem& s, const uint32_t* positions, size_t n_param, const std::vector<uint32_t>& slot_of_pos, bool for_comp) {
+inline bool driven_slots_cached(const EzpzSystem& s, const uint32_t* positions, size_t n_param, bool for_comp, uint32_t route) {
+    const EzpzSystem::DrivenParams& d = s.driven;
+    return d.valid && d.for_comp == for_comp && d.route == route && d.positions.size() == n_param &&
+           std::equal(positions, positions + n_param, d.positions.begin());
+}
+inline int driven_slots(EzpzSystem& s, const uint32_t* positions, size_t n_param, const std::vector<uint32_t>& slot_of_pos, bool for_comp,
+                        uint32_t route = EZPZ_PARAMS_ROUTE_DEFAULT) {
     EzpzSystem::DrivenParams& d = s.driven;
-    if (d.valid && d.for_comp == for_comp && d.positions.size() == n_param && std::equal(positions, positions + n_param, d.positions.begin()))
-        return EZPZ_OK;
+    if (driven_slots_cached(s, positions, n_param, for_comp, route)) return EZPZ_OK;
     d.valid = false;
     std::vector<uint32_t> table;
-    if (for_comp) {
+    if (route == EZPZ_PARAMS_ROUTE_FRONTS) {
+        table = slot_of_pos;  // (the fronts' records carry the caller's position: the map itself)
+    } else if (for_comp) {
         comp_param_overlay(*s.comp, slot_of_pos.data(), table);
     } else {
         table.resize(std::max<size_t>(s.host_con_pos.size(), 1), kNoParamSlot);
@@ -37,6 +44,7 @@ inline int driven_slots(EzpzSystem& s, const uint32_t* positions, size_t n_param
     HIP_TRY(hipMemcpy(d.slots.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     d.positions.assign(positions, positions + n_param);
     d.for_comp = for_comp;
+    d.route = route;
     d.valid = true;
     return EZPZ_OK;
 }
@@ -71,5 +79,17 @@ inline ParLds par_lds_plan(const EzpzSystem& s, size_t n_param) {
     const bool in_lds = params_lds_enabled() && with <= s.lim.lds_bytes && per_cu(with) == per_cu(s.lds_bytes);
     return {in_lds, copies, in_lds ? with : s.lds_bytes, in_lds ? (uint32_t)(base / 8) : 0u};
 }
+
+// ---- the fronts as the route of both entries (front_params.hip; ezpz_system_set_params_route) ---------------------------------
+// A workgroup's copy of its system's driven values: behind everything else in the LDS when that costs the CU no workgroup of the
+// build (the occupancy the launch itself asks the runtime for), else -- and with EZPZ_PARAMS_LDS=0 -- the rows are read through L2.
+struct FrontParLds {
+    bool in_lds;
+    uint32_t bytes;  // the launch's dynamic LDS
+    uint32_t off;    // FrontArgs::par_lds_off
+};
+int front_params_lds_plan(EzpzSystem& s, size_t n_param, bool sweep, FrontParLds& out);  // (launch_mu is held, the device current)
+// The launch: a.params / par_slot / n_param set; sweep: a.steps solves per sweep in one launch (the SWP build).
+int front_params_launch(EzpzSystem& s, SolveArgs& a, bool sweep, hipStream_t stream);
 
 }  // namespace ezpz

@@ -470,8 +470,38 @@ struct Red {
 // measured twice and not kept: with a barrier per level of the tree, one solve of 300 variables 191 -> 193 us, 800: 2.09 -> 2.30 ms;
 // with the wavefronts' schedules 50 / 150 / 300 / 500 / 800 / 2000 / 5000 / 10 000 variables 84 -> 107, 96 -> 114, 179 -> 171, 347 ->
 // 413, 1844 -> 2038, 451 -> 509, 2659 -> 2703, 919 -> 798 us)
-template <bool LIN>
-__global__ void __launch_bounds__(512, 1) front_solve_kernel(const FrontArgs a) {
+// PAR: the build of ezpz_system_solve_batch_params on the fronts (ezpz_system_set_params_route; front_params.hip) --
+// every system brings its own values for the constraint parameters the call drives (FrontParArgs::params, n_param doubles per system;
+// par_slot: per CALLER position, the value's place among them or kNoParamSlot -- DevCon::pos is the caller's position, so every
+// workgroup of a system reads the same table).  A workgroup copies its system's row into LDS beside the gather of x (par_lds_off;
+// coalesced, ordered by the barrier behind the gather) or reads it where the caller left it, and the two sweeps that evaluate
+// constraints put the driven value into their copy of the record; the table itself -- possibly the staged one -- is never written.
+// SWP: the build of ezpz_system_sweep_params (implies PAR) -- `batch` sweeps of `steps` solves; the slot that takes sweep q runs
+// its steps back to back as items of the same loop: row k * batch + q of params, x_out, status, mask and log is step k's, x is
+// gathered from x0 at step 0 only (behind a step the workspace holds the bits just stored to x_out, ghosts included: every
+// workgroup applies the same steps to the same bits), everything else starts afresh per item as it does per system.
+// Template flags, not run-time branches, and an argument block of their own (FrontParArgs): the two builds of front.hip stay
+// instruction for instruction what they were.
+// A constraint's record with its driven parameter, if it has one (the residual and the Jacobian sweep).
+template <bool PAR, class ARGS>
+__device__ __forceinline__ DevCon front_load_con(const DevCon* p, const ARGS& a, const double* lds, const double* par_glob) {
+    DevCon c = load_con(p);
+    if constexpr (PAR) {
+        const uint32_t ps = a.par_slot[c.pos];
+        // (an index from the LDS's base, not a pointer that is either an LDS or a global one: that would be a generic pointer)
+        if (ps != kNoParamSlot) {
+            if (a.par_lds_off)
+                c.param = lds[a.par_lds_off + ps];
+            else
+                c.param = par_glob[ps];
+        }
+    }
+    return c;
+}
+
+template <bool LIN, bool PAR = false, bool SWP = false>
+__global__ void __launch_bounds__(512, 1) front_solve_kernel(const typename FrontArgsOf<PAR>::type a) {
+    static_assert(!SWP || PAR, "a sweep drives parameters");
     using namespace frontal;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -548,7 +578,19 @@ __global__ void __launch_bounds__(512, 1) front_solve_kernel(const FrontArgs a) 
     const bool probing = a.probe_m != 0;
     const uint16_t* const slotmap = reinterpret_cast<const uint16_t*>(a.plan + W.o_slotmap);
     uint32_t sys_parity = 0;
-    for (uint64_t sys = slot; sys < a.batch; sys += n_slots, sys_parity ^= 1u) {
+    // (PAR: the workgroup's copy of its system's driven values lies behind everything else in the LDS, at FrontParArgs::par_lds_off)
+    // (SWP: the slot's items are the steps of its sweeps slot, slot + n_slots, ... one sweep behind the other, counted like systems)
+    uint64_t items_end = 0;
+    if constexpr (SWP) items_end = slot < a.batch ? slot + (a.batch - slot + n_slots - 1) / n_slots * a.steps * n_slots : 0;
+    for (uint64_t item = slot; item < (SWP ? items_end : a.batch); item += n_slots, sys_parity ^= 1u) {
+        uint64_t sys = item, swp = item;  // the item's row, and the sweep it belongs to
+        uint32_t step = 0;
+        if constexpr (SWP) {
+            const uint64_t j = (item - slot) / n_slots;
+            swp = slot + j / a.steps * n_slots;
+            step = (uint32_t)(j % a.steps);
+            sys = (uint64_t)step * a.batch + swp;
+        }
 #ifdef EZPZ_STAMPS
         int stamp_n = 0;
         cx.stamps = a.stamps;
@@ -557,8 +599,16 @@ __global__ void __launch_bounds__(512, 1) front_solve_kernel(const FrontArgs a) 
         FRONT_STAMP(1);
         // (probes: a work item is ONE probe of one system -- item = system x probe_m + probe -- so that a system's probes run side by
         // side on as many workgroups)
-        const double* const x0 = a.x0 + (probing ? sys / a.probe_m : sys) * a.n_vars;
-        for (uint32_t i = tid; i < n_loc; i += blockDim.x) xs[i] = x0[var_glob[i]];
+        const double* const x0 = a.x0 + (SWP ? swp : probing ? sys / a.probe_m : sys) * a.n_vars;
+        if (!SWP || step == 0)
+            for (uint32_t i = tid; i < n_loc; i += blockDim.x) xs[i] = x0[var_glob[i]];
+        const double* par_glob = nullptr;
+        if constexpr (PAR) {
+            par_glob = a.params + sys * a.n_param;
+            // (the previous item's readers are behind its last barrier; this item's are behind the next one)
+            if (a.par_lds_off)
+                for (uint32_t i = tid; i < a.n_param; i += blockDim.x) smem[a.par_lds_off + i] = par_glob[i];
+        }
         int* const nwarn = G > 1 ? &head->nwarn[sys_parity] : &ints[0];
         if (tid == 0 && G == 1) ints[0] = 0;
         __syncthreads();
@@ -727,7 +777,7 @@ __global__ void __launch_bounds__(512, 1) front_solve_kernel(const FrontArgs a) 
             const uint32_t l_dst = (mode == EVAL0) ? l_r : l_rn;
             double sq = 0.0, mx = __builtin_nan("");
             for (uint32_t ci = tid; ci < n_cons; ci += blockDim.x) {
-                const DevCon c = load_con(cons + ci);
+                const DevCon c = front_load_con<PAR>(cons + ci, a, smem, par_glob);
                 double r0, r1;
                 const bool deg = con_residual<LIN>(c, (const double*)xs, r0, r1);
                 if (mode == FINAL) {
@@ -782,7 +832,7 @@ __global__ void __launch_bounds__(512, 1) front_solve_kernel(const FrontArgs a) 
                 }
                 if constexpr (!LIN) {
                     for (uint32_t ci = tid; ci < n_cons; ci += blockDim.x) {
-                        const DevCon c = load_con(cons + ci);
+                        const DevCon c = front_load_con<PAR>(cons + ci, a, smem, par_glob);
                         JacWriter<double*> w;
                         w.jv = jvp;
                         w.jbase = c.jbase;

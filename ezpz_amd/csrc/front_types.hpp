@@ -157,5 +157,23 @@ struct FrontArgs {
     unsigned long long* stamps;  // diagnostic builds
     DoneWord done;
 };
+// The argument block of the PAR and SWP builds (front_params.hip): FrontArgs, then the driven parameters.  A type of its own and
+// not more fields of FrontArgs: a longer block moves the arguments the runtime appends behind it, and with them the code of the
+// builds that never read these fields.  params[row * n_param + slot] replaces the parameter of every constraint whose caller
+// position p has par_slot[p] == slot; par_lds_off: where a workgroup keeps its system's values in LDS (doubles from the start; 0:
+// they are read from `params`); steps: SWP builds -- `batch` sweeps of `steps` solves each, row = step * batch + sweep.
+struct FrontParArgs : FrontArgs {
+    const double* params;
+    const uint32_t* par_slot;
+    uint32_t n_param, par_lds_off, steps, pad;
+};
+template <bool PAR>
+struct FrontArgsOf {
+    typedef FrontArgs type;
+};
+template <>
+struct FrontArgsOf<true> {
+    typedef FrontParArgs type;
+};
 
 }  // namespace ezpz

@@ -12,15 +12,6 @@ namespace {
 std::mutex g_grid_mu;
 hipEvent_t g_grid_event[16] = {};  // per device: completion of the last launch of this process whose workgroups wait for each other
 
-bool stream_capturing(hipStream_t stream) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
-        (void)hipGetLastError();
-        capturing = hipStreamCaptureStatusNone;
-    }
-    return capturing != hipStreamCaptureStatusNone;
-}
-
 }  // namespace
 namespace ezpz {
 thread_local uint64_t t_call_batch = 0;

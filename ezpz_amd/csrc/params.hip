@@ -5,8 +5,9 @@
 // (comp_kernel.hip.hpp, the PAR builds: a per-call overlay beside the chunks' parameter tables), else the list-walk teams on
 // one workgroup per system or less (lm_kernel.hip.hpp, the PAR builds: instantiated here, beside launch.hip's).  Never the
 // run-time compiled kernels -- lane, wavefront, block classes hold parameters as literals or stage them once per launch -- and
-// never the lanes across the batch or the fronts, whose programs carry the parameters in their records: a system that has been
-// specialised, or whose plain calls take those shapes, is still served from here.
+// never the lanes across the batch, whose programs carry the parameters in their records: a system that has been
+// specialised, or whose plain calls take those shapes, is still served from here.  The fronts serve it where the caller asked
+// for them (ezpz_system_set_params_route; front_params.hip): an overlay by caller position beside their records.
 #include "driven_params.hpp"
 #include "list_walk_launch.hip.hpp"
 
@@ -15,6 +16,7 @@ using namespace ezpz;
 namespace {
 
 int launch_params(EzpzSystem& s, SolveArgs& a, bool for_comp, hipStream_t stream) {
+    if (s.params_route == EZPZ_PARAMS_ROUTE_FRONTS) return front_params_launch(s, a, false, stream);
     if (for_comp) {
         CompLaunch L = comp_launch_args(a);
         L.params = a.params;
@@ -52,7 +54,16 @@ int ezpz_system_solve_batch_params_device(EzpzSystem* sys, const double* x0_dev,
     std::vector<uint32_t> slot_of_pos;
     if (int rc = driven_slot_map(*sys, positions, n_param, slot_of_pos)) return rc;
     const bool for_comp = sys->comp && sys->comp->interpretable;
-    if (!for_comp) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (the route is read again under the lock: a setter that runs between the two turns this call into an argument error)
+    const uint32_t route = [&] {
+        std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
+        return sys->params_route;
+    }();
+    if (route == EZPZ_PARAMS_ROUTE_FRONTS) {
+        // fronts on several workgroups allocate their scratch on first use and chain their launches on an event: never inside a capture
+        if (sys->fronts->n_wgs > 1 && stream_capturing(st)) return EZPZ_ERR_INVALID_ARGUMENT;
+    } else if (!for_comp) {
         if (int rc = ensure_program(sys)) return rc;
         // one system on several workgroups: declined (the workgroups' sub-programs would each need their slice of the side array)
         if (sys->mode != MODE_SUB && sys->grid_wgs > 1) return EZPZ_ERR_INVALID_ARGUMENT;
@@ -60,9 +71,9 @@ int ezpz_system_solve_batch_params_device(EzpzSystem* sys, const double* x0_dev,
     if (batch == 0) return EZPZ_OK;
     release_thread_kernel(sys->device);
     EZPZ_ON_DEVICE(sys->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
-    if (int rc = driven_slots(*sys, positions, n_param, slot_of_pos, for_comp)) return rc;
+    if (sys->params_route != route) return EZPZ_ERR_INVALID_ARGUMENT;
+    if (int rc = driven_slots(*sys, positions, n_param, slot_of_pos, for_comp, route)) return rc;
     SolveArgs a = solve_args_for(sys, x0_dev, batch, cfg, x_out_dev, status_dev, unsat_mask_dev, warn_log_dev, warn_cap);
     a.params = params_dev;
     a.par_slot = sys->driven.slots.p;
@@ -105,6 +116,9 @@ int ezpz_system_solve_batch_params(EzpzSystem* sys, const double* x0, const uint
     if (rc != EZPZ_OK || batch == 0) return rc;
     HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
     HIP_TRY(hipMemcpy(status, sys->st_dev.p, batch * sizeof(EzpzStatus), hipMemcpyDeviceToHost));
+    if (sys->params_route == EZPZ_PARAMS_ROUTE_FRONTS && sys->fronts->n_wgs > 1)  // (like every host entry of such a system: system.hpp)
+        for (size_t b = 0; b < batch; ++b)
+            if (status[b].iterations == EZPZ_ITERATIONS_TEAM_TIMEOUT) return EZPZ_ERR_HIP;
     if (n) HIP_TRY(hipMemcpy(x_out, sys->x_dev.p, batch * n * sizeof(double), hipMemcpyDeviceToHost));
     if (unsat_mask && C) HIP_TRY(hipMemcpy(unsat_mask, sys->mask_dev.p, batch * C, hipMemcpyDeviceToHost));
     if (want_log) {

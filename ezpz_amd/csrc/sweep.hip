@@ -6,7 +6,8 @@
 // and every layout is step-major so that the chain can be issued literally -- which is what a route with in_kernel == 0 does.
 // The routes are the params entry's (params.hip): the component interpreter for a block system, else the list-walk teams on one
 // workgroup per system or less; in one launch they run the SWP builds of those kernels, instantiated here and nowhere else,
-// whose teams keep a sweep's values in their workspace from one step to the next.
+// whose teams keep a sweep's values in their workspace from one step to the next.  A system whose params route is the fronts
+// (ezpz_system_set_params_route) sweeps on them: the SWP build of front_solve_kernel, instantiated in front_params.hip.
 #include "call_trace.hpp"
 #include "comp_launch.hip.hpp"
 #include "driven_params.hpp"
@@ -18,9 +19,15 @@ namespace {
 
 // Which routes run a sweep in one launch.  profiles/sweep_rate.txt decides (tools/sweep_rate.py): a route whose one sweep of
 // 240 steps is not faster in one launch than as the chain of launches, beyond the spread of the measurement, is listed here and
-// stays on the chain (one bit per EZPZ_SWEEP_* route).  As measured, none is.
+// stays on the chain (one bit per EZPZ_SWEEP_* route).  As measured, none is.  The fronts are measured apart for systems on one
+// workgroup and on several (profiles/front_params_rate.txt, tools/front_params_rate.py), by the same rule: 1.01 to 1.02 x, beyond
+// the spread in every case, so neither goes on the chain.
 constexpr uint32_t kRoutesOnTheChain = 0;
-bool route_in_kernel(uint32_t route) { return !(kRoutesOnTheChain >> route & 1u); }
+constexpr bool kFrontsOneWgOnTheChain = false, kFrontsSeveralWgsOnTheChain = false;
+bool route_in_kernel(const EzpzSystem& s, uint32_t route) {
+    if (route == EZPZ_SWEEP_FRONTS) return !(s.fronts->n_wgs > 1 ? kFrontsSeveralWgsOnTheChain : kFrontsOneWgOnTheChain);
+    return !(kRoutesOnTheChain >> route & 1u);
+}
 
 // (the program exists: ensure_program has run for a list-walk route)
 uint32_t route_of(const EzpzSystem& s, bool for_comp) {
@@ -33,13 +40,21 @@ uint32_t route_of(const EzpzSystem& s, bool for_comp) {
 // What the device form, the host form and the plan check alike before anything else happens: the list, and the route it takes.
 struct Request {
     std::vector<uint32_t> slot_of_pos;
-    bool for_comp = false;
+    bool for_comp = false, fronts = false;
     uint32_t route = 0;
 };
 int check_request(EzpzSystem* sys, const uint32_t* positions, size_t n_param, Request& r) {
     if (n_param && (!positions || n_param > 0xFFFFFFFEull)) return EZPZ_ERR_INVALID_ARGUMENT;
     if (int rc = driven_slot_map(*sys, positions, n_param, r.slot_of_pos)) return rc;
     r.for_comp = sys->comp && sys->comp->interpretable;
+    {
+        std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
+        r.fronts = sys->params_route == EZPZ_PARAMS_ROUTE_FRONTS;
+    }
+    if (r.fronts) {
+        r.route = EZPZ_SWEEP_FRONTS;
+        return EZPZ_OK;
+    }
     if (!r.for_comp) {
         if (int rc = ensure_program(sys)) return rc;
         // one system on several workgroups: declined, like the params entry declines it
@@ -59,8 +74,18 @@ int ezpz_system_sweep_params_plan(EzpzSystem* sys, const uint32_t* positions, si
     if (int rc = check_request(sys, positions, n_param, r)) return rc;
     EzpzSweepPlan p{};
     p.route = r.route;
-    p.in_kernel = n_param && route_in_kernel(r.route) ? 1u : 0u;
-    if (r.for_comp) {
+    p.in_kernel = n_param && route_in_kernel(*sys, r.route) ? 1u : 0u;
+    if (r.fronts) {
+        p.lds_bytes = (uint32_t)sys->fronts->lds_bytes;
+        if (n_param) {  // (the occupancy of the build: the one question of this entry that the device answers)
+            EZPZ_ON_DEVICE(sys->device);
+            std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
+            FrontParLds L;
+            if (int rc = front_params_lds_plan(*sys, n_param, p.in_kernel != 0, L)) return rc;
+            p.params_in_lds = L.in_lds ? 1u : 0u;
+            p.lds_bytes = L.bytes;
+        }
+    } else if (r.for_comp) {
         p.lds_bytes = sys->comp->lds_bytes;
     } else {
         const ParLds L = par_lds_plan(*sys, n_param);
@@ -85,7 +110,7 @@ int ezpz_system_sweep_params_device(EzpzSystem* sys, const double* x0_dev, const
     if (int rc = check_request(sys, positions, n_param, r)) return rc;
     if (!work) return EZPZ_OK;
     const size_t n = sys->counts.n_vars, C = sys->counts.n_cons;
-    if (n_param == 0 || !route_in_kernel(r.route)) {
+    if (n_param == 0 || !route_in_kernel(*sys, r.route)) {
         // the chain itself, enqueued on the stream: step k's block of every array is a batch in the params entry's layout
         // (n_param == 0: the plain entry's re-solves with the system's own values, on whatever route it takes)
         for (size_t k = 0; k < steps; ++k) {
@@ -101,13 +126,16 @@ int ezpz_system_sweep_params_device(EzpzSystem* sys, const double* x0_dev, const
     release_thread_kernel(sys->device);
     EZPZ_ON_DEVICE(sys->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // (fronts on several workgroups: never inside a capture, like the params entry)
+    if (r.fronts && sys->fronts->n_wgs > 1 && stream_capturing(st)) return EZPZ_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
+    const uint32_t proute = r.fronts ? EZPZ_PARAMS_ROUTE_FRONTS : EZPZ_PARAMS_ROUTE_DEFAULT;
+    if (sys->params_route != proute) return EZPZ_ERR_INVALID_ARGUMENT;  // (a setter ran between the check and the lock)
     // (the params entry's table, lock and event: sweeps and params calls on one system run one behind the other, and a list
     // that either of them used last uploads nothing)
     EzpzSystem::DrivenParams& d = sys->driven;
-    const bool repeated = d.valid && d.for_comp == r.for_comp && d.positions.size() == n_param &&
-                          std::equal(positions, positions + n_param, d.positions.begin());
-    if (int rc = driven_slots(*sys, positions, n_param, r.slot_of_pos, r.for_comp)) return rc;
+    const bool repeated = driven_slots_cached(*sys, positions, n_param, r.for_comp, proute);
+    if (int rc = driven_slots(*sys, positions, n_param, r.slot_of_pos, r.for_comp, proute)) return rc;
     if (!repeated) call_stamp(SWEEP_TABLE_UPLOADED);
     SolveArgs a = solve_args_for(sys, x0_dev, batch, cfg, x_out_dev, status_dev, unsat_mask_dev, warn_log_dev, warn_cap);
     a.params = params_dev;
@@ -118,7 +146,9 @@ int ezpz_system_sweep_params_device(EzpzSystem* sys, const double* x0_dev, const
     if (a.sys_list || a.sys_count || a.resume || a.done.flag || a.done.request) return EZPZ_ERR_INVALID_ARGUMENT;
     HIP_TRY(d.uploaded ? hipStreamWaitEvent(st, d.uploaded, 0) : hipEventCreateWithFlags(&d.uploaded, hipEventDisableTiming));
     int rc;
-    if (r.for_comp) {
+    if (r.fronts) {
+        rc = front_params_launch(*sys, a, true, st);
+    } else if (r.for_comp) {
         CompArgs ca = comp_args_for(*sys->comp, sys->dev_comp, comp_launch_args(a));
         ca.params = a.params;
         ca.par_overlay = a.par_slot;
@@ -170,6 +200,9 @@ int ezpz_system_sweep_params(EzpzSystem* sys, const double* x0, const uint32_t* 
     HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
     const size_t all = steps * batch;
     HIP_TRY(hipMemcpy(status, sys->st_dev.p, all * sizeof(EzpzStatus), hipMemcpyDeviceToHost));
+    if (sys->params_route == EZPZ_PARAMS_ROUTE_FRONTS && sys->fronts->n_wgs > 1)  // (like every host entry of such a system: system.hpp)
+        for (size_t b = 0; b < all; ++b)
+            if (status[b].iterations == EZPZ_ITERATIONS_TEAM_TIMEOUT) return EZPZ_ERR_HIP;
     if (n) HIP_TRY(hipMemcpy(x_out, sys->x_dev.p, all * n * sizeof(double), hipMemcpyDeviceToHost));
     if (unsat_mask && C) HIP_TRY(hipMemcpy(unsat_mask, sys->mask_dev.p, all * C, hipMemcpyDeviceToHost));
     if (want_log) {

@@ -234,6 +234,16 @@ struct EzpzSystem {
     DevBuf<unsigned char> front_scratch;
     uint64_t front_capacity = 0;
     uint64_t front_max_batch = 0;  // calls of up to this many systems take the fronts (~0: every call; shape.cpp)
+    // ezpz_system_set_params_route: the params entry and the sweeps of this system take the fronts (front_params.hip; under launch_mu),
+    // and what their PAR / SWP builds found out on first use: the workgroups of the build the device holds, and for the last
+    // call's number of driven values whether a workgroup's copy of them fits the LDS without costing the CU a workgroup
+    uint32_t params_route = 0;
+    struct FrontPar {
+        uint64_t capacity = 0;
+        int per_cu = 0;
+        uint32_t n_param = 0xFFFFFFFFu;
+        bool in_lds = false;
+    } front_par[2];  // [SWP]
     uint32_t grid_wgs = 1;     // grid team: workgroups that share one system (each keeps its share of the state in LDS)
     uint32_t grid_ws_doubles = 0;
     DevBuf<GridScratch> grid_scratch;
@@ -306,6 +316,7 @@ struct EzpzSystem {
     struct DrivenParams {
         std::vector<uint32_t> positions;
         bool valid = false, for_comp = false;
+        uint32_t route = 0;  // EZPZ_PARAMS_ROUTE_* the table was made for (the fronts read it by caller position)
         DevBuf<uint32_t> slots;
         hipEvent_t uploaded = nullptr;  // the last launch that read `slots`: a new list overwrites them behind it
         ~DrivenParams() {
@@ -444,6 +455,14 @@ extern thread_local uint64_t t_call_batch;
 // the sequence budget.  (The caller refuses stream capture before it allocates anything: it would leave the chaining event unusable.)
 int launch_resident(int device, hipStream_t stream, void* scratch, size_t scratch_bytes, uint64_t& seq_used, uint64_t batch,
                     uint64_t exchanges_per_system, const std::function<int()>& launch);
+inline bool stream_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(stream, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        capturing = hipStreamCaptureStatusNone;
+    }
+    return capturing != hipStreamCaptureStatusNone;
+}
 int front_launch(EzpzSystem& s, SolveArgs& args, hipStream_t stream);
 int front_launch_probe(EzpzSystem& s, const double* x_dev, size_t batch, double* y_dev, uint32_t m, hipStream_t stream,
                        const double* w_dev = nullptr, double lambda_scale = 1e-11);  // front.hip  // front.hip: the frontal shape (EzpzSystem::fronts)

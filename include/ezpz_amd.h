@@ -315,11 +315,24 @@ int ezpz_system_solve_batch(EzpzSystem* sys, const double* x0, size_t batch, con
  * position whose constraint has no parameter, n_param > 0 with positions or params NULL -- and a system that one solve spreads
  * over several workgroups (EzpzSystemInfo.grid_workgroups > 1 of its list-walk shape), which this entry declines.
  * The entry has its own route: the component interpreter for block systems, else the list-walk teams; never the run-time
- * compiled kernels (a specialised system is served all the same), the lanes across the batch or the fronts.
+ * compiled kernels (a specialised system is served all the same) or the lanes across the batch -- and the fronts only where
+ * the caller asks for them:
+ * ezpz_system_set_params_route(sys, EZPZ_PARAMS_ROUTE_FRONTS) makes this entry and the sweeps below run on the FRONTAL shape
+ * (team_mode 5) of a system whose frontal plan serves every call (EzpzSystemInfo.front_max_batch == 0xFFFFFFFF: created with
+ * EZPZ_TEAM_FRONTS, or with EZPZ_TEAM_AUTO_LATENCY where the planner took the fronts); every other system -- a system created
+ * for batches that takes the fronts for its small calls included -- gets EZPZ_ERR_INVALID_ARGUMENT and keeps its route.  On
+ * that route system b gets exactly, bit for bit, what ezpz_system_solve_batch gives on a system created with the same team_size
+ * from `cs` with those parameters substituted (values, EzpzStatus, mask, warning log), on one workgroup per system or several:
+ * the decline of grid_workgroups > 1 above is the list-walk route's alone.  A launch on several workgroups refuses a stream that
+ * is being captured (EZPZ_ERR_INVALID_ARGUMENT, nothing enqueued), as the plain entry does.  EZPZ_PARAMS_ROUTE_DEFAULT restores
+ * the route described above; it is what every system starts with.  The setter waits for the system's launches of both entries.
  * Thread safety and the aliasing of x0 / x_out: as for ezpz_system_solve_batch_device; launches of this entry on one
  * EzpzSystem run one behind the other whatever streams they were enqueued on.  The _device form only enqueues on
  * `stream`, except that a `positions` list other than the system's last one is turned into its device table first: the call then
  * waits for the system's earlier launches of this entry and copies synchronously (repeat the list, and calls only enqueue). */
+#define EZPZ_PARAMS_ROUTE_DEFAULT 0u
+#define EZPZ_PARAMS_ROUTE_FRONTS 1u
+int ezpz_system_set_params_route(EzpzSystem* sys, uint32_t route);
 int ezpz_constraint_has_param(const EzpzConstraint* c);
 int ezpz_system_solve_batch_params_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
                                           const double* params_dev, size_t batch, const EzpzConfig* cfg, double* x_out_dev,
@@ -347,7 +360,8 @@ int ezpz_system_solve_batch_params(EzpzSystem* sys, const double* x0, const uint
  * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: the argument errors of the params entry (a position
  * >= n_cs, listed twice, or whose constraint has no parameter; positions or params NULL with n_param > 0; x_out, status or x0 NULL
  * with work to do) -- and a system that one solve spreads over several workgroups (EzpzSystemInfo.grid_workgroups > 1 of its
- * list-walk shape), which this entry declines like the params entry.  Sweeps through ezpz_multi_* and ezpz_mixed_* do not exist.
+ * list-walk shape), which this entry declines like the params entry unless the system's params route is the fronts
+ * (ezpz_system_set_params_route: the sweep is then bit for bit the chain of params calls on that route).  Sweeps through ezpz_multi_* and ezpz_mixed_* do not exist.
  * Aliasing: x0 may be exactly x_out (step 0's block), as with the plain entry; any other overlap among the arrays is the caller's
  * error, and the result then undefined.
  * The _device form only enqueues on `stream` -- one launch where the plan says in_kernel, else the chain of `steps` launches --
@@ -361,10 +375,13 @@ int ezpz_system_solve_batch_params(EzpzSystem* sys, const double* x0, const uint
 #define EZPZ_SWEEP_PARTITIONED_WORKGROUP 2u /* one workgroup per sweep, a partition per wavefront */
 #define EZPZ_SWEEP_BARRIER_WORKGROUP 3u     /* one workgroup per sweep on one partition (workspace in LDS or global memory) */
 #define EZPZ_SWEEP_RECORD_WALK 4u           /* ... whose linear solve is a record walk */
+/* ... the five routes the entry chooses among by itself; and the one a caller opts into (ezpz_system_set_params_route): the
+ * frontal shape, a sweep per slot of its workgroups -- route 5 */
+#define EZPZ_SWEEP_FRONTS (EZPZ_SWEEP_RECORD_WALK + 1u)
 typedef struct EzpzSweepPlan {
     uint32_t route;         /* EZPZ_SWEEP_* */
     uint32_t in_kernel;     /* 1: one launch, the values never leave the team's workspace; 0: the chain of `steps` launches */
-    uint32_t params_in_lds; /* list-walk routes: a team stages its step's driven values in LDS */
+    uint32_t params_in_lds; /* list-walk routes and the fronts: a team stages its step's driven values in LDS */
     uint32_t lds_bytes;     /* dynamic LDS per workgroup of the launch */
 } EzpzSweepPlan;
 int ezpz_system_sweep_params_plan(EzpzSystem* sys, const uint32_t* positions, size_t n_param, EzpzSweepPlan* out);
