@@ -61,7 +61,9 @@ class CLaunchPolicy(C.Structure):
 class CSensitivityPlan(C.Structure):
     _fields_ = [("n_components", C.c_uint32), ("n_active", C.c_uint32), ("n_small", C.c_uint32), ("n_lds", C.c_uint32),
                 ("n_workspace", C.c_uint32), ("max_component_vars", C.c_uint32), ("max_envelope", C.c_uint32),
-                ("lds_bytes", C.c_uint32), ("workspace_bytes", C.c_uint64)]
+                ("lds_bytes", C.c_uint32), ("workspace_bytes", C.c_uint64),
+                ("route", C.c_uint32), ("front_workgroups", C.c_uint32), ("rhs_per_item", C.c_uint32),
+                ("items_per_system", C.c_uint32), ("front_lds_bytes", C.c_uint32)]
 
 
 class CSweepPlan(C.Structure):
@@ -73,6 +75,8 @@ SWEEP_FRONTS = len(SWEEP_ROUTES)  # EZPZ_SWEEP_FRONTS: the route a caller opts i
 SWEEP_ROUTE_NAMES = SWEEP_ROUTES + ("fronts",)
 PARAMS_ROUTE_DEFAULT, PARAMS_ROUTE_FRONTS = 0, 1  # EZPZ_PARAMS_ROUTE_*
 PARAMS_ROUTES = {"default": PARAMS_ROUTE_DEFAULT, "fronts": PARAMS_ROUTE_FRONTS}
+SENSITIVITY_ROUTE_DEFAULT, SENSITIVITY_ROUTE_FRONTS = 0, 1  # EZPZ_SENSITIVITY_ROUTE_*
+SENSITIVITY_ROUTES = {"default": SENSITIVITY_ROUTE_DEFAULT, "fronts": SENSITIVITY_ROUTE_FRONTS}
 
 
 class CViewport(C.Structure):
@@ -108,6 +112,7 @@ EXPORTS = [
     "ezpz_system_param_sensitivity",
     "ezpz_system_sweep_params_plan", "ezpz_system_sweep_params_device", "ezpz_system_sweep_params",
     "ezpz_system_set_params_route",
+    "ezpz_system_set_sensitivity_route", "ezpz_debug_front_sens_tables",
 ]
 
 _lib = None
@@ -236,6 +241,10 @@ def lib():
     L.ezpz_system_param_sensitivity.argtypes = [vp, vp, vp, sz, vp, sz, C.c_double, vp, vp, vp]
     L.ezpz_system_set_params_route.restype = C.c_int
     L.ezpz_system_set_params_route.argtypes = [vp, u32]
+    L.ezpz_system_set_sensitivity_route.restype = C.c_int
+    L.ezpz_system_set_sensitivity_route.argtypes = [vp, u32]
+    L.ezpz_debug_front_sens_tables.restype = C.c_long
+    L.ezpz_debug_front_sens_tables.argtypes = [vp, sz, sz, u32, u32, C.c_uint64, vp, sz, vp, sz, vp]
     L.ezpz_system_sweep_params_plan.restype = C.c_int
     L.ezpz_system_sweep_params_plan.argtypes = [vp, vp, sz, C.POINTER(CSweepPlan)]
     L.ezpz_system_sweep_params_device.restype = C.c_int

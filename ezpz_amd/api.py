@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -887,12 +887,23 @@ class System:
         out["route_name"] = SWEEP_ROUTE_NAMES[p.route]
         return out
 
+    def set_sensitivity_route(self, route: str) -> None:
+        """`ezpz_system_set_sensitivity_route`: "fronts" makes param_sensitivity, its device form (and the backward of
+        torch_ops.solve_params) of this system run on the frontal plan -- one factorisation for many right-hand sides, no limit on
+        the size of a component; only a system whose frontal plan serves every call accepts it; "default" restores the entry's
+        own route.  The params route (set_params_route) is a setting of its own."""
+        if route not in SENSITIVITY_ROUTES:
+            raise ValueError(f"route: one of {sorted(SENSITIVITY_ROUTES)}, got {route!r}")
+        rc = lib().ezpz_system_set_sensitivity_route(self._h, SENSITIVITY_ROUTES[route])
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
     def param_sensitivity(self, x: np.ndarray, positions, params: Optional[np.ndarray] = None, lam: Optional[float] = None,
                           want_degenerate: bool = False):
         """`ezpz_system_param_sensitivity`: S[b, j, :] = -(JtJ + lam I)^-1 Jt dr/dp_j at the values x [batch, n_vars] (normally a
         solve's answer) with params [batch, len(positions)] overlaid as solve_batch_params overlays them (None: the system's own
         values); per unit of the `param` field.  lam defaults to Config().initial_lambda.  Returns (S [batch, k, n_vars], status
-        [batch] uint32: 1 where the factorisation failed and S[b] is NaN) -- and the degenerate counts with want_degenerate."""
+        [batch] uint32: 1 where the factorisation failed and S[b] is NaN; on the fronts route also 2: a wait between workgroups ran out) -- and the degenerate counts with want_degenerate."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, max(self.n_vars, 1))
         batch = x.shape[0]
         pos = self._positions(positions)

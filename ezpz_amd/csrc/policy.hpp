@@ -30,6 +30,11 @@ inline bool debug_topic(const char* topic) {
 }
 
 
+// Dimension sensitivities on the fronts (front_sens.hip): a system's listed constraints are cut into chunks that run side by
+// side, and every chunk repeats the factorisation -- never fewer right-hand sides per chunk than this.  (One factorisation is some
+// K / 2 times the work of one right-hand side's two substitutions on a front of K pivots; not yet measured on a device: DESIGN.md 3g.)
+constexpr uint32_t kFrontSensMinRhsPerItem = 8;
+
 inline EzpzLaunchPolicy launch_policy_for(int compute_units) {
     const uint64_t cus = (uint64_t)std::max(compute_units, 1);
     EzpzLaunchPolicy p{};

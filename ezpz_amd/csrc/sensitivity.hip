@@ -390,6 +390,14 @@ int ezpz_system_param_sensitivity_plan(EzpzSystem* sys, const uint32_t* position
     if (!sys || !out) return EZPZ_ERR_INVALID_ARGUMENT;
     std::vector<uint32_t> slot_of_pos;
     if (int rc = check_positions(sys, positions, n_param, slot_of_pos)) return rc;
+    {
+        // the fronts as this entry's route (ezpz_system_set_sensitivity_route; front_sens.hip): no component limit there
+        std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
+        if (sys->sens_route == EZPZ_SENSITIVITY_ROUTE_FRONTS) {
+            EZPZ_ON_DEVICE(sys->device);
+            return front_sens_plan_info(*sys, n_param, *out);
+        }
+    }
     SensPlan P;
     std::vector<SensComp> comps;
     std::vector<SensRec> recs;
@@ -411,6 +419,17 @@ int ezpz_system_param_sensitivity_device(EzpzSystem* sys, const double* x_dev, c
     EZPZ_ON_DEVICE(sys->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
+    if (sys->sens_route == EZPZ_SENSITIVITY_ROUTE_FRONTS) {
+        // (fronts on several workgroups allocate their scratch on first use and chain their launches on an event: never inside a capture)
+        if (sys->fronts->n_wgs > 1 && stream_capturing(st)) return EZPZ_ERR_INVALID_ARGUMENT;
+        if (batch == 0) return EZPZ_OK;
+        if (n_param == 0) {
+            HIP_TRY(hipMemsetAsync(status_dev, 0, batch * sizeof(uint32_t), st));
+            return EZPZ_OK;
+        }
+        return front_sens_launch(*sys, x_dev, positions, n_param, slot_of_pos, params_dev, batch, lambda, S_out_dev, status_dev,
+                                 degenerate_count_dev, st);
+    }
     SensPlan* plan = nullptr;
     if (n_param)
         if (int rc = plan_for(sys, positions, n_param, slot_of_pos, plan)) return rc;

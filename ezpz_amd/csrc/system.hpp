@@ -313,6 +313,10 @@ struct EzpzSystem {
     // `positions` list with its device tables and workspace (built on first use; touched under launch_mu)
     std::vector<EzpzConstraint> host_cs;
     std::shared_ptr<void> sens;
+    // ezpz_system_set_sensitivity_route: the sensitivity entries of this system run on the frontal plan (front_sens.hip, DESIGN.md
+    // 3g; under launch_mu), and that route's plan of the last call's `positions` list: its tables on the device beside the plan
+    uint32_t sens_route = 0;
+    std::shared_ptr<void> front_sens;
     struct DrivenParams {
         std::vector<uint32_t> positions;
         bool valid = false, for_comp = false;
@@ -475,6 +479,12 @@ int lane_indexed_launch(EzpzSystem* sys, const double* x_ragged, const uint64_t*
 void launch_copy_out(void* dst_host_as_device, const void* src_dev, size_t bytes, void* stream);  // a copy kernel into mapped host memory
 
 // ---- api.hip ----------------------------------------------------------------------------------------------------------------
+// The sensitivity entries on the fronts (front_sens.hip; ezpz_system_set_sensitivity_route): launch_mu is held, the system's device
+// current, the request checked (slot_of_pos: caller position -> place in the list), batch and n_param not zero.
+int front_sens_launch(EzpzSystem& s, const double* x_dev, const uint32_t* positions, size_t n_param, const std::vector<uint32_t>& slot_of_pos,
+                      const double* params_dev, size_t batch, double lambda, double* S_dev, uint32_t* status_dev, uint32_t* deg_dev,
+                      hipStream_t st);
+int front_sens_plan_info(EzpzSystem& s, size_t n_param, EzpzSensitivityPlan& out);
 int ensure_program(EzpzSystem* sys);  // the rest of a deferred analysis (EzpzSystem::program_deferred)
 // ezpz_system_eval_batch for a caller that holds sys->mu already (launch.hip; FreedomAnalysis by probes checks its null vectors
 // against the Jacobian)

@@ -414,7 +414,7 @@ int ezpz_system_sweep_params(EzpzSystem* sys, const double* x0, const uint32_t* 
  * else is written.
  * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: the argument errors of the params entries (a position
  * >= n_cs, listed twice, or whose constraint has no parameter; positions NULL with n_param > 0; x, S_out or status_out NULL with
- * batch > 0) -- and a listed constraint in a component of more than EZPZ_SENSITIVITY_MAX_COMPONENT_VARS variables, or in a
+ * batch > 0) -- and, on the default route (ezpz_system_set_sensitivity_route below lifts it), a listed constraint in a component of more than EZPZ_SENSITIVITY_MAX_COMPONENT_VARS variables, or in a
  * component of the workspace shape with so many listed constraints that x, two doubles per listed constraint and 12 bytes per
  * variable exceed 64 KB of LDS (some 2800 listed constraints in a component of 1024 variables).
  * The _device form takes device pointers and only enqueues on `stream`: no host synchronisation and no allocation, except
@@ -434,7 +434,31 @@ typedef struct EzpzSensitivityPlan {
     uint32_t max_envelope;       /* entries of the largest factor (row envelope, diagonal included) */
     uint32_t lds_bytes;          /* per workgroup of the LDS shape */
     uint64_t workspace_bytes;    /* per resident workgroup of the workspace shape */
+    /* ... and with ezpz_system_set_sensitivity_route(sys, EZPZ_SENSITIVITY_ROUTE_FRONTS) (the fields above but n_components are 0 then): */
+    uint32_t route;              /* EZPZ_SENSITIVITY_ROUTE_* the call takes */
+    uint32_t front_workgroups;   /* workgroups per system of the frontal plan */
+    uint32_t rhs_per_item;       /* right-hand sides per work item = per factorisation (for a call of one system) */
+    uint32_t items_per_system;   /* work items a system's list is cut into (for a call of one system) */
+    uint32_t front_lds_bytes;    /* dynamic LDS of the launch */
 } EzpzSensitivityPlan;
+/* The fronts as the route of the sensitivity entries: ezpz_system_set_sensitivity_route(sys, EZPZ_SENSITIVITY_ROUTE_FRONTS) makes
+ * ezpz_system_param_sensitivity and its _device form run on the FRONTAL plan of a system whose plan serves every call (the
+ * condition of ezpz_system_set_params_route: EzpzSystemInfo.front_max_batch == 0xFFFFFFFF); every other system, a NULL system and
+ * an unknown route get EZPZ_ERR_INVALID_ARGUMENT and keep their route.  It is a setter of its own: the params route is not
+ * touched, and with it unset every call is bit for bit what it was.  On that route
+ *   - every listed constraint is served whatever the size of its component (no EZPZ_SENSITIVITY_MAX_COMPONENT_VARS): one
+ *     factorisation of JtJ + lambda I on the fronts serves many right-hand sides, the listed constraints of a system are cut into
+ *     work items that run side by side (EzpzSensitivityPlan.rhs_per_item; EZPZ_SENS_FRONTS_RHS_PER_ITEM=<n> overrides it);
+ *   - S, params, lambda, degenerate_count_out and the argument errors are those described above; S[b, j, :] does not depend on
+ *     the rest of the list, its order, the work items or the batch (bit for bit); an entry that is exactly zero is +0.0;
+ *   - status[b] = 1 (a pivot was not positive) as above, and status[b] = 2 with S[b] all NaN: a wait between the workgroups of
+ *     a system ran out (grid_workgroups > 1 on a device that does not hold them all at once) -- never a hang;
+ *   - a system on several workgroups refuses a stream that is being captured (EZPZ_ERR_INVALID_ARGUMENT, nothing enqueued).
+ * The results are those of a valid Cholesky factorisation in the fronts' elimination order: at the bar of the numpy reference
+ * (tests/sensitivity_ref.py), not bitwise those of the default route.  The setter waits for the system's launches on the route. */
+#define EZPZ_SENSITIVITY_ROUTE_DEFAULT 0u
+#define EZPZ_SENSITIVITY_ROUTE_FRONTS 1u
+int ezpz_system_set_sensitivity_route(EzpzSystem* sys, uint32_t route);
 int ezpz_constraint_param_derivative(const EzpzConstraint* c, const double* x, double g_out[2], int* degenerate);
 int ezpz_system_param_sensitivity_plan(EzpzSystem* sys, const uint32_t* positions, size_t n_param, EzpzSensitivityPlan* out);
 int ezpz_system_param_sensitivity_device(EzpzSystem* sys, const double* x_dev, const uint32_t* positions, size_t n_param,
@@ -648,6 +672,13 @@ unsigned long long ezpz_debug_jit_compilations(void);
  * shape does not apply to the system, or a negative EZPZ_ERR_*.  tests/front_ref.py executes the blob in numpy. */
 long ezpz_debug_front_plan(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, uint32_t wgs, uint32_t max_wgs,
                            uint64_t lds_bytes, unsigned char* buf, size_t cap, uint64_t* info);
+/* Diagnostic (host only): the tables the sensitivity route of the fronts derives from that plan for a `positions` list
+ * (csrc/front_sens_types.hpp: the rhs-only assembly streams, the rhs-only extend-add of every front, the home of each listed
+ * constraint), as 32-bit words; info[0..3] = workgroups, words, the plan blob's bytes, 0.  Returns the tables' size in bytes, 0
+ * when the shape does not apply, or a negative EZPZ_ERR_*.  tests/front_sens_ref.py executes them in numpy. */
+long ezpz_debug_front_sens_tables(const EzpzConstraint* cs, size_t n_cs, size_t n_vars, uint32_t wgs, uint32_t max_wgs,
+                                  uint64_t lds_bytes, const uint32_t* positions, size_t n_param, unsigned char* buf, size_t cap,
+                                  uint64_t* info);
 
 /* ---- textual front end, ezpz/src/textual.rs:43-49 (Problem: FromStr) + executor.rs:40-445 ------------ */
 typedef struct EzpzProblem EzpzProblem; /* opaque: parsed + lowered problem text */

@@ -1,0 +1,112 @@
+"""Dimension sensitivities on the FRONTAL shape, what a machine without a GPU can check: the surface of
+ezpz_system_set_sensitivity_route; the host tables of csrc/front_sens_plan.cpp -- the rhs-only assembly streams, the rhs-only
+extend-add, the homes of the listed constraints -- executed in numpy (tests/front_sens_ref.py) against the dense
+-(JtJ + lam I)^-1 Jt g_j of tests/sensitivity_ref.py; and the condition on the inputs of tests/test_gpu_front_sens.py: the
+reference's own spread on every system that file uses."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import front_sens_ref as FS
+import sensitivity_ref as R
+from sensitivity import BAR_CEILING
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_surface():
+    import ezpz_amd as E
+    from ezpz_amd import _lib
+
+    header = open(os.path.join(ROOT, "include", "ezpz_amd.h")).read()
+    assert re.search(r"#define\s+EZPZ_SENSITIVITY_ROUTE_DEFAULT\s+0u", header)
+    assert re.search(r"#define\s+EZPZ_SENSITIVITY_ROUTE_FRONTS\s+1u", header)
+    assert re.search(r"int\s+ezpz_system_set_sensitivity_route\(EzpzSystem\*\s*sys,\s*uint32_t\s+route\);", header)
+    assert "ezpz_system_set_sensitivity_route" in _lib.EXPORTS and "ezpz_debug_front_sens_tables" in _lib.EXPORTS
+    L = E.lib()
+    assert L.ezpz_system_set_sensitivity_route(None, 1) == -103
+    assert L.ezpz_system_set_sensitivity_route(None, 0) == -103
+    assert callable(E.System.set_sensitivity_route)
+    assert _lib.SENSITIVITY_ROUTES == {"default": 0, "fronts": 1}
+    fields = [f for f, _ in _lib.CSensitivityPlan._fields_]
+    assert fields[-5:] == ["route", "front_workgroups", "rhs_per_item", "items_per_system", "front_lds_bytes"]
+    assert C.sizeof(_lib.CSensitivityPlan) == 64
+
+
+def _half_permuted(pos):
+    return np.random.default_rng(4).permutation(pos)[: max(1, len(pos) // 2)]
+
+
+@pytest.mark.parametrize("wgs", [1, 2, 4])
+@pytest.mark.parametrize("name", ["sketch25", "sketch75", "band", "hub"])
+def test_tables_executed_in_numpy(name, wgs):
+    """Factorisation with a zero right-hand side, then per listed position the rhs-only pass through the tables: S against the
+    dense solve from the oracle's rows, at the bar the reference's own spread grants; the full list and a permuted half list give
+    the same rows bit for bit (a row does not depend on the rest of the list)."""
+    s = FS.system(name)
+    b = 0
+    recs = R.substituted(s["recs"], s["pos"], s["params"][b])
+    Sref, spread = FS.references(name)[b]
+    S, bad = FS.executed(recs, s["n_vars"], wgs, s["pos"], s["x"][b], s["lam"])
+    assert not bad
+    scale = np.maximum(1.0, np.abs(Sref).max(axis=1))[:, None]
+    err = float((np.abs(S - Sref) / scale).max())
+    print(name, wgs, "error", err, "bar", R.bar(spread))
+    assert err <= R.bar(spread), (name, wgs, err, R.bar(spread))
+    half = _half_permuted(s["pos"])
+    Sh, bad = FS.executed(recs, s["n_vars"], wgs, half, s["x"][b], s["lam"])
+    assert not bad
+    where = {int(p): j for j, p in enumerate(s["pos"])}
+    assert np.array_equal(Sh, S[[where[int(p)] for p in half]])
+
+
+def test_tables_hold_rhs_entries_only():
+    """Every entry of the rhs-only assembly stream is a FASM_RHS entry of the plan's assembly stream, each exactly once."""
+    import front_ref as F
+
+    s = FS.system("sketch75")
+    for wgs in (1, 3):
+        plan = F.Plan(s["recs"], s["n_vars"], wgs)
+        T = FS.Tables(s["recs"], s["n_vars"], wgs, s["pos"])
+        for g in range(plan.n_wgs):
+            W = plan.wgs[g]
+            t_end = int(W["t_cons"]) if int(W["t_cons"]) != 0xFFFFFFFF else int(W["tab_bytes"])
+            stream = plan.arr("<u4", int(W["o_tables"]) + int(W["t_stream"]), (t_end - int(W["t_stream"])) // 4)
+            want = []
+            for tr in range(int(W["asm_trips"])):
+                base = int(stream[int(W["asm_word0"]) + tr])
+                wdt = int(stream[base]) >> 24
+                for l in range(64):
+                    hdr = int(stream[base + l])
+                    if hdr & F.FASM_RHS and not hdr & F.FASM_NOP:
+                        want.append((hdr, tuple(int(stream[base + 64 * (1 + q) + l]) for q in range(wdt))))
+            w_asm_offs, asm_trips, _, _ = T.wg(g)
+            got = []
+            for tr in range(asm_trips):
+                base = int(T.w[w_asm_offs + tr])
+                wdt = int(T.w[base]) >> 24
+                for l in range(64):
+                    hdr = int(T.w[base + l])
+                    if not hdr & F.FASM_NOP:
+                        got.append((hdr, tuple(int(T.w[base + 64 * (1 + q) + l]) for q in range(wdt))))
+            assert sorted(got) == sorted(want) and len(want) > 0
+
+
+@pytest.mark.parametrize("name", ["sketch25", "sketch75", "sketch150", "band", "hub"])
+def test_reference_spread_on_the_gpu_inputs(name):
+    """The numpy reference's Cholesky-against-lstsq spread on the systems tests/test_gpu_front_sens.py checks: at most 5e-6, so no
+    granted bar exceeds BAR_CEILING.  (Measured, 2 systems each: sketch25 1.4e-12, sketch75 2.9e-10, sketch150 8.7e-8, band 3.9e-9,
+    hub 6.1e-8, sketch600 5.6e-8 -- it depends on the linear algebra library in its last digits, so the numbers are not asserted.)"""
+    for b, (_, spread) in enumerate(FS.references(name)):
+        print(name, b, "spread", spread)
+        assert spread <= 5e-6 and R.bar(spread) <= BAR_CEILING
+
+
+def test_reference_spread_above_the_limit():
+    """sketch600 with its 16 listed positions (1200 variables in one component)."""
+    for b, (_, spread) in enumerate(FS.references("sketch600", 2, FS.sixteen)):
+        print("sketch600", b, "spread", spread)
+        assert spread <= 5e-6 and R.bar(spread) <= BAR_CEILING

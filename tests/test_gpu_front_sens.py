@@ -1,0 +1,352 @@
+"""Dimension sensitivities on the FRONTAL shape (ezpz_system_set_sensitivity_route; csrc/front_sens.hip, front_sens_kernel: one
+factorisation on the fronts, many right-hand sides): against the numpy reference of tests/sensitivity_ref.py at
+its own rule max(1e-10, 20 x spread) -- tests/test_front_sens_cpu.py measures the spreads of exactly these systems --, above the
+1024-variable limit of the default route, bit for bit however the rows are asked for, failures that stay local, exact zeros,
+their meaning (finite differences of two solves), the device form, autograd above the limit, and the setter."""
+import contextlib
+import os
+import warnings
+
+import numpy as np
+import pytest
+
+import front_sens_ref as FS
+import sensitivity_ref as R
+from oracle import oracle as O
+from test_gpu_front_params import env, front_system
+
+pytestmark = pytest.mark.gpu
+
+ERR_INVALID_ARGUMENT = -103
+_LOG_STARTED = False
+
+
+@pytest.fixture(scope="module")
+def E():
+    import ezpz_amd
+
+    if ezpz_amd.device_count() < 1:
+        pytest.fail("GPU tests need a HIP device: the product path has no CPU fallback")
+    return ezpz_amd
+
+
+def _log(line):
+    """sensitivity_ref.log's rule, into $EZPZ_PROFILE_DIR/front_sens_bar.txt."""
+    global _LOG_STARTED
+    out = os.environ.get("EZPZ_PROFILE_DIR")
+    if out and os.path.isdir(out):
+        with open(os.path.join(out, "front_sens_bar.txt"), "a" if _LOG_STARTED else "w") as f:
+            f.write(line + "\n")
+        _LOG_STARTED = True
+
+
+@contextlib.contextmanager
+def logging_here():
+    """sensitivity_ref.assert_matches logs through sensitivity_ref.log: into this file's profile while the block runs."""
+    old, R.log = R.log, _log
+    try:
+        yield
+    finally:
+        R.log = old
+
+
+_SYSTEMS = {}
+
+
+def _system(E, name, wgs, route="fronts"):
+    """A system on the fronts with `wgs` workgroups (0: what the planner gives), the sensitivity route set."""
+    key = (name, wgs, route)
+    if key not in _SYSTEMS:
+        recs, g = FS.inputs(name)
+        if wgs:
+            s = front_system(E, recs, len(g), wgs, route=None)
+        else:
+            s = E.System(recs, len(g), team_size=E.TEAM_FRONTS)
+            assert s.info()["team_mode"] == 5 and s.info()["front_max_batch"] == 0xFFFFFFFF, s.info()
+        if route:
+            s.set_sensitivity_route(route)
+        _SYSTEMS[key] = s
+    return _SYSTEMS[key]
+
+
+@contextlib.contextmanager
+def rhs_per_item(n):
+    with env(EZPZ_SENS_FRONTS_RHS_PER_ITEM=n):
+        yield
+
+
+# ---- 1. against the numpy reference -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2), ("sketch150", 3), ("band", 1), ("band", 4), ("hub", 1), ("hub", 4)])
+def test_against_the_numpy_reference(E, name, wgs):
+    """If a system exceeded the rule, the default route's error on it (the parent's code, an independent implementation) would be
+    measured and 4 x that granted instead: it has not been needed -- the errors are logged beside the bars."""
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    plan = sysobj.param_sensitivity_plan(s["pos"])
+    print(name, wgs, plan)
+    assert plan["route"] == 1 and plan["front_workgroups"] == wgs and plan["rhs_per_item"] * plan["items_per_system"] >= len(s["pos"])
+    S, st, deg = sysobj.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"], want_degenerate=True)
+    assert S.shape == (len(s["x"]), len(s["pos"]), s["n_vars"]) and not st.any()
+    with logging_here():
+        for b, (Sref, spread) in enumerate(FS.references(name)):
+            assert deg[b] == R.degenerate_count(s["recs"], s["x"][b], s["pos"], s["params"][b]), (name, b)
+            R.assert_matches(S[b], Sref, spread, f"fronts, {name} on {wgs} workgroup(s) [{b}]")
+
+
+# ---- 2. above the limit ---------------------------------------------------------------------------------------------------------------
+def test_above_the_limit(E):
+    """sketch600: 1200 variables in one component.  The default route declines and touches nothing; the fronts serve it."""
+    s = FS.system("sketch600", 2, FS.sixteen)
+    sysobj = _system(E, "sketch600", 0, route=None)
+    n, k = s["n_vars"], len(s["pos"])
+    assert n == 1200 and k == 16
+    x, p = np.ascontiguousarray(s["x"]), np.ascontiguousarray(s["params"])
+    S = np.full((2, k, n), 7.0)
+    st, deg = np.full(2, 9, np.uint32), np.full(2, 5, np.uint32)
+    call = lambda: E.lib().ezpz_system_param_sensitivity(sysobj._h, x.ctypes.data, s["pos"].ctypes.data, k, p.ctypes.data, 2, s["lam"],
+                                                         S.ctypes.data, st.ctypes.data, deg.ctypes.data)
+    assert call() == ERR_INVALID_ARGUMENT and np.all(S == 7.0) and np.all(st == 9) and np.all(deg == 5)
+    sysobj.set_sensitivity_route("fronts")
+    try:
+        plan = sysobj.param_sensitivity_plan(s["pos"])
+        print("sketch600", plan, "grid_workgroups", sysobj.info()["grid_workgroups"])
+        assert plan["route"] == 1 and plan["front_workgroups"] == sysobj.info()["grid_workgroups"]
+        assert call() == 0 and not st.any()
+        with logging_here():
+            for b, (Sref, spread) in enumerate(FS.references("sketch600", 2, FS.sixteen)):
+                assert deg[b] == R.degenerate_count(s["recs"], s["x"][b], s["pos"], s["params"][b])
+                R.assert_matches(S[b], Sref, spread, f"fronts, sketch600 on {plan['front_workgroups']} workgroup(s) [{b}]")
+    finally:
+        sysobj.set_sensitivity_route("default")
+
+
+# ---- 3. the same bits, however asked ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,wgs", [("sketch75", 2), ("hub", 1)])
+def test_the_same_bits_however_asked(E, name, wgs):
+    """Parameters are the system's own values (None), so that a shorter list leaves the constraints it drops at the same values."""
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    pos, x = s["pos"], s["x"]
+    k = len(pos)
+    full, st = sysobj.param_sensitivity(x, pos, None, lam=s["lam"])
+    assert not st.any()
+    again, _ = sysobj.param_sensitivity(x, pos, None, lam=s["lam"])
+    assert np.array_equal(full, again)
+    perm = np.random.default_rng(3).permutation(k)
+    a, _ = sysobj.param_sensitivity(x, pos[perm], None, lam=s["lam"])
+    assert np.array_equal(a, full[:, perm])
+    a, _ = sysobj.param_sensitivity(x, pos[: k // 2], None, lam=s["lam"])
+    assert np.array_equal(a, full[:, : k // 2])
+    a, _ = sysobj.param_sensitivity(x, pos[k // 3: k // 3 + 1], None, lam=s["lam"])
+    assert np.array_equal(a, full[:, k // 3: k // 3 + 1])
+    for n in (1, 3):
+        with rhs_per_item(n):
+            assert sysobj.param_sensitivity_plan(pos)["rhs_per_item"] == n
+            a, _ = sysobj.param_sensitivity(x, pos, None, lam=s["lam"])
+        assert np.array_equal(a, full), n
+    one, _ = sysobj.param_sensitivity(x[:1], pos, None, lam=s["lam"])
+    assert np.array_equal(one[0], full[0])
+    tiled, st = sysobj.param_sensitivity(np.tile(x[:1], (64, 1)), pos, None, lam=s["lam"])
+    assert not st.any() and np.array_equal(tiled, np.broadcast_to(one, tiled.shape))
+    order = np.asarray([1, 0])
+    a, _ = sysobj.param_sensitivity(x[order], pos, None, lam=s["lam"])
+    assert np.array_equal(a, full[order])
+    # with a parameter row per system the rows are those of the list's own values
+    a, _ = sysobj.param_sensitivity(x, pos, s["params"], lam=s["lam"])
+    b, _ = sysobj.param_sensitivity(x[order], pos[perm], s["params"][order][:, perm], lam=s["lam"])
+    assert np.array_equal(b, a[order][:, perm])
+
+
+def test_a_workgroups_second_item(E):
+    """sketch25, 8 listed positions, 4096 tiled systems (13 MB of S): persistent workgroups take further items."""
+    sysobj, s = _system(E, "sketch25", 1), FS.system("sketch25")
+    pos = s["pos"][np.linspace(0, len(s["pos"]) - 1, 8).astype(int)]
+    one, _ = sysobj.param_sensitivity(s["x"][:1], pos, None, lam=s["lam"])
+    big, st = sysobj.param_sensitivity(np.tile(s["x"][:1], (4096, 1)), pos, None, lam=s["lam"])
+    assert not st.any() and np.array_equal(big, np.broadcast_to(one, big.shape))
+
+
+# ---- 4. failures stay local ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch150", 3)])
+def test_failures_stay_local(E, name, wgs):
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    x = np.tile(s["x"], (2, 1))
+    p = np.tile(s["params"], (2, 1))
+    good, st = sysobj.param_sensitivity(x, s["pos"], p, lam=s["lam"])
+    assert not st.any()
+    J = R.jacobian(R.substituted(s["recs"], s["pos"], p[1]), x[1], s["n_vars"])
+    lam_bad = -(np.linalg.eigvalsh(J.T @ J)[0] * 1.5 + 1.0)
+    bad, st = sysobj.param_sensitivity(x[1:2], s["pos"], p[1:2], lam=lam_bad)
+    assert st[0] == 1 and np.isnan(bad).all()
+    xx = x.copy()
+    xx[2] = np.nan
+    S, st = sysobj.param_sensitivity(xx, s["pos"], p, lam=s["lam"])
+    assert st.tolist() == [0, 0, 1, 0] and np.isnan(S[2]).all()
+    assert np.array_equal(S[[0, 1, 3]], good[[0, 1, 3]])
+
+
+# ---- 5. exact zeros -----------------------------------------------------------------------------------------------------------------------
+def test_exact_zeros(E):
+    """Two disjoint copies of sketch25 in one system; only constraints of the first are listed."""
+    recs, g = FS.inputs("sketch25")
+    second = recs.copy()
+    for i in range(len(second)):
+        second["ids"][i][: O.KIND_NUM_IDS[int(second["kind"][i])]] += 50
+    both = np.concatenate([recs, second])
+    s = FS.system("sketch25")
+    sysobj = front_system(E, both, 100, 1, route=None)
+    sysobj.set_sensitivity_route("fronts")
+    x = np.concatenate([s["x"], s["x"]], axis=1)
+    S, st = sysobj.param_sensitivity(x, s["pos"], s["params"], lam=s["lam"])
+    assert not st.any()
+    assert np.all(S[:, :, 50:] == 0.0) and not np.signbit(S[:, :, 50:]).any()
+    assert np.any(S[:, :, :50] != 0.0)
+    with logging_here():
+        for b, (Sref, spread) in enumerate(FS.references("sketch25")):
+            R.assert_matches(S[b][:, :50], Sref, spread, f"fronts, two copies of sketch25, the listed one [{b}]")
+
+
+# ---- 6. meaning ------------------------------------------------------------------------------------------------------------------------------
+def test_meaning_finite_differences_of_two_solves(E):
+    """(x(p + delta e_j) - x(p)) / delta of two solve_batch_params calls on the fronts route, sketch150 on 3 workgroups, residual
+    tolerance 1e-13, against S; granted: 4 x the distance between the ORACLE's same finite difference and the numpy S."""
+    sysobj, s = _system(E, "sketch150", 3), FS.system("sketch150")
+    sysobj.set_params_route("fronts")
+    recs, pos, n = s["recs"], s["pos"], s["n_vars"]
+    delta = 1e-6
+    cfg = E.Config(max_iterations=60, residual_tolerance=1e-13)
+    ocfg = O.Config(max_iterations=60, residual_tolerance=1e-13)
+    p0 = recs["param"][pos].copy()
+    picks = [0, len(pos) // 3, len(pos) // 2, len(pos) - 1]
+    rows = np.stack([p0] + [p0 + delta * (np.arange(len(pos)) == j) for j in picks])
+    x0 = np.repeat(s["start"][0][None, :], len(rows), axis=0)
+    x, st, _ = sysobj.solve_batch_params(x0, pos, rows, cfg)
+    xo = np.stack([O.solve_batch(R.substituted(recs, pos, r), x0[:1], ocfg, linsolve=O.LINSOLVE_SPARSE)[1][0] for r in rows])
+    S, status = sysobj.param_sensitivity(x[:1], pos, rows[:1], lam=s["lam"])
+    Sref, _ = R.reference(recs, n, xo[0], pos, rows[0], s["lam"])
+    assert not status.any()
+    for k, j in enumerate(picks):
+        fd_dev, fd_orc = (x[k + 1] - x[0]) / delta, (xo[k + 1] - xo[0]) / delta
+        scale = max(1.0, np.abs(Sref[j]).max())
+        granted = 4.0 * np.abs(fd_orc - Sref[j]).max() / scale
+        err = np.abs(fd_dev - S[0, j]).max() / scale
+        print("meaning", j, "oracle's finite difference to numpy S", granted / 4.0, "device", err)
+        _log(f"meaning, fronts, sketch150 parameter {j}: oracle's finite difference to the numpy S {granted / 4.0:.3e}; device's to its S {err:.3e} (granted {granted:.3e})")
+        assert err <= granted, (j, err, granted)
+
+
+# ---- 7. device form ---------------------------------------------------------------------------------------------------------------------------
+def _device_call(sysobj, s, torch, stream, S, st, deg, x, p):
+    sysobj.param_sensitivity_device(x.data_ptr(), s["pos"], p.data_ptr(), len(s["x"]), S.data_ptr(), st.data_ptr(), lam=s["lam"],
+                                    degenerate_ptr=deg.data_ptr(), stream=stream.cuda_stream)
+
+
+@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2)])
+def test_device_form(E, name, wgs):
+    import torch
+
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    host, _, hdeg = sysobj.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"], want_degenerate=True)
+    x, p = torch.tensor(s["x"], device="cuda"), torch.tensor(s["params"], device="cuda")
+    fresh = lambda: (torch.full(host.shape, 3.0, dtype=torch.float64, device="cuda"), torch.full((len(s["x"]),), 9, dtype=torch.int32, device="cuda"),
+                     torch.full((len(s["x"]),), 9, dtype=torch.int32, device="cuda"))
+    S, st, deg = fresh()
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        _device_call(sysobj, s, torch, stream, S, st, deg, x, p)
+    stream.synchronize()
+    assert np.array_equal(S.cpu().numpy(), host) and not st.cpu().numpy().any()
+    assert np.array_equal(deg.cpu().numpy().astype(np.uint32), hdeg)
+    S, st, deg = fresh()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    if wgs == 1:
+        # a call captured after the list was planned replays the same bits
+        with torch.cuda.graph(graph, stream=stream):
+            _device_call(sysobj, s, torch, torch.cuda.current_stream(), S, st, deg, x, p)
+        for _ in range(2):
+            S.fill_(3.0)
+            graph.replay()
+            torch.cuda.synchronize()
+            assert np.array_equal(S.cpu().numpy(), host) and not st.cpu().numpy().any()
+    else:
+        # several workgroups: a capturing stream is refused up front, nothing is enqueued, the outputs keep their sentinels
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # ("The CUDA Graph is empty")
+            with pytest.raises(E.NonLinearSystemError) as err:
+                with torch.cuda.graph(graph, stream=stream):
+                    _device_call(sysobj, s, torch, torch.cuda.current_stream(), S, st, deg, x, p)
+        assert err.value.code == ERR_INVALID_ARGUMENT
+        torch.cuda.synchronize()
+        assert np.all(S.cpu().numpy() == 3.0) and np.all(st.cpu().numpy() == 9) and np.all(deg.cpu().numpy() == 9)
+    # the next direct call gives the clean bits
+    with torch.cuda.stream(stream):
+        _device_call(sysobj, s, torch, stream, S, st, deg, x, p)
+    stream.synchronize()
+    assert np.array_equal(S.cpu().numpy(), host) and not st.cpu().numpy().any()
+
+
+# ---- 8. autograd above the limit -----------------------------------------------------------------------------------------------------------
+def test_autograd_above_the_limit(E):
+    import torch
+
+    from ezpz_amd import torch_ops
+
+    s = FS.system("sketch600", 2, FS.sixteen)
+    sysobj = _system(E, "sketch600", 0, route=None)
+    sysobj.set_params_route("fronts")
+    x0, p = torch.tensor(s["start"], device="cuda"), torch.tensor(s["params"], device="cuda")
+    grad_x = torch.tensor(np.random.default_rng(2).uniform(-1.0, 1.0, s["x"].shape), device="cuda")
+    # with the sensitivity route unset the forward runs on the fronts and the backward is declined, as it is today
+    pt = p.clone().requires_grad_(True)
+    xs = torch_ops.solve_params(sysobj, x0, s["pos"], pt, lam=s["lam"])
+    with pytest.raises(E.NonLinearSystemError):
+        xs.backward(grad_x)
+    sysobj.set_sensitivity_route("fronts")
+    try:
+        pt = p.clone().requires_grad_(True)
+        xs = torch_ops.solve_params(sysobj, x0, s["pos"], pt, lam=s["lam"])
+        xs.backward(grad_x)
+        got, gx, xf = pt.grad.cpu().numpy(), grad_x.cpu().numpy(), xs.detach().cpu().numpy()
+        for b in range(len(xf)):
+            Sref, spread = R.reference(s["recs"], s["n_vars"], xf[b], s["pos"], s["params"][b], s["lam"])
+            scale = np.maximum(1.0, np.abs(Sref).max(axis=1))
+            err = float((np.abs(got[b] - Sref @ gx[b]) / scale).max())
+            print("autograd sketch600", b, err, R.bar(spread))
+            _log(f"autograd, fronts, sketch600[{b}]: grad_params against S_ref grad_x: largest error {err:.3e} | bar granted {R.bar(spread):.3e} (spread {spread:.3e})")
+            assert err <= R.bar(spread), (b, err, R.bar(spread))
+    finally:
+        sysobj.set_sensitivity_route("default")
+        sysobj.set_params_route("default")
+
+
+# ---- 9. the setter ---------------------------------------------------------------------------------------------------------------------------
+def test_setter(E):
+    L = E.lib()
+    m = R.system("massive40")
+    block = E.System(m["recs"], m["n_vars"])
+    before, _ = block.param_sensitivity(m["x"], m["pos"], m["params"], lam=m["lam"])
+    assert L.ezpz_system_set_sensitivity_route(block._h, 1) == ERR_INVALID_ARGUMENT
+    with pytest.raises(E.NonLinearSystemError):
+        block.set_sensitivity_route("fronts")
+    after, _ = block.param_sensitivity(m["x"], m["pos"], m["params"], lam=m["lam"])
+    assert np.array_equal(before, after) and block.param_sensitivity_plan(m["pos"])["route"] == 0
+    s = FS.system("sketch150")
+    plain = E.System(s["recs"], s["n_vars"])  # created by default: for batches
+    never, _ = plain.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+    if plain.info()["front_max_batch"] != 0xFFFFFFFF:
+        assert L.ezpz_system_set_sensitivity_route(plain._h, 1) == ERR_INVALID_ARGUMENT
+        again, _ = plain.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+        assert np.array_equal(never, again)
+    fronts = _system(E, "sketch150", 3, route=None)
+    assert L.ezpz_system_set_sensitivity_route(fronts._h, 2) == ERR_INVALID_ARGUMENT
+    with pytest.raises(ValueError):
+        fronts.set_sensitivity_route("sideways")
+    a, _ = fronts.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+    assert np.array_equal(a, never)  # the default route's bits do not depend on how the system was created
+    fronts.set_sensitivity_route("fronts")
+    on, _ = fronts.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+    assert fronts.param_sensitivity_plan(s["pos"])["route"] == 1
+    fronts.set_sensitivity_route("default")
+    off, _ = fronts.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+    assert fronts.param_sensitivity_plan(s["pos"])["route"] == 0
+    assert np.array_equal(off, never) and not np.array_equal(on, never)
