@@ -11,16 +11,50 @@ import ezpz_amd as E
 import front_ref as F
 import gen
 import sensitivity_ref as R
+from oracle import oracle as O
 from front_ref import FASM_NOP, FASM_RHS, FRONT_EXPORTS, FRONT_REMOTE_PARENT, tri
 
 LAM = 1e-9
 
 
 def inputs(name):
-    """sketchN = gen.connected_sketch(N, 1000 + N); band / hub = gen.graph_sketch(name, 50, default_rng(21))."""
+    """sketchN = gen.connected_sketch(N, 1000 + N); band / hub = gen.graph_sketch(name, 50, default_rng(21));
+    mixed40 = gen.mixed_sketch(40, 77): all 13 kinds with a parameter, drawn weights -- mixed40:unit with every weight 1.0,
+    mixed40:double with every weight 2.0, mixed40+corner with the disjoint corner of `corner` appended;
+    linear100 = gen.linear_chain(100): the linear build -- linear100:weighted with weights of default_rng(78).uniform(0.5, 2.0)."""
+    if name.startswith("mixed40"):
+        recs, g = gen.mixed_sketch(40, 77)
+        if name == "mixed40+corner":
+            extra, vals = corner(len(g))
+            return np.concatenate([recs, extra]), np.concatenate([g, vals])
+        if name != "mixed40":
+            recs["weight"] = {"mixed40:unit": 1.0, "mixed40:double": 2.0}[name]
+        return recs, g
+    if name.startswith("linear100"):
+        recs, g = gen.linear_chain(100)
+        if name != "linear100":
+            assert name == "linear100:weighted"
+            recs["weight"] = np.random.default_rng(78).uniform(0.5, 2.0, len(recs))
+        return recs, g
     if name.startswith("sketch"):
         return gen.connected_sketch(int(name[6:]), 1000 + int(name[6:]))
     return gen.graph_sketch(name, 50, np.random.default_rng(21))
+
+
+CORNER_FIXED = 8  # the corner's records: 8 Fixed, then the three constraints whose guards fire
+
+
+def corner(n):
+    """A component of its own on the variables n .. n + 7: four points Q1, Q2, P, D, every coordinate held by a Fixed, Q1 == Q2
+    exactly -- a line of length zero, an arc of radius zero -- and three constraints with a parameter on them whose residual's
+    guard fires there: VerticalPointLineDistance, LinesAtAngle, ArcLength.  (No PointLineDistance: the oracle's Jacobian of it
+    is NaN without a degenerate flag at a line of length zero.)  Returns the records and the Fixed values."""
+    Q1, Q2, P, D = [(n + 2 * i, n + 2 * i + 1) for i in range(4)]
+    vals = np.asarray([1.0, 2.0, 1.0, 2.0, 3.0, 2.5, 4.0, 4.0])
+    cons = [O.fixed(n + i, float(v)) for i, v in enumerate(vals)]
+    cons += [O.vertical_point_line_distance(P, Q1, Q2, 1.0, weight=1.5), O.lines_at_angle(Q1, Q2, P, D, ("deg", 30.0), weight=0.7),
+             O.arc_length(Q1, Q2, P, 2.0)]
+    return O.stack(cons), vals
 
 
 def driven(recs):
@@ -34,6 +68,21 @@ def system(name, batch=2, pick=None):
     """name -> dict(recs, n_vars, pos, params [B, k], x [B, n] (the oracle's answers), lam): every constraint with a parameter
     listed (pick: a function of that list), draws of default_rng(33): parameters +-1e-3, starts +-0.02."""
     key = (name, batch, None if pick is None else pick.__name__)
+    if key not in _SYSTEMS and name == "mixed40:double":
+        # mixed40:unit at the same values with every weight 2.0 and 4 x lambda: J and g scaled by 2, JtJ + lam I and Jt g by 4
+        _SYSTEMS[key] = dict(system("mixed40:unit", batch, pick), recs=inputs(name)[0], lam=4.0 * LAM)
+    if key not in _SYSTEMS and name == "mixed40+corner":
+        # mixed40's own draw; the corner's three constraints listed after the others (not its Fixed), its variables at the
+        # Fixed values themselves
+        assert pick is None
+        base, (recs, g) = system("mixed40", batch), inputs(name)
+        n_base, n = len(base["recs"]), base["n_vars"]
+        first = n_base + CORNER_FIXED
+        pos = np.concatenate([base["pos"], np.arange(first, len(recs), dtype=np.uint32)])
+        own = recs["param"][first:][None, :] + np.random.default_rng(34).uniform(-1e-3, 1e-3, (batch, len(recs) - first))
+        tail = np.repeat(g[None, n:], batch, axis=0)
+        _SYSTEMS[key] = dict(recs=recs, n_vars=len(g), pos=pos, params=np.concatenate([base["params"], own], axis=1),
+                             x=np.concatenate([base["x"], tail], axis=1), lam=LAM, start=np.concatenate([base["start"], tail], axis=1))
     if key not in _SYSTEMS:
         recs, g = inputs(name)
         rng = np.random.default_rng(33)
@@ -57,6 +106,16 @@ def references(name, batch=2, pick=None):
         s = system(name, batch, pick)
         _REFS[key] = [R.reference(s["recs"], s["n_vars"], s["x"][b], s["pos"], s["params"][b], s["lam"]) for b in range(batch)]
     return _REFS[key]
+
+
+def two_row(recs, pos):
+    """The places in `pos` of the listed constraints with two rows (ArcRadius, ArcLength, PointsAtAngle)."""
+    return [j for j, p in enumerate(pos) if O.residual_dim(recs[int(p)]) == 2]
+
+
+# kinds.hpp: kind_is_linear, in the oracle's numbering
+LINEAR_KINDS = (O.FIXED, O.SCALAR_EQUAL, O.VERTICAL, O.HORIZONTAL, O.VERTICAL_DISTANCE, O.HORIZONTAL_DISTANCE, O.CIRCLE_RADIUS,
+                O.POINTS_COINCIDENT, O.MIDPOINT)
 
 
 def sixteen(pos):

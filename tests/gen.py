@@ -110,3 +110,104 @@ def graph_sketch(family, npts, rng):
         else:
             cons.append(O.vertical_distance(pt(i), pt(a), float(true[i][1] - true[a][1])))
     return O.stack(cons), true.reshape(-1)
+
+
+def _rot(v, t):
+    c, s = np.cos(t), np.sin(t)
+    return np.asarray([c * v[0] - s * v[1], s * v[0] + c * v[1]])
+
+
+def mixed_sketch(npts, seed):
+    """connected_sketch(npts, 1000 + npts) at the oracle's solution (the true layout), with a decoration on every second point a
+    (b = a + 1) that cycles through ten types consistent with that layout, so that all 13 kinds with a parameter occur -- the
+    two-row ones (ArcRadius, ArcLength, PointsAtAngle) and both angle units among them; the tenth type is a second Distance at
+    1.002 x the true length: inconsistent on purpose, so that weights change the answer.  Every weight is then drawn from
+    default_rng(seed + 1).uniform(0.5, 2.0).  The sign of an angle and the parameter of a kind that subtracts it are read off
+    the oracle's own residual at the true layout.  (mixed_sketch(40, 77): 118 variables, 116 constraints.)  Returns the records and
+    the true values."""
+    recs, g = connected_sketch(npts, 1000 + npts)
+    rc, x, _, conv, _ = O.solve_batch(recs, g[None, :], O.Config(max_iterations=60, residual_tolerance=1e-12), linsolve=O.LINSOLVE_SPARSE)
+    assert rc == 0 and conv[0]
+    rng = np.random.default_rng(seed)
+    vals = [float(v) for v in x[0]]
+    cons = [recs[i] for i in range(len(recs))]
+    pt = lambda i: (2 * i, 2 * i + 1)
+    xy = lambda i: np.asarray(vals[2 * i: 2 * i + 2])
+
+    def new_point(p):
+        vals.extend([float(p[0]), float(p[1])])
+        return (len(vals) - 2, len(vals) - 1)
+
+    def subtracting(make):
+        """make(param) of a kind whose residual is f(x) - param in every row: the parameter that makes it zero."""
+        r, deg = O.residual(make(0.0), np.asarray(vals))
+        assert not deg and np.ptp(r) <= 1e-9 * max(1.0, abs(r[0])), r
+        cons.append(make(float(r[0])))
+
+    def signed(make, value):
+        for v in (value, -value):
+            r, deg = O.residual(make(v), np.asarray(vals))
+            if not deg and np.abs(r).max() < 1e-9:
+                cons.append(make(v))
+                return
+        raise AssertionError("neither sign of the angle fits the layout")
+
+    for n_dec, a in enumerate(range(0, npts - 1, 2)):
+        b = a + 1
+        pa, pb = xy(a), xy(b)
+        u = pb - pa
+        unit = "deg" if (n_dec // 10) % 2 == 0 else "rad"
+        theta = float(rng.uniform(0.4, 1.2))
+        angle = lambda t: (unit, float(np.degrees(t)) if unit == "deg" else t)
+        kind = n_dec % 10
+        if kind == 0:
+            r = float(rng.uniform(0.5, 2.0))
+            t0, t1 = np.radians(rng.uniform(15.0, 45.0)), np.radians(rng.uniform(135.0, 165.0))
+            s = new_point(pa + r * np.asarray([np.cos(t0), np.sin(t0)]))
+            e = new_point(pa + r * np.asarray([np.cos(t1), np.sin(t1)]))
+            subtracting(lambda p: O.arc_radius(pt(a), s, e, p))
+            subtracting(lambda p: O.vertical_distance(s, pt(a), p))
+            subtracting(lambda p: O.vertical_distance(e, pt(a), p))
+        elif kind == 1:
+            e = new_point(pa + _rot(u, theta))
+            signed(lambda p: O.arc_length(pt(a), pt(b), e, p), theta * float(np.hypot(*u)))
+        elif kind == 2:
+            q = new_point(pa + _rot(u, theta) * float(rng.uniform(0.6, 1.5)))
+            signed(lambda p: O.points_at_angle(pt(a), pt(b), q, angle(p)), theta)
+            subtracting(lambda p: O.distance(pt(a), q, p))
+        elif kind == 3:
+            q = new_point(pb + _rot(u, theta) * float(rng.uniform(0.6, 1.5)))
+            signed(lambda p: O.lines_at_angle(pt(a), pt(b), pt(b), q, angle(p)), theta)
+            subtracting(lambda p: O.distance(pt(b), q, p))
+        elif kind == 4:
+            q = new_point(pa + _rot(u, theta) * float(rng.uniform(0.6, 1.5)))
+            signed(lambda p: O.arc_angle(pt(a), pt(b), q, angle(p)), theta)
+            subtracting(lambda p: O.distance(pt(a), q, p))
+        elif kind in (5, 6, 7):
+            q = new_point(pa + _rot(u, theta) * float(rng.uniform(0.6, 1.5)))
+            if kind == 5:
+                subtracting(lambda p: O.point_line_distance(q, pt(a), pt(b), p))
+                subtracting(lambda p: O.distance(q, pt(a), p))
+            elif kind == 6:
+                subtracting(lambda p: O.vertical_point_line_distance(q, pt(a), pt(b), p))
+                subtracting(lambda p: O.horizontal_distance(q, pt(a), p))
+            else:
+                subtracting(lambda p: O.horizontal_point_line_distance(q, pt(a), pt(b), p))
+                subtracting(lambda p: O.vertical_distance(q, pt(a), p))
+        elif kind == 8:
+            vals.append(float(rng.uniform(0.5, 2.0)))
+            subtracting(lambda p: O.circle_radius(pt(a), len(vals) - 1, p))
+        else:
+            cons.append(O.distance(pt(a), pt(b), 1.002 * float(np.hypot(*u))))
+    out = O.stack(cons)
+    out["weight"] = np.random.default_rng(seed + 1).uniform(0.5, 2.0, len(out))
+    return out, np.asarray(vals)
+
+
+def linear_chain(npts):
+    """Fixed, HorizontalDistance and VerticalDistance only (tests/test_gpu_front_params.py: test_linear_only_system)."""
+    cons = [O.fixed(0, 0.5), O.fixed(1, -0.5)]
+    for k in range(1, npts):
+        a, b = (2 * (k - 1), 2 * k - 1), (2 * k, 2 * k + 1)
+        cons += [O.horizontal_distance(b, a, 1.0 + 0.01 * k), O.vertical_distance(b, a, 0.5)]
+    return O.stack(cons), np.zeros(2 * npts)

@@ -40,12 +40,7 @@ def _half_permuted(pos):
     return np.random.default_rng(4).permutation(pos)[: max(1, len(pos) // 2)]
 
 
-@pytest.mark.parametrize("wgs", [1, 2, 4])
-@pytest.mark.parametrize("name", ["sketch25", "sketch75", "band", "hub"])
-def test_tables_executed_in_numpy(name, wgs):
-    """Factorisation with a zero right-hand side, then per listed position the rhs-only pass through the tables: S against the
-    dense solve from the oracle's rows, at the bar the reference's own spread grants; the full list and a permuted half list give
-    the same rows bit for bit (a row does not depend on the rest of the list)."""
+def _tables_case(name, wgs):
     s = FS.system(name)
     b = 0
     recs = R.substituted(s["recs"], s["pos"], s["params"][b])
@@ -61,6 +56,64 @@ def test_tables_executed_in_numpy(name, wgs):
     assert not bad
     where = {int(p): j for j, p in enumerate(s["pos"])}
     assert np.array_equal(Sh, S[[where[int(p)] for p in half]])
+
+
+@pytest.mark.parametrize("wgs", [1, 2, 4])
+@pytest.mark.parametrize("name", ["sketch25", "sketch75", "band", "hub"])
+def test_tables_executed_in_numpy(name, wgs):
+    """Factorisation with a zero right-hand side, then per listed position the rhs-only pass through the tables: S against the
+    dense solve from the oracle's rows, at the bar the reference's own spread grants; the full list and a permuted half list give
+    the same rows bit for bit (a row does not depend on the rest of the list)."""
+    _tables_case(name, wgs)
+
+
+@pytest.mark.parametrize("name,wgs", [("mixed40", 1), ("mixed40", 3), ("mixed40+corner", 1), ("mixed40+corner", 3), ("linear100", 1),
+                                      ("linear100:weighted", 3)])
+def test_tables_executed_in_numpy_all_kinds_guards_linear(name, wgs):
+    """The same on the systems with two-row listed constraints, angle kinds, weights, guards that fire and linear kinds only
+    (test_inputs_are_what_they_claim): the host tables are not what the GPU test of these systems finds wrong.  (Measured errors:
+    mixed40 3.1e-10 on 1 workgroup and on 3, bar 7.9e-9; with the corner 3.3e-10 on both, bar 8.1e-9; linear100 4.1e-13, weighted on 3
+    workgroups 4.4e-13, bar 1e-10.)"""
+    _tables_case(name, wgs)
+
+
+def test_inputs_are_what_they_claim():
+    """The properties the GPU tests of mixed40, mixed40+corner and linear100 rest on: a test that passes on inputs that lost them
+    would prove nothing."""
+    import front_ref as F
+    from oracle import oracle as O
+
+    s = FS.system("mixed40")
+    recs, pos = s["recs"], s["pos"]
+    listed = recs[pos]
+    assert len(pos) == len(recs) and all(R.has_param(r) for r in recs)
+    kinds = set(int(k) for k in listed["kind"])
+    assert kinds == {O.DISTANCE, O.VERTICAL_DISTANCE, O.HORIZONTAL_DISTANCE, O.FIXED, O.CIRCLE_RADIUS, O.ARC_RADIUS, O.POINT_LINE_DISTANCE,
+                     O.VERTICAL_POINT_LINE_DISTANCE, O.HORIZONTAL_POINT_LINE_DISTANCE, O.ARC_LENGTH, O.LINES_AT_ANGLE, O.ARC_ANGLE,
+                     O.POINTS_AT_ANGLE}
+    for k in (O.LINES_AT_ANGLE, O.ARC_ANGLE, O.POINTS_AT_ANGLE):  # both angle units of every angle kind
+        assert set(int(t) for t in listed["tag"][listed["kind"] == k]) == {O.ANGLE_OTHER_DEG, O.ANGLE_OTHER_RAD}, k
+    two = FS.two_row(recs, pos)
+    assert set(int(recs["kind"][pos[j]]) for j in two) == {O.ARC_RADIUS, O.ARC_LENGTH, O.POINTS_AT_ANGLE}
+    for wgs in (1, 3):
+        assert F.Plan(recs, s["n_vars"], wgs).n_wgs == wgs
+    T = FS.Tables(recs, s["n_vars"], 3, pos)
+    assert any(T.home(j)[0] != 0 for j in two)
+    assert np.any(recs["weight"] != 1.0) and np.all(FS.system("mixed40:unit")["recs"]["weight"] == 1.0)
+    assert np.all(FS.system("mixed40:double")["recs"]["weight"] == 2.0) and FS.system("mixed40:double")["lam"] == 4.0 * s["lam"]
+    assert np.array_equal(FS.system("mixed40:double")["x"], FS.system("mixed40:unit")["x"])
+    for b in range(len(s["x"])):
+        assert R.degenerate_count(recs, s["x"][b], pos, s["params"][b]) == 0
+    c = FS.system("mixed40+corner")
+    assert len(c["pos"]) == len(pos) + 3 and np.array_equal(c["pos"][:-3], pos) and c["n_vars"] == s["n_vars"] + 8
+    assert [int(k) for k in c["recs"]["kind"][c["pos"][-3:]]] == [O.VERTICAL_POINT_LINE_DISTANCE, O.LINES_AT_ANGLE, O.ARC_LENGTH]
+    for b in range(len(c["x"])):
+        assert R.degenerate_count(c["recs"], c["x"][b], c["pos"], c["params"][b]) == 3
+    for name in ("linear100", "linear100:weighted"):
+        lin = FS.system(name)
+        assert all(int(k) in FS.LINEAR_KINDS for k in lin["recs"]["kind"]) and len(lin["pos"]) == len(lin["recs"]) == 200
+        assert [F.Plan(lin["recs"], lin["n_vars"], wgs).n_wgs for wgs in (1, 3)] == [1, 3]
+        assert np.all(lin["recs"]["weight"] == 1.0) == (name == "linear100")
 
 
 def test_tables_hold_rhs_entries_only():
@@ -95,12 +148,19 @@ def test_tables_hold_rhs_entries_only():
             assert sorted(got) == sorted(want) and len(want) > 0
 
 
-@pytest.mark.parametrize("name", ["sketch25", "sketch75", "sketch150", "band", "hub"])
+NEW_INPUTS = ["mixed40", "mixed40:unit", "mixed40:double", "mixed40+corner", "linear100", "linear100:weighted"]
+SMALL_INPUTS = R.kind_names() + ["weighted", "under"]  # tests/sensitivity_ref.py's own systems, on the fronts in the GPU test
+
+
+@pytest.mark.parametrize("name", ["sketch25", "sketch75", "sketch150", "band", "hub"] + NEW_INPUTS + SMALL_INPUTS)
 def test_reference_spread_on_the_gpu_inputs(name):
     """The numpy reference's Cholesky-against-lstsq spread on the systems tests/test_gpu_front_sens.py checks: at most 5e-6, so no
     granted bar exceeds BAR_CEILING.  (Measured, 2 systems each: sketch25 1.4e-12, sketch75 2.9e-10, sketch150 8.7e-8, band 3.9e-9,
-    hub 6.1e-8, sketch600 5.6e-8 -- it depends on the linear algebra library in its last digits, so the numbers are not asserted.)"""
-    for b, (_, spread) in enumerate(FS.references(name)):
+    hub 6.1e-8, sketch600 5.6e-8; mixed40 4.0e-10, mixed40:unit 2.7e-10, mixed40:double 2.7e-10, mixed40+corner 4.0e-10, linear100
+    6.0e-13, linear100:weighted 5.2e-13; the 16 small systems 1.2e-10 at most (points_at_angle_rad) -- it depends on the linear
+    algebra library in its last digits, so the numbers are not asserted.)"""
+    refs = R.references(name) if name in SMALL_INPUTS else FS.references(name)
+    for b, (_, spread) in enumerate(refs):
         print(name, b, "spread", spread)
         assert spread <= 5e-6 and R.bar(spread) <= BAR_CEILING
 

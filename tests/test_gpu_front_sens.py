@@ -2,7 +2,10 @@
 factorisation on the fronts, many right-hand sides): against the numpy reference of tests/sensitivity_ref.py at
 its own rule max(1e-10, 20 x spread) -- tests/test_front_sens_cpu.py measures the spreads of exactly these systems --, above the
 1024-variable limit of the default route, bit for bit however the rows are asked for, failures that stay local, exact zeros,
-their meaning (finite differences of two solves), the device form, autograd above the limit, and the setter."""
+their meaning (finite differences of two solves), the device form, autograd above the limit, and the setter.  From section 10 on,
+what connected_sketch and graph_sketch never put on the device: every kind with a parameter as a right-hand side (the second row
+of ArcRadius, ArcLength, PointsAtAngle; the sincos branches of con_dparam per degree and per radian), weights that are not 1,
+guards that fire on listed constraints, and the linear build (the conditions on those inputs: tests/test_front_sens_cpu.py)."""
 import contextlib
 import os
 import warnings
@@ -76,7 +79,8 @@ def rhs_per_item(n):
 
 
 # ---- 1. against the numpy reference -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2), ("sketch150", 3), ("band", 1), ("band", 4), ("hub", 1), ("hub", 4)])
+@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2), ("sketch150", 3), ("band", 1), ("band", 4), ("hub", 1), ("hub", 4),
+                                      ("mixed40", 1), ("mixed40", 3), ("mixed40:unit", 3)])
 def test_against_the_numpy_reference(E, name, wgs):
     """If a system exceeded the rule, the default route's error on it (the parent's code, an independent implementation) would be
     measured and 4 x that granted instead: it has not been needed -- the errors are logged beside the bars."""
@@ -350,3 +354,201 @@ def test_setter(E):
     off, _ = fronts.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
     assert fronts.param_sensitivity_plan(s["pos"])["route"] == 0
     assert np.array_equal(off, never) and not np.array_equal(on, never)
+
+
+# ---- 10. kind by kind -----------------------------------------------------------------------------------------------------------------
+SMALL = R.kind_names() + ["weighted", "under"]
+# the small systems the planner of the fronts declines on their own: beside sketch25 as a disjoint second component
+BESIDE_SKETCH25 = ()
+
+
+def _small_system(E, name):
+    """-> (the system on one workgroup, the first variable of `name` in it)."""
+    key = (name, 1, "fronts")
+    s = R.system(name)
+    off = 50 if name in BESIDE_SKETCH25 else 0
+    if key not in _SYSTEMS:
+        recs = s["recs"]
+        if off:
+            first, g = FS.inputs("sketch25")
+            assert len(g) == off
+            recs = recs.copy()
+            for i in range(len(recs)):
+                recs["ids"][i][: O.KIND_NUM_IDS[int(recs["kind"][i])]] += off
+            recs = np.concatenate([first, recs])
+        sysobj = front_system(E, recs, off + s["n_vars"], 1, route=None)
+        sysobj.set_sensitivity_route("fronts")
+        _SYSTEMS[key] = sysobj
+    return _SYSTEMS[key], off
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_kind_by_kind(E, name):
+    """The 14 systems of tests/test_gpu_params.py's CASES -- one per kind with a parameter, the angle kinds per degree and per
+    radian --, the over-determined `weighted` (weights change S in its first digit) and the under-determined `under`, on the
+    fronts: S against the reference, the status, the degenerate count (a PointsAtAngle solve may end on a collapsed arm)."""
+    sysobj, off = _small_system(E, name)
+    s = R.system(name)
+    x, pos = s["x"], s["pos"]
+    if off:
+        x = np.concatenate([np.repeat(FS.system("sketch25")["x"][:1], len(x), axis=0), x], axis=1)
+        pos = pos + np.uint32(len(FS.inputs("sketch25")[0]))
+    plan = sysobj.param_sensitivity_plan(pos)
+    assert plan["route"] == 1 and plan["front_workgroups"] == 1, plan
+    S, st, deg = sysobj.param_sensitivity(x, pos, s["params"], lam=s["lam"], want_degenerate=True)
+    assert S.shape == (len(x), len(pos), off + s["n_vars"]) and not st.any()
+    assert np.all(S[:, :, :off] == 0.0) and not np.signbit(S[:, :, :off]).any()
+    with logging_here():
+        for b, (Sref, spread) in enumerate(R.references(name)):
+            assert deg[b] == R.degenerate_count(s["recs"], s["x"][b], s["pos"], s["params"][b]), (name, b)
+            R.assert_matches(S[b][:, off:], Sref, spread, f"fronts, {name}[{b}]")
+
+
+# ---- 11. the same bits however asked, two-row constraints in the list ------------------------------------------------------------------
+def test_the_same_bits_with_two_row_constraints_in_the_list(E):
+    """mixed40 on 3 workgroups.  A right-hand side of two rows leaves two entries in the residual-space vector; both are zero
+    again before the next right-hand side of the chunk -- else the rows of a list [two-row, one-row, two-row, one-row] depend on
+    how many right-hand sides share a work item.  Every row of a list is the row of its position asked alone."""
+    sysobj, s = _system(E, "mixed40", 3), FS.system("mixed40")
+    pos, x, lam = s["pos"], s["x"], s["lam"]
+    k = len(pos)
+    two = FS.two_row(s["recs"], pos)
+    assert len(two) == 6
+    full, st = sysobj.param_sensitivity(x, pos, None, lam=lam)
+    assert not st.any()
+    perm = np.random.default_rng(3).permutation(k)
+    a, _ = sysobj.param_sensitivity(x, pos[perm], None, lam=lam)
+    assert np.array_equal(a, full[:, perm])
+    for j in two:
+        a, st = sysobj.param_sensitivity(x, pos[j: j + 1], None, lam=lam)
+        assert not st.any() and np.array_equal(a, full[:, j: j + 1]), j
+    one = [j for j in range(k) if j not in two]
+    angle = [j for j in one if int(s["recs"]["kind"][pos[j]]) in (O.LINES_AT_ANGLE, O.ARC_ANGLE)]
+    mixed = np.asarray([two[0], angle[0], two[3], one[5]])  # (two[0] and two[3]: homes in workgroups 1 and 2)
+    alone = np.concatenate([sysobj.param_sensitivity(x, pos[j: j + 1], None, lam=lam)[0] for j in mixed], axis=1)
+    assert np.array_equal(alone, full[:, mixed])
+    for n in (1, 2, 4):
+        with rhs_per_item(n):
+            assert sysobj.param_sensitivity_plan(pos[mixed])["rhs_per_item"] == n
+            a, st = sysobj.param_sensitivity(x, pos[mixed], None, lam=lam)
+        assert not st.any() and np.array_equal(a, alone), n
+    single, _ = sysobj.param_sensitivity(x[:1], pos, None, lam=lam)
+    assert np.array_equal(single[0], full[0])
+    tiled, st = sysobj.param_sensitivity(np.tile(x[:1], (64, 1)), pos, None, lam=lam)
+    assert not st.any() and np.array_equal(tiled, np.broadcast_to(single, tiled.shape))
+
+
+# ---- 12. weights --------------------------------------------------------------------------------------------------------------------------
+def test_weights_are_taken(E):
+    """mixed40 with its drawn weights and with every weight 1.0, at the same values: S differs (each against its own reference:
+    test_against_the_numpy_reference), by far more than either's bar."""
+    s = FS.system("mixed40")
+    a, st = _system(E, "mixed40", 3).param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+    b, stb = _system(E, "mixed40:unit", 3).param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"])
+    assert not st.any() and not stb.any()
+    scale = np.maximum(1.0, np.abs(a).max(axis=2))
+    diff = float((np.abs(a - b).max(axis=2) / scale).max())
+    print("weighted against unit weights at the same values:", diff)
+    assert diff > 1e-3
+
+
+@pytest.mark.parametrize("wgs", [1, 3])
+def test_weights_of_two_and_four_lambda_give_the_bits_of_unit_weights(E, wgs):
+    """Exact: every weight 2.0 scales J and g by 2 -- a power of two, so JtJ + 4 lam I and Jt g are 4 x those of unit weights
+    in every bit, 1 / sqrt(pivot) is half, and every entry of S is the same double.  Unit weights take the kernel's unit_w
+    path (weights not read), 2.0 the weighted one."""
+    u, d = FS.system("mixed40:unit"), FS.system("mixed40:double")
+    assert np.array_equal(u["x"], d["x"]) and d["lam"] == 4.0 * u["lam"] and np.all(d["recs"]["weight"] == 2.0)
+    a, st = _system(E, "mixed40:unit", wgs).param_sensitivity(u["x"], u["pos"], u["params"], lam=u["lam"])
+    b, stb = _system(E, "mixed40:double", wgs).param_sensitivity(d["x"], d["pos"], d["params"], lam=d["lam"])
+    assert not st.any() and not stb.any()
+    print("entries that differ:", int((a != b).sum()), "of", a.size)
+    assert np.array_equal(a, b)
+
+
+# ---- 13. guards that fire -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("wgs", [1, 3])
+def test_guards_on_listed_constraints(E, wgs):
+    """mixed40+corner: three listed constraints on a line of length zero.  Each counts once (its Jacobian's guard and its
+    residual's both fire), its g is zero, so its row of S is +0.0 in every entry -- as are the corner's variables in every row:
+    no listed constraint with a g reaches that component."""
+    name = "mixed40+corner"
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    n_base = FS.system("mixed40")["n_vars"]
+    plan = sysobj.param_sensitivity_plan(s["pos"])
+    assert plan["route"] == 1 and plan["front_workgroups"] == wgs, plan
+    S, st, deg = sysobj.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"], want_degenerate=True)
+    assert not st.any() and deg.tolist() == [3, 3]
+    assert np.all(S[:, -3:, :] == 0.0) and not np.signbit(S[:, -3:, :]).any()
+    assert np.all(S[:, :, n_base:] == 0.0) and not np.signbit(S[:, :, n_base:]).any()
+    with logging_here():
+        for b, (Sref, spread) in enumerate(FS.references(name)):
+            R.assert_matches(S[b][:-3], Sref[:-3], spread, f"fronts, {name} on {wgs} workgroup(s), the rows off the corner [{b}]")
+
+
+# ---- 14. the linear build -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,wgs", [("linear100", 1), ("linear100", 3), ("linear100:weighted", 1), ("linear100:weighted", 3)])
+def test_linear_build(E, name, wgs):
+    """Fixed, HorizontalDistance, VerticalDistance only: front_sens_kernel<true> (the plan's linear_only follows from the kinds:
+    tests/test_front_sens_cpu.py checks them; neither info() nor the sensitivity plan shows the flag).  J and g do not depend on
+    x, so S at x and S at x + uniform(-1, 1) are the same bits."""
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    plan = sysobj.param_sensitivity_plan(s["pos"])
+    assert plan["route"] == 1 and plan["front_workgroups"] == wgs, plan
+    S, st, deg = sysobj.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"], want_degenerate=True)
+    assert not st.any() and not deg.any()
+    with logging_here():
+        for b, (Sref, spread) in enumerate(FS.references(name)):
+            R.assert_matches(S[b], Sref, spread, f"fronts, {name} on {wgs} workgroup(s) [{b}]")
+    moved = s["x"] + np.random.default_rng(9).uniform(-1.0, 1.0, s["x"].shape)
+    again, st = sysobj.param_sensitivity(moved, s["pos"], s["params"], lam=s["lam"])
+    assert not st.any() and np.array_equal(again, S)
+
+
+# ---- 15. device form and autograd with every kind ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["mixed40", "mixed40+corner"])
+def test_device_form_with_every_kind(E, name):
+    """On a stream, 3 workgroups: the host call's bits, the degenerate counts (0, and 3 with the corner) included."""
+    import torch
+
+    sysobj, s = _system(E, name, 3), FS.system(name)
+    host, _, hdeg = sysobj.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"], want_degenerate=True)
+    x, p = torch.tensor(s["x"], device="cuda"), torch.tensor(s["params"], device="cuda")
+    S = torch.full(host.shape, 3.0, dtype=torch.float64, device="cuda")
+    st, deg = (torch.full((len(s["x"]),), 9, dtype=torch.int32, device="cuda") for _ in range(2))
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        _device_call(sysobj, s, torch, stream, S, st, deg, x, p)
+    stream.synchronize()
+    assert np.array_equal(S.cpu().numpy(), host) and not st.cpu().numpy().any()
+    assert np.array_equal(deg.cpu().numpy().astype(np.uint32), hdeg) and hdeg.tolist() == ([3, 3] if name == "mixed40+corner" else [0, 0])
+
+
+def test_autograd_with_every_kind(E):
+    """mixed40 on 3 workgroups, both routes on the fronts: params.grad against S_ref grad_x at the forward's answer."""
+    import torch
+
+    from ezpz_amd import torch_ops
+
+    s = FS.system("mixed40")
+    sysobj = _system(E, "mixed40", 3, route=None)
+    sysobj.set_params_route("fronts")
+    sysobj.set_sensitivity_route("fronts")
+    try:
+        x0 = torch.tensor(s["start"], device="cuda")
+        pt = torch.tensor(s["params"], device="cuda").requires_grad_(True)
+        grad_x = torch.tensor(np.random.default_rng(2).uniform(-1.0, 1.0, s["x"].shape), device="cuda")
+        xs = torch_ops.solve_params(sysobj, x0, s["pos"], pt, lam=s["lam"])
+        xs.backward(grad_x)
+        got, gx, xf = pt.grad.cpu().numpy(), grad_x.cpu().numpy(), xs.detach().cpu().numpy()
+        for b in range(len(xf)):
+            Sref, spread = R.reference(s["recs"], s["n_vars"], xf[b], s["pos"], s["params"][b], s["lam"])
+            scale = np.maximum(1.0, np.abs(Sref).max(axis=1))
+            err = float((np.abs(got[b] - Sref @ gx[b]) / scale).max())
+            print("autograd mixed40", b, err, R.bar(spread))
+            _log(f"autograd, fronts, mixed40[{b}]: grad_params against S_ref grad_x: largest error {err:.3e} | bar granted {R.bar(spread):.3e} (spread {spread:.3e})")
+            assert err <= R.bar(spread), (b, err, R.bar(spread))
+    finally:
+        sysobj.set_sensitivity_route("default")
+        sysobj.set_params_route("default")
