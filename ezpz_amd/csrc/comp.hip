@@ -1,5 +1,6 @@
 // Launch of the component-resident LM kernel (comp_kernel.hip.hpp) -- its own translation unit so that the two kernel
-// builds compile beside the list-walk kernels of launch.hip.
+// builds compile beside the list-walk kernels of launch.hip.  comp_launch is also the route launcher of a driven call on the
+// interpreter (the PAR builds; driven_params.hpp: comp_driven_launch_args).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -16,13 +17,9 @@ int comp_launch(const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch
                 void* stream) {
     if (L.batch == 0) return EZPZ_OK;
     CompArgs a = comp_args_for(plan, dev_blob, L);  // (comp_launch.hip.hpp)
-    if (L.params) {  // (ezpz_system_solve_batch_params: the builds whose lanes take their parameters per system)
-        a.params = L.params;
-        a.par_overlay = L.par_overlay;
-        a.n_param = L.n_param;
+    if (L.params)  // (ezpz_system_solve_batch_params: the builds whose lanes take their parameters per system)
         return plan.linear ? comp_launch_build<true, true>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream))
                            : comp_launch_build<false, true>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream));
-    }
     return plan.linear ? comp_launch_build<true, false>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream))
                        : comp_launch_build<false, false>(plan, a, device, cus, lds_limit, static_cast<hipStream_t>(stream));
 }

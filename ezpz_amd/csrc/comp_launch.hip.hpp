@@ -34,7 +34,7 @@ int comp_launch_build(const CompPlan& plan, const CompArgs& args, int device, in
     return EZPZ_OK;
 }
 
-// The kernel's argument block for a call (without the driven parameters, which the PAR and SWP launches add).
+// The kernel's argument block for a call, the driven parameters of a PAR or SWP launch included (a sweep adds its steps).
 inline CompArgs comp_args_for(const CompPlan& plan, const uint32_t* dev_blob, const CompLaunch& L) {
     CompArgs a{};
     a.prog = dev_blob;
@@ -59,6 +59,9 @@ inline CompArgs comp_args_for(const CompPlan& plan, const uint32_t* dev_blob, co
     a.scratch_row0 = plan.rows_persistent;
     a.scratch_rows = plan.scratch_rows;
     a.red_row0 = plan.rows_persistent + plan.n_waves * plan.scratch_rows;
+    a.params = L.params;
+    a.par_overlay = L.par_overlay;
+    a.n_param = L.n_param;
     return a;
 }
 

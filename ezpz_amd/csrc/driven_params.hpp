@@ -1,9 +1,49 @@
-// What ezpz_system_solve_batch_params (params.hip) and ezpz_system_sweep_params (sweep.hip) share on the host: the device table a
-// `positions` list becomes, kept on the system, and where the list-walk teams keep their system's driven values.
+// What the entries that take a `positions` list of driven constraints share on the host: the check of a list,
+// and for ezpz_system_solve_batch_params and ezpz_system_sweep_params the one path behind both -- the request, the enqueue, the
+// host form (driven.cpp) -- with the route launchers it calls, each in the translation unit that instantiates its kernels.
 #pragma once
 #include "system.hpp"
 
 namespace ezpz {
+
+// The check of a `positions` list for every entry that takes one, and the map from caller position to place in the list
+// (kNoParamSlot: not driven).
+int driven_slot_map(const EzpzSystem& s, const uint32_t* positions, size_t n_param, std::vector<uint32_t>& slot_of_pos);
+
+// A list resolved once for the params entry, the sweep and ezpz_system_sweep_params_plan: the map, and the routes it takes.
+struct DrivenRequest {
+    std::vector<uint32_t> slot_of_pos;
+    bool for_comp = false;      // the component interpreter (else the list-walk teams, or the fronts)
+    uint32_t params_route = 0;  // EZPZ_PARAMS_ROUTE_* as read under launch_mu: checked again when the call takes the lock
+    uint32_t sweep_route = 0;   // EZPZ_SWEEP_*
+};
+// (a list-walk route: the program is built, and a system on a grid team is declined -- its workgroups' sub-programs would each
+// need their slice of the side array)
+int driven_request(EzpzSystem* sys, const uint32_t* positions, size_t n_param, DrivenRequest& r);
+// The device form of both entries behind their argument checks: steps == 0 a params call of `batch` systems, steps >= 1 `batch`
+// sweeps of `steps` solves in one launch (n_param, and for a sweep batch, not zero).
+int driven_enqueue(EzpzSystem* sys, const DrivenRequest& r, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                   const double* params_dev, size_t steps, size_t batch, const EzpzConfig* cfg, double* x_out_dev, EzpzStatus* status_dev,
+                   uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, hipStream_t stream);
+// The host form of both: stages max(steps, 1) * batch rows in the system's scratch, runs `device_form` on them (values in place) on
+// hipStreamPerThread, waits and reads back -- statuses first (a team timeout: EZPZ_ERR_HIP), the log cut to n_warnings per row.
+using DrivenDeviceForm = std::function<int(double* x_dev, const double* params_dev, EzpzStatus* status_dev, uint8_t* mask_dev, uint64_t* log_dev)>;
+int driven_host_form(EzpzSystem* sys, const double* x0, size_t n_param, const double* params, size_t steps, size_t batch, double* x_out,
+                     EzpzStatus* status, uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap, const DrivenDeviceForm& device_form);
+
+// ---- the route launchers (launch_mu is held, the device current; a.params / par_slot / n_param set, a.steps for a sweep) -------
+int list_walk_params_launch(EzpzSystem& s, SolveArgs& a, hipStream_t stream);                  // params.hip: the PAR builds
+int list_walk_sweep_launch(EzpzSystem& s, SolveArgs& a, uint32_t route, hipStream_t stream);   // sweep.hip: the SWP builds
+int comp_sweep_launch(EzpzSystem& s, const SolveArgs& a, hipStream_t stream);                  // sweep.hip: the interpreter's SWP builds
+int front_params_launch(EzpzSystem& s, SolveArgs& a, bool sweep, hipStream_t stream);          // front_params.hip: PAR, or SWP
+// (the interpreter's PAR builds: comp_launch of comp.hip with these arguments -- the one place that hands it the driven ones)
+inline CompLaunch comp_driven_launch_args(const SolveArgs& a) {
+    CompLaunch L = comp_launch_args(a);
+    L.params = a.params;
+    L.par_overlay = a.par_slot;
+    L.n_param = a.n_param;
+    return L;
+}
 
 // EZPZ_PARAMS_LDS=0: the teams read the driven values where the caller left them, whatever room their LDS has (A/B runs;
 // tests/test_gpu_params.py runs that form in a child process).  EZPZ_DEBUG=params: which form a launch took, on stderr.
@@ -14,52 +54,8 @@ inline bool params_lds_enabled() {
     }();
     return on;
 }
-
-// What a `positions` list becomes on the device -- the list-walk teams' side array (per constraint of the table: its place in the
-// list, or none) or the interpreter's overlay -- kept on the system for a caller that repeats its list.  (launch_mu is held.)
-inline bool driven_slots_cached(const EzpzSystem& s, const uint32_t* positions, size_t n_param, bool for_comp, uint32_t route) {
-    const EzpzSystem::DrivenParams& d = s.driven;
-    return d.valid && d.for_comp == for_comp && d.route == route && d.positions.size() == n_param &&
-           std::equal(positions, positions + n_param, d.positions.begin());
-}
-inline int driven_slots(EzpzSystem& s, const uint32_t* positions, size_t n_param, const std::vector<uint32_t>& slot_of_pos, bool for_comp,
-                        uint32_t route = EZPZ_PARAMS_ROUTE_DEFAULT) {
-    EzpzSystem::DrivenParams& d = s.driven;
-    if (driven_slots_cached(s, positions, n_param, for_comp, route)) return EZPZ_OK;
-    d.valid = false;
-    std::vector<uint32_t> table;
-    if (route == EZPZ_PARAMS_ROUTE_FRONTS) {
-        table = slot_of_pos;  // (the fronts' records carry the caller's position: the map itself)
-    } else if (for_comp) {
-        comp_param_overlay(*s.comp, slot_of_pos.data(), table);
-    } else {
-        table.resize(std::max<size_t>(s.host_con_pos.size(), 1), kNoParamSlot);
-        for (size_t ci = 0; ci < s.host_con_pos.size(); ++ci) table[ci] = slot_of_pos[s.host_con_pos[ci]];
-    }
-    // (the launches that read the previous list's table have to be through with it: each waited for the one before it, so the
-    // last one's completion is everybody's)
-    if (d.uploaded) HIP_TRY(hipEventSynchronize(d.uploaded));
-    int rc = d.slots.ensure(table.size());
-    if (rc != EZPZ_OK) return rc;
-    HIP_TRY(hipMemcpy(d.slots.p, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    d.positions.assign(positions, positions + n_param);
-    d.for_comp = for_comp;
-    d.route = route;
-    d.valid = true;
-    return EZPZ_OK;
-}
-
-// The request's argument checks and the map from caller position to place in the list (kNoParamSlot: not driven).
-inline int driven_slot_map(const EzpzSystem& s, const uint32_t* positions, size_t n_param, std::vector<uint32_t>& slot_of_pos) {
-    const size_t n_cs = s.host_has_param.size();
-    slot_of_pos.assign(std::max<size_t>(n_cs, 1), kNoParamSlot);
-    for (size_t j = 0; j < n_param; ++j) {
-        const uint32_t pos = positions[j];
-        if (pos >= n_cs || slot_of_pos[pos] != kNoParamSlot || !s.host_has_param[pos]) return EZPZ_ERR_INVALID_ARGUMENT;
-        slot_of_pos[pos] = (uint32_t)j;
-    }
-    return EZPZ_OK;
-}
+// (the params launches' line: the list-walk teams' -- `copies` of the values per workgroup -- or, copies == 0, the fronts')
+void debug_params_line(const EzpzSystem& s, uint32_t n_param, bool in_lds, size_t copies, size_t lds_from, size_t lds_to);
 
 // The teams' copies of their system's values: one per team of a workgroup of sub-wavefront teams, two for a wavefront-
 // partitioned workgroup (its wavefronts may be a system apart), one for a barrier workgroup -- behind everything else in
@@ -89,7 +85,5 @@ struct FrontParLds {
     uint32_t off;    // FrontArgs::par_lds_off
 };
 int front_params_lds_plan(EzpzSystem& s, size_t n_param, bool sweep, FrontParLds& out);  // (launch_mu is held, the device current)
-// The launch: a.params / par_slot / n_param set; sweep: a.steps solves per sweep in one launch (the SWP build).
-int front_params_launch(EzpzSystem& s, SolveArgs& a, bool sweep, hipStream_t stream);
 
 }  // namespace ezpz

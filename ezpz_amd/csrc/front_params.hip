@@ -1,6 +1,7 @@
 // Driven dimensions and sweeps on the FRONTAL shape: the route ezpz_system_set_params_route selects for
 // ezpz_system_solve_batch_params and ezpz_system_sweep_params on a system whose frontal plan serves every call.  The only
 // translation unit that instantiates the PAR and SWP builds of front_solve_kernel; front.hip's builds are what they were.
+// front_params_launch is the route launcher driven.cpp's enqueue calls for both entries.
 #include "driven_params.hpp"
 #include "front_launch.hip.hpp"
 
@@ -45,13 +46,23 @@ int launch_build(EzpzSystem& s, SolveArgs& a, hipStream_t stream) {
     fa.n_param = a.n_param;
     fa.par_lds_off = L.off;
     fa.steps = SWP ? a.steps : 1u;
-    static const bool say = debug_topic("params");
-    if (say)
-        std::fprintf(stderr, "[ezpz params] fronts: %u values per system %s (%u workgroups per system, LDS %zu -> %u of %zu bytes)\n", a.n_param,
-                     L.in_lds ? "staged in LDS" : "read from global memory", s.fronts->n_wgs, s.fronts->lds_bytes, L.bytes, s.lim.lds_bytes);
+    debug_params_line(s, a.n_param, L.in_lds, 0, s.fronts->lds_bytes, L.bytes);
     // (a sweep's steps run one behind the other on its slot: `batch` items side by side, batch x steps in all)
     return front_launch_on(s, front_solve_kernel<LIN, true, SWP>, fa, s.front_par[SWP ? 1 : 0].capacity, L.bytes, fa.batch,
                            fa.batch * (uint64_t)fa.steps, stream);
+}
+
+// The build of a system and a call.
+struct Build {
+    int (*lds_plan)(EzpzSystem&, uint32_t, FrontParLds&);
+    int (*launch)(EzpzSystem&, SolveArgs&, hipStream_t);
+};
+template <bool LIN, bool SWP>
+constexpr Build kBuild{lds_plan_build<LIN, SWP>, launch_build<LIN, SWP>};
+const Build& build_of(const EzpzSystem& s, bool sweep) {
+    const bool lin = s.fronts->linear_only;
+    if (sweep) return lin ? kBuild<true, true> : kBuild<false, true>;
+    return lin ? kBuild<true, false> : kBuild<false, false>;
 }
 
 }  // namespace
@@ -60,16 +71,12 @@ namespace ezpz {
 
 int front_params_lds_plan(EzpzSystem& s, size_t n_param, bool sweep, FrontParLds& out) {
     if (!s.fronts || !s.dev_fronts) return EZPZ_ERR_INVALID_ARGUMENT;
-    const bool lin = s.fronts->linear_only;
-    if (sweep) return lin ? lds_plan_build<true, true>(s, (uint32_t)n_param, out) : lds_plan_build<false, true>(s, (uint32_t)n_param, out);
-    return lin ? lds_plan_build<true, false>(s, (uint32_t)n_param, out) : lds_plan_build<false, false>(s, (uint32_t)n_param, out);
+    return build_of(s, sweep).lds_plan(s, (uint32_t)n_param, out);
 }
 
 int front_params_launch(EzpzSystem& s, SolveArgs& a, bool sweep, hipStream_t stream) {
     if (!s.fronts || !s.dev_fronts || !a.n_param || !a.params || !a.par_slot || (sweep && !a.steps)) return EZPZ_ERR_INVALID_ARGUMENT;
-    const bool lin = s.fronts->linear_only;
-    if (sweep) return lin ? launch_build<true, true>(s, a, stream) : launch_build<false, true>(s, a, stream);
-    return lin ? launch_build<true, false>(s, a, stream) : launch_build<false, false>(s, a, stream);
+    return build_of(s, sweep).launch(s, a, stream);
 }
 
 }  // namespace ezpz
@@ -82,9 +89,9 @@ extern "C" int ezpz_system_set_params_route(EzpzSystem* sys, uint32_t route) {
     std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
     if (sys->params_route == route) return EZPZ_OK;
     // (the launches that read the other route's table are through before the next call of either entry replaces it)
-    if (sys->driven.uploaded) {
+    if (sys->driven.list.done) {
         EZPZ_ON_DEVICE(sys->device);
-        HIP_TRY(hipEventSynchronize(sys->driven.uploaded));
+        if (int rc = sys->driven.list.before_overwrite()) return rc;
     }
     sys->params_route = route;
     return EZPZ_OK;

@@ -1,7 +1,8 @@
 // Dimension sensitivities on the FRONTAL shape: the route ezpz_system_set_sensitivity_route selects for
 // ezpz_system_param_sensitivity[_device] on a system whose frontal plan serves every call -- one factorisation per work item,
 // many right-hand sides, whatever the size of the component.  The only translation unit that instantiates front_sens_kernel;
-// the builds of front.hip and front_params.hip are what they were.  The tables come from front_sens_plan.cpp.
+// the builds of front.hip and front_params.hip are what they were.  The tables come from front_sens_plan.cpp; the list they
+// were made for is a KeptList (system.hpp), whose event this route alone stays out of while its stream is being captured.
 #include "driven_params.hpp"
 #include "front_launch.hip.hpp"
 #include "front_sens_kernel.hip.hpp"
@@ -12,14 +13,9 @@ namespace {
 
 // The route's plan of a `positions` list, kept on the system for a caller that repeats its list (touched under launch_mu).
 struct FrontSensPlan {
-    std::vector<uint32_t> positions;
-    bool valid = false;
+    KeptList list;
     DevBuf<uint32_t> tabs, par_slot;
-    hipEvent_t done = nullptr;  // the last launch that read the tables
-    uint64_t capacity = 0;      // workgroups of the build the device holds at once (0 = not asked yet)
-    ~FrontSensPlan() {
-        if (done) (void)hipEventDestroy(done);
-    }
+    uint64_t capacity = 0;  // workgroups of the build the device holds at once (0 = not asked yet)
 };
 
 FrontSensPlan& plan_of(EzpzSystem& s) {
@@ -76,27 +72,24 @@ int front_sens_launch(EzpzSystem& s, const double* x_dev, const uint32_t* positi
                       hipStream_t st) {
     const FrontPlan& plan = *s.fronts;
     FrontSensPlan& P = plan_of(s);
-    if (!(P.valid && P.positions.size() == n_param && std::equal(positions, positions + n_param, P.positions.begin()))) {
+    if (!P.list.same(positions, n_param)) {
         std::vector<uint32_t> tabs;
         if (!front_sens_tables(plan, positions, n_param, tabs)) return EZPZ_ERR_INVALID_ARGUMENT;
-        // (the launches that read the previous list's tables have to be through with them)
-        if (P.done) HIP_TRY(hipEventSynchronize(P.done));
-        P.valid = false;
         int rc;
+        if ((rc = P.list.before_overwrite()) != EZPZ_OK) return rc;
+        P.list.valid = false;
         if ((rc = P.tabs.ensure(tabs.size())) != EZPZ_OK) return rc;
         if ((rc = P.par_slot.ensure(slot_of_pos.size())) != EZPZ_OK) return rc;
         HIP_TRY(hipMemcpy(P.tabs.p, tabs.data(), tabs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(P.par_slot.p, slot_of_pos.data(), slot_of_pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         if (int rc2 = capacity_of(s, P)) return rc2;
-        P.positions.assign(positions, positions + n_param);
-        P.valid = true;
+        P.list.keep(positions, n_param);
     }
     const size_t n_vars = s.counts.n_vars;
-    // (the launches of this route on one system run one behind the other whatever their streams: the completion of the last one is
-    // what a call with another list waits for before it overwrites the tables.  A launch that is being recorded into a graph
-    // takes no part in that: its replays read the tables of the list it was recorded with, which the caller keeps repeating)
-    const bool recording = stream_capturing(st);
-    if (!recording) HIP_TRY(P.done ? hipStreamWaitEvent(st, P.done, 0) : hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
+    // (a launch that is being recorded into a graph takes no part in the list's event -- this route alone: its replays read the
+    // tables of the list it was recorded with, which the caller keeps repeating)
+    const bool take_part = !stream_capturing(st);
+    if (int rc = P.list.order_behind(st, take_part)) return rc;
     HIP_TRY(hipMemsetAsync(status_dev, 0, batch * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(S_dev, 0, batch * n_param * n_vars * sizeof(double), st));
     if (deg_dev) HIP_TRY(hipMemsetAsync(deg_dev, 0, batch * sizeof(uint32_t), st));
@@ -135,8 +128,7 @@ int front_sens_launch(EzpzSystem& s, const double* x_dev, const uint32_t* positi
         hipLaunchKernelGGL(front_sens_finish_kernel, grid, dim3(256), 0, st, S_dev, (const uint32_t*)status_dev, row, (uint64_t)batch);
         HIP_TRY(hipGetLastError());
     }
-    if (!recording) HIP_TRY(hipEventRecord(P.done, st));
-    return EZPZ_OK;
+    return P.list.record(st, take_part);
 }
 
 }  // namespace ezpz
@@ -149,12 +141,9 @@ extern "C" int ezpz_system_set_sensitivity_route(EzpzSystem* sys, uint32_t route
     std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
     if (sys->sens_route == route) return EZPZ_OK;
     // (the launches of the route that is left are through before the next call takes the other one)
-    if (sys->front_sens) {
-        FrontSensPlan& P = *static_cast<FrontSensPlan*>(sys->front_sens.get());
-        if (P.done) {
-            EZPZ_ON_DEVICE(sys->device);
-            HIP_TRY(hipEventSynchronize(P.done));
-        }
+    if (sys->front_sens && plan_of(*sys).list.done) {
+        EZPZ_ON_DEVICE(sys->device);
+        if (int rc = plan_of(*sys).list.before_overwrite()) return rc;
     }
     sys->sens_route = route;
     return EZPZ_OK;

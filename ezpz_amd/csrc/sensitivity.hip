@@ -2,9 +2,10 @@
 // ezpz_constraint_param_derivative (include/ezpz_amd.h).  The kernels are in sensitivity.hip.hpp and are
 // instantiated here only; this file is the host side: the plan of a `positions` list -- connected components by union-find,
 // the shape of every component that holds a listed constraint, its records, elimination order, envelope and product lists --
-// kept on the system (like the params overlay) with its device tables, workspace and the host entry's buffers.
+// kept on the system (a KeptList, like the params overlay's) with its device tables, workspace and the host entry's buffers.
+// The check of a list is the one every driven entry shares (driven_params.hpp: driven_slot_map).
+#include "driven_params.hpp"
 #include "sensitivity.hip.hpp"
-#include "system.hpp"
 
 #include <numeric>
 
@@ -12,8 +13,10 @@ using namespace ezpz;
 
 namespace {
 
+static_assert(kSensNone == kNoParamSlot, "SensRec::drv takes the list check's map (driven_slot_map) as it is");
+
 struct SensPlan {
-    std::vector<uint32_t> positions;
+    KeptList list;  // (its event: the last launch that read the tables and used the workspace)
     EzpzSensitivityPlan info{};
     std::vector<uint32_t> list_small, list_lds, list_ws;
     size_t lds_bytes = 0;       // dynamic LDS of the LDS shape's launch, and of the workspace shape's
@@ -26,13 +29,9 @@ struct SensPlan {
     DevBuf<SensRec> recs;
     DevBuf<uint32_t> u32;
     DevBuf<double> ws;
-    hipEvent_t done = nullptr;  // the last launch that read the tables and used the workspace
     // the host entry's buffers
     DevBuf<double> x, par, S;
     DevBuf<uint32_t> st;
-    ~SensPlan() {
-        if (done) (void)hipEventDestroy(done);
-    }
 };
 
 struct Ids {
@@ -319,34 +318,19 @@ int make_plan(const EzpzSystem& s, const uint32_t* positions, size_t n_param, co
     return EZPZ_OK;
 }
 
-// The request's argument errors (those of the params entries), and positions -> place in the list.
-int check_positions(const EzpzSystem* sys, const uint32_t* positions, size_t n_param, std::vector<uint32_t>& slot_of_pos) {
-    if (n_param && !positions) return EZPZ_ERR_INVALID_ARGUMENT;
-    if (n_param > 0xFFFFFFFEull) return EZPZ_ERR_INVALID_ARGUMENT;
-    const size_t n_cs = sys->host_has_param.size();
-    slot_of_pos.assign(std::max<size_t>(n_cs, 1), kSensNone);
-    for (size_t j = 0; j < n_param; ++j) {
-        const uint32_t pos = positions[j];
-        if (pos >= n_cs || slot_of_pos[pos] != kSensNone || !sys->host_has_param[pos]) return EZPZ_ERR_INVALID_ARGUMENT;
-        slot_of_pos[pos] = (uint32_t)j;
-    }
-    return EZPZ_OK;
-}
-
 // The system's plan for `positions` with its device tables (launch_mu is held; the system's device is current).
 int plan_for(EzpzSystem* sys, const uint32_t* positions, size_t n_param, const std::vector<uint32_t>& slot_of_pos, SensPlan*& out) {
     if (!sys->sens) sys->sens = std::make_shared<SensPlan>();
     SensPlan& P = *static_cast<SensPlan*>(sys->sens.get());
     out = &P;
-    if (P.positions.size() == n_param && std::equal(positions, positions + n_param, P.positions.begin()) && P.comps.p) return EZPZ_OK;
+    if (P.list.same(positions, n_param)) return EZPZ_OK;
     std::vector<SensComp> comps;
     std::vector<SensRec> recs;
     std::vector<uint32_t> u32;
     SensPlan fresh;
     if (int rc = make_plan(*sys, positions, n_param, slot_of_pos, fresh, comps, recs, u32)) return rc;
-    // (the launches that read the previous list's tables have to be through with them)
-    if (P.done) HIP_TRY(hipEventSynchronize(P.done));
-    P.positions.clear();
+    if (int rc = P.list.before_overwrite()) return rc;
+    P.list.valid = false;
     std::vector<uint32_t> lists = fresh.list_small;
     lists.insert(lists.end(), fresh.list_lds.begin(), fresh.list_lds.end());
     lists.insert(lists.end(), fresh.list_ws.begin(), fresh.list_ws.end());
@@ -367,7 +351,7 @@ int plan_for(EzpzSystem* sys, const uint32_t* positions, size_t n_param, const s
     P.lds_threads = fresh.lds_threads;
     P.ws_stride = fresh.ws_stride;
     P.ws_grid = fresh.ws_grid;
-    P.positions.assign(positions, positions + n_param);
+    P.list.keep(positions, n_param);
     return EZPZ_OK;
 }
 
@@ -389,7 +373,7 @@ int ezpz_constraint_param_derivative(const EzpzConstraint* c, const double* x, d
 int ezpz_system_param_sensitivity_plan(EzpzSystem* sys, const uint32_t* positions, size_t n_param, EzpzSensitivityPlan* out) {
     if (!sys || !out) return EZPZ_ERR_INVALID_ARGUMENT;
     std::vector<uint32_t> slot_of_pos;
-    if (int rc = check_positions(sys, positions, n_param, slot_of_pos)) return rc;
+    if (int rc = driven_slot_map(*sys, positions, n_param, slot_of_pos)) return rc;
     {
         // the fronts as this entry's route (ezpz_system_set_sensitivity_route; front_sens.hip): no component limit there
         std::lock_guard<std::mutex> launch_lock(sys->launch_mu);
@@ -412,7 +396,7 @@ int ezpz_system_param_sensitivity_device(EzpzSystem* sys, const double* x_dev, c
                                          uint32_t* degenerate_count_dev, void* stream) {
     if (!sys) return EZPZ_ERR_INVALID_ARGUMENT;
     std::vector<uint32_t> slot_of_pos;
-    if (int rc = check_positions(sys, positions, n_param, slot_of_pos)) return rc;
+    if (int rc = driven_slot_map(*sys, positions, n_param, slot_of_pos)) return rc;
     if (batch && (!status_dev || (n_param && (!S_out_dev || (sys->counts.n_vars && !x_dev))))) return EZPZ_ERR_INVALID_ARGUMENT;
     if (batch > 0xFFFFFFFFull) return EZPZ_ERR_TOO_LARGE;
     release_thread_kernel(sys->device);
@@ -438,9 +422,8 @@ int ezpz_system_param_sensitivity_device(EzpzSystem* sys, const double* x_dev, c
     if (n_param == 0) return EZPZ_OK;
     SensPlan& P = *plan;
     const size_t n_vars = sys->counts.n_vars;
-    // (the launches of this entry on one system run one behind the other, whatever their streams: they share the workspace, and the
-    // completion of the last one is what a call with another list waits for before it overwrites the tables)
-    HIP_TRY(P.done ? hipStreamWaitEvent(st, P.done, 0) : hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
+    // (the launches of this entry on one system run one behind the other, whatever their streams: they share the workspace too)
+    if (int rc = P.list.order_behind(st)) return rc;
     HIP_TRY(hipMemsetAsync(S_out_dev, 0, batch * n_param * n_vars * sizeof(double), st));
     if (degenerate_count_dev) HIP_TRY(hipMemsetAsync(degenerate_count_dev, 0, batch * sizeof(uint32_t), st));
     SensArgs a{};
@@ -487,15 +470,14 @@ int ezpz_system_param_sensitivity_device(EzpzSystem* sys, const double* x_dev, c
         hipLaunchKernelGGL(sens_finish_kernel, grid, dim3(256), 0, st, a);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(P.done, st));
-    return EZPZ_OK;
+    return P.list.record(st);
 }
 
 int ezpz_system_param_sensitivity(EzpzSystem* sys, const double* x, const uint32_t* positions, size_t n_param, const double* params,
                                   size_t batch, double lambda, double* S_out, uint32_t* status_out, uint32_t* degenerate_count_out) {
     if (!sys) return EZPZ_ERR_INVALID_ARGUMENT;
     std::vector<uint32_t> slot_of_pos;
-    if (int rc = check_positions(sys, positions, n_param, slot_of_pos)) return rc;
+    if (int rc = driven_slot_map(*sys, positions, n_param, slot_of_pos)) return rc;
     if (batch && (!status_out || (n_param && (!S_out || (sys->counts.n_vars && !x))))) return EZPZ_ERR_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> lock(sys->mu);
     EZPZ_ON_DEVICE(sys->device);

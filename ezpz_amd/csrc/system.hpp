@@ -6,6 +6,8 @@
 //   launch.hip    kernel dispatch: launch(), the device-pointer entry point, the evaluation-only kernel
 //   pipeline.cpp  host-pointer entry points: the one-call path (resident kernels), zero-copy, the three-stage pipeline
 //   freedom.hip   FreedomAnalysis
+//   driven.cpp    the entries that take a `positions` list of driven constraints: the list check, and the one call path behind
+//                 params.hip and sweep.hip (driven_params.hpp); sensitivity.hip and front_sens.hip keep their lists in a KeptList
 //   mixed.hip, multi.cpp, solve.cpp  on top of the C ABI (heterogeneous batches, several devices, solve / solve_inner)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -130,6 +132,37 @@ struct DevBuf {
     }
     ~DevBuf() {
         if (p) (void)hipFree(p);
+    }
+};
+
+// A `positions` list of driven constraints whose device tables a system keeps for a caller that repeats it (touched under the
+// system's launch_mu), and the completion of the last launch that read the tables.  The launches that read them run one behind the
+// other whatever their streams (order_behind, then record), so that one event is what a call with another list waits for before it
+// overwrites them.  `take_part` = false: a launch that stays out of the event (the frontal sensitivity route while its stream is
+// being captured: front_sens.hip); everybody else takes part under capture too.
+struct KeptList {
+    std::vector<uint32_t> positions;
+    bool valid = false;
+    hipEvent_t done = nullptr;
+    bool same(const uint32_t* p, size_t n) const { return valid && positions.size() == n && std::equal(p, p + n, positions.begin()); }
+    void keep(const uint32_t* p, size_t n) {
+        positions.assign(p, p + n);
+        valid = true;
+    }
+    int before_overwrite() {
+        if (done) HIP_TRY(hipEventSynchronize(done));
+        return EZPZ_OK;
+    }
+    int order_behind(hipStream_t stream, bool take_part = true) {
+        if (take_part) HIP_TRY(done ? hipStreamWaitEvent(stream, done, 0) : hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        return EZPZ_OK;
+    }
+    int record(hipStream_t stream, bool take_part = true) {
+        if (take_part) HIP_TRY(hipEventRecord(done, stream));
+        return EZPZ_OK;
+    }
+    ~KeptList() {
+        if (done) (void)hipEventDestroy(done);
     }
 };
 
@@ -303,30 +336,27 @@ struct EzpzSystem {
         }
     } pipe;
     std::vector<uint32_t> host_var_of, host_row_of, host_slot_row, host_slot_col;  // internal -> caller numbering
-    // ezpz_system_solve_batch_params (params.hip): whether the constraint at each caller position reads its parameter, the caller
-    // position of every constraint of the program's table, and what the last call's `positions` list was turned into (kept for a
-    // caller that repeats its list; touched under launch_mu): the list, the table-order side array of the list-walk teams, the
-    // interpreter's overlay (comp_program.cpp: comp_param_overlay)
+    // The driven entries: whether the constraint at each caller position reads its parameter, and the caller
+    // position of every constraint of the program's table
     std::vector<uint8_t> host_has_param;
     std::vector<uint32_t> host_con_pos;
-    // ezpz_system_param_sensitivity (sensitivity.hip): the constraints as the caller gave them, and the plan of the last call's
-    // `positions` list with its device tables and workspace (built on first use; touched under launch_mu)
+    // ezpz_system_solve_batch_params and ezpz_system_sweep_params (driven.cpp) share what the last call's `positions` list was
+    // turned into: the table-order side array of the list-walk teams, the interpreter's overlay (comp_program.cpp:
+    // comp_param_overlay) or, for the fronts, the map by caller position -- `for_comp` and `route` (EZPZ_PARAMS_ROUTE_*) say which
+    struct DrivenParams {
+        KeptList list;
+        bool for_comp = false;
+        uint32_t route = 0;
+        DevBuf<uint32_t> slots;
+    } driven;
+    // ezpz_system_param_sensitivity (sensitivity.hip): the constraints as the caller gave them, and the SensPlan of the last call's
+    // list -- its KeptList, device tables, workspace and the host entry's buffers (built on first use; touched under launch_mu)
     std::vector<EzpzConstraint> host_cs;
     std::shared_ptr<void> sens;
     // ezpz_system_set_sensitivity_route: the sensitivity entries of this system run on the frontal plan (front_sens.hip, DESIGN.md
-    // 3g; under launch_mu), and that route's plan of the last call's `positions` list: its tables on the device beside the plan
+    // 3g; under launch_mu), and that route's FrontSensPlan: the KeptList of the last call's list and its tables beside the plan
     uint32_t sens_route = 0;
     std::shared_ptr<void> front_sens;
-    struct DrivenParams {
-        std::vector<uint32_t> positions;
-        bool valid = false, for_comp = false;
-        uint32_t route = 0;  // EZPZ_PARAMS_ROUTE_* the table was made for (the fronts read it by caller position)
-        DevBuf<uint32_t> slots;
-        hipEvent_t uploaded = nullptr;  // the last launch that read `slots`: a new list overwrites them behind it
-        ~DrivenParams() {
-            if (uploaded) (void)hipEventDestroy(uploaded);
-        }
-    } driven;
     // FreedomAnalysis program (built on first use) and its scratch
     struct Freedom {
         bool built = false;

@@ -10,8 +10,8 @@ import pytest
 from oracle import oracle as O
 from oracle import textual as T
 from sensitivity import assert_batch_matches_oracle
-from sweep_common import (CASES, P0, P1, STEPS, SWEEPS, chain, chain_of_calls, driven_walk, oracle_chain, oracle_inputs, shapes,
-                          substituted)
+from sweep_common import (CASES, P0, P1, ROUTES, STEPS, SWEEPS, chain, chain_of_calls, driven_walk, oracle_chain, oracle_inputs,
+                          shapes, substituted)
 
 pytestmark = pytest.mark.gpu
 
@@ -320,6 +320,72 @@ def test_device_form(E):
     xc, stc, _ = chain_of_calls(s, x0, other, p2, want_mask=False)
     assert np.array_equal(xs, xc) and sts.tobytes() == stc.tobytes()
     assert np.array_equal(xd1.cpu().numpy(), xc[0]) and st1.cpu().numpy().view(STATUS_DTYPE).tobytes() == stc[0].tobytes()
+
+
+def _answer(E, call, s):
+    """What a call gives on `s`: its results, or the error code it is declined with."""
+    try:
+        return call(s), None
+    except E.NonLinearSystemError as e:
+        return None, e.code
+
+
+@pytest.mark.parametrize("name", list(ROUTES) + ["fronts"])
+def test_entries_interleaved_on_one_system(E, shape_of, monkeypatch, name):
+    """The three driven entries take turns on ONE system with two lists: what the system keeps of a `positions` list -- the params
+    and sweep entries' shared table, the sensitivity route's plan -- is replaced, matched and reused between them.  Every result is
+    bit for bit that of the same call made as the first and only call on a fresh system; a sensitivity call that a fresh system
+    declines (a component above EZPZ_SENSITIVITY_MAX_COMPONENT_VARS on the default route) is declined here with the same error."""
+    if name == "fronts":
+        (recs, g), team, mode = chain(40), E.TEAM_FRONTS, 5
+        monkeypatch.setenv("EZPZ_FRONT_WGS", "1")
+    else:
+        recs, g, team, mode = shape_of[name]
+
+    def system():
+        s = E.System(recs, len(g), team_size=team)
+        assert s.info()["team_mode"] == mode, (name, s.info())
+        if name == "fronts":
+            assert s.info()["grid_workgroups"] == 1
+            s.set_params_route("fronts")
+            s.set_sensitivity_route("fronts")
+        return s
+
+    pos_a, par_a, x0_a = driven_walk(E, recs, g, 8, 3, 61)
+    pos_b, par_b, x0_b = driven_walk(E, recs, g, 8, 3, 62, n_drive=2)
+    assert len(pos_a) != len(pos_b)
+    lists = {"A": (pos_a, par_a, x0_a), "B": (pos_b, par_b, x0_b)}
+
+    def params(which):
+        pos, par, x0 = lists[which]
+        return lambda s: s.solve_batch_params(x0, pos, par[0], want_mask=True)
+
+    def sweep(which):
+        pos, par, x0 = lists[which]
+        return lambda s: s.sweep_params(x0, pos, par, want_mask=True)
+
+    def sensitivity(which):
+        pos, par, x0 = lists[which]
+        return lambda s: s.param_sensitivity(x0, pos, par[1], want_degenerate=True)
+
+    order = [("params", params, "A"), ("sweep", sweep, "B"), ("params", params, "A"), ("sensitivity", sensitivity, "A"),
+             ("sweep", sweep, "A"), ("sensitivity", sensitivity, "B"), ("params", params, "B")]
+    shared = system()
+    for i, (entry, make, which) in enumerate(order):
+        what = "%s: call %d, %s(%s)" % (name, i, entry, which)
+        call = make(which)
+        got, got_err = _answer(E, call, shared)
+        want, want_err = _answer(E, call, system())
+        assert got_err == want_err, (what, got_err, want_err)
+        if entry != "sensitivity":
+            assert want_err is None, (what, want_err)
+            _same(got, want, what)
+        elif want_err is None:
+            for a, b in zip(got, want):
+                assert a.shape == b.shape and a.tobytes() == b.tobytes(), what
+        else:
+            assert want_err == ERR_INVALID_ARGUMENT, (what, want_err)
+            print(what, "declined on both with", want_err)
 
 
 def test_device_form_under_graph_capture(E):
