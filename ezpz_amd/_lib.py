@@ -84,6 +84,10 @@ class CViewport(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class CRedundancyConfig(C.Structure):
+    _fields_ = [("rank_tol", C.c_double), ("conflict_tol", C.c_double), ("group_tol", C.c_double)]
+
+
 # every symbol include/ezpz_amd.h declares
 EXPORTS = [
     "ezpz_default_config", "ezpz_device_count", "ezpz_error_string", "ezpz_system_create", "ezpz_system_destroy",
@@ -113,6 +117,7 @@ EXPORTS = [
     "ezpz_system_sweep_params_plan", "ezpz_system_sweep_params_device", "ezpz_system_sweep_params",
     "ezpz_system_set_params_route",
     "ezpz_system_set_sensitivity_route", "ezpz_debug_front_sens_tables",
+    "ezpz_default_redundancy_config", "ezpz_system_redundancy", "ezpz_system_redundancy_device",
 ]
 
 _lib = None
@@ -149,6 +154,12 @@ def lib():
     L.ezpz_system_freedom_batch.argtypes = [vp, vp, sz, vp, vp]
     L.ezpz_system_freedom_batch_device.restype = C.c_int
     L.ezpz_system_freedom_batch_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.ezpz_default_redundancy_config.restype = None
+    L.ezpz_default_redundancy_config.argtypes = [C.POINTER(CRedundancyConfig)]
+    L.ezpz_system_redundancy.restype = C.c_int
+    L.ezpz_system_redundancy.argtypes = [vp, vp, sz, C.POINTER(CRedundancyConfig), vp, vp, vp, vp, sz, vp]
+    L.ezpz_system_redundancy_device.restype = C.c_int
+    L.ezpz_system_redundancy_device.argtypes = [vp, vp, sz, C.POINTER(CRedundancyConfig), vp, vp, vp, vp, sz, vp, vp]
     L.ezpz_current_device.restype = C.c_int
     L.ezpz_current_device.argtypes = []
     L.ezpz_host_register.restype = C.c_int

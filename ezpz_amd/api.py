@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -388,6 +388,19 @@ class Config:
 
     def _c(self) -> CConfig:
         return CConfig(self.max_iterations, self.residual_tolerance, self.step_tolerance, self.initial_lambda)
+
+
+@dataclass
+class RedundancyConfig:
+    """EzpzRedundancyConfig: a row that keeps more than rank_tol of its length is independent, a dependent row whose unweighted
+    leftover residual exceeds conflict_tol conflicts, an accepted row with a share above group_tol joins a conflict group."""
+
+    rank_tol: float = 1e-6
+    conflict_tol: float = 1e-4
+    group_tol: float = 1e-6
+
+    def _c(self) -> CRedundancyConfig:
+        return CRedundancyConfig(self.rank_tol, self.conflict_tol, self.group_tol)
 
 
 class WarningContent:
@@ -765,6 +778,47 @@ class System:
                              stream: int = 0) -> None:
         rc = lib().ezpz_system_freedom_batch_device(self._h, x_ptr, batch, mask_ptr, part_ptr or None,
                                                     count_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+    INDEPENDENT, ZERO, REDUNDANT, CONFLICTING = 0, 1, 2, 3  # the statuses of `redundancy`
+
+    def redundancy(self, x: np.ndarray, focus=None, config: Optional[RedundancyConfig] = None, want_rows: bool = False):
+        """Redundancy analysis (`ezpz_system_redundancy`) of each value vector x [batch, n_vars], normally a solve's answers: the
+        rows of the weighted Jacobian are visited in request order, and a row that depends on earlier ones is REDUNDANT or -- its
+        residual cannot be met together with theirs -- CONFLICTING; a row without entries at x is ZERO.  Returns a dict:
+        "con_status" [batch, n_constraints] uint8 (the maximum over a constraint's rows), "rank" [batch] (independent rows),
+        "row_status" [batch, n_rows] with want_rows, and with `focus` (constraint positions) "group" [batch, len(focus),
+        n_constraints]: 1 for focus[k] and for every constraint whose accepted rows the dependent rows of focus[k] are made of."""
+        n, n_cs = self.n_vars, len(self.records)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, max(n, 1))
+        batch = x.shape[0]
+        f = self._positions(focus) if focus is not None else np.zeros(0, np.uint32)
+        cfg = (config or RedundancyConfig())._c()
+        con = np.zeros((batch, n_cs), np.uint8)
+        rank = np.zeros(batch, np.uint32)
+        rows = np.zeros((batch, max(self.info()["n_rows"], 1)), np.uint8) if want_rows else None
+        group = np.zeros((batch, len(f), n_cs), np.uint8)
+        rc = lib().ezpz_system_redundancy(self._h, x.ctypes.data, batch, C.byref(cfg), con.ctypes.data,
+                                          rows.ctypes.data if want_rows else None, rank.ctypes.data,
+                                          f.ctypes.data if len(f) else None, len(f), group.ctypes.data if len(f) else None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        out = {"con_status": con, "rank": rank}
+        if want_rows:
+            out["row_status"] = rows[:, : self.info()["n_rows"]]
+        if focus is not None:
+            out["group"] = group
+        return out
+
+    def redundancy_device(self, x_ptr: int, batch: int, con_status_ptr: int, row_status_ptr: int = 0, rank_ptr: int = 0,
+                          focus=None, group_ptr: int = 0, stream: int = 0, config: Optional[RedundancyConfig] = None) -> None:
+        """Device pointers (e.g. torch tensors' data_ptr()) and a hipStream_t handle; enqueue only.  `focus` stays a host list."""
+        f = self._positions(focus) if focus is not None else np.zeros(0, np.uint32)
+        cfg = (config or RedundancyConfig())._c()
+        rc = lib().ezpz_system_redundancy_device(self._h, x_ptr or None, batch, C.byref(cfg), con_status_ptr or None,
+                                                 row_status_ptr or None, rank_ptr or None, f.ctypes.data if len(f) else None,
+                                                 len(f), group_ptr or None, stream or None)
         if rc != 0:
             raise NonLinearSystemError(rc)
 

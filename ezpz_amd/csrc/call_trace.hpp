@@ -28,6 +28,9 @@ enum CallStage : uint32_t {
     // ezpz_system_sweep_params_device (sweep.hip)
     SWEEP_TABLE_UPLOADED = 30,  // a `positions` list other than the system's last one: waited for earlier launches, copied its table
     SWEEP_LAUNCHED = 31,        // the one launch of the sweep enqueued
+    // ezpz_system_redundancy_device (redundancy.hip)
+    REDUNDANCY_PREPARED = 40,  // something blocking first: tables built, a focus list other than the last one's, a buffer that had to grow
+    REDUNDANCY_LAUNCHED = 41,  // gather, evaluation and the analysis kernel enqueued
 };
 
 struct CallTrace {

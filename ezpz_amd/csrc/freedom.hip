@@ -8,10 +8,8 @@
 using namespace ezpz;
 
 // ---- FreedomAnalysis (solver/find_dof.rs, analysis.rs) ----------------------------------------------------------------
-namespace {
-
 // Connected components of the Jacobian's row/variable graph and, per component, the dense placement of its slots.
-int build_freedom(EzpzSystem* sys) {
+int ezpz::build_freedom(EzpzSystem* sys) {
     auto& F = sys->freedom;
     if (F.built) return EZPZ_OK;
     const uint32_t n = sys->counts.n_vars, m = sys->counts.n_rows, zj = sys->counts.zj;
@@ -106,6 +104,8 @@ int build_freedom(EzpzSystem* sys) {
     if (!comps.empty()) F.comp0 = comps[F.big];
     F.ws = std::max<uint32_t>(ws, 1);
     F.max_n = max_n;
+    F.host_comps = comps;
+    F.host_items = items;
     // LANE: a lane per (system, component) with 128 private workspaces in <= 64 KiB of LDS
     F.lane = F.ws <= 64;
     if (F.lane) {
@@ -118,6 +118,8 @@ int build_freedom(EzpzSystem* sys) {
     F.built = true;
     return EZPZ_OK;
 }
+
+namespace {
 
 // x_dev: final values, caller order.  Everything on `stream`.
 // `done_flag` (optional): a word of mapped host memory; when the call fits ONE launch of one workgroup -- a small system's

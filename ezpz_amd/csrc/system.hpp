@@ -6,6 +6,7 @@
 //   launch.hip    kernel dispatch: launch(), the device-pointer entry point, the evaluation-only kernel
 //   pipeline.cpp  host-pointer entry points: the one-call path (resident kernels), zero-copy, the three-stage pipeline
 //   freedom.hip   FreedomAnalysis
+//   redundancy.hip  redundant / conflicting constraints and conflict groups (the row-space counterpart, on freedom.hip's components)
 //   driven.cpp    the entries that take a `positions` list of driven constraints: the list check, and the one call path behind
 //                 params.hip and sweep.hip (driven_params.hpp); sensitivity.hip and front_sens.hip keep their lists in a KeptList
 //   mixed.hip, multi.cpp, solve.cpp  on top of the C ABI (heterogeneous batches, several devices, solve / solve_inner)
@@ -371,7 +372,12 @@ struct EzpzSystem {
         uint32_t big = 0;     // ... and its index
         DevBuf<uint8_t> mask;
         DevBuf<uint32_t> count;
+        std::vector<FreedomComp> host_comps;  // what `comps` and the items of `lists` hold (redundancy.hip derives its row tables)
+        std::vector<uint32_t> host_items;
     } freedom;
+    // ezpz_system_redundancy (redundancy.hip): its RedundancyPlan -- row tables beside the freedom lists, workspace, the host
+    // entry's buffers (built on first use; touched under mu, like `freedom`)
+    std::shared_ptr<void> redundancy;
     ~EzpzSystem() {
         if (dev_program) (void)hipFree(dev_program);
         if (dev_grid_blob) (void)hipFree(dev_grid_blob);
@@ -519,6 +525,11 @@ int ensure_program(EzpzSystem* sys);  // the rest of a deferred analysis (EzpzSy
 // ezpz_system_eval_batch for a caller that holds sys->mu already (launch.hip; FreedomAnalysis by probes checks its null vectors
 // against the Jacobian)
 int eval_batch_locked(EzpzSystem* sys, const double* x, size_t batch, double* r_out, double* jv_out, uint32_t* degenerate_count_out);
+
+// ---- freedom.hip ------------------------------------------------------------------------------------------------------------
+// The component tables of sys->freedom (built once): the connected components of the Jacobian's row / variable graph and each
+// component's dense placement of its slots.  The caller holds sys->mu; the system's device is current.
+int build_freedom(EzpzSystem* sys);
 
 // ---- pipeline.cpp -----------------------------------------------------------------------------------------------------------
 bool host_range_registered(const void* p, size_t bytes);  // inside a range the caller registered (ezpz_host_register)

@@ -508,6 +508,53 @@ int ezpz_system_freedom_batch(EzpzSystem* sys, const double* x, size_t batch, ui
 int ezpz_system_freedom_batch_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* under_mask_dev,
                                      double* participation_dev, uint32_t* n_under_dev, void* stream);
 
+/* ---- Redundancy analysis: redundant and conflicting constraints per system (a project extension: the reference has none) ----
+ * The row-space counterpart of FreedomAnalysis.  Per system b: values x_b (normally a solve's answer, the caller's variable
+ * order) and the tier the system was created from.  J (m x n) is the weighted Jacobian at x_b and r the weighted residual, rows
+ * in the reference's order (request order, a constraint's rows consecutive: what ezpz_system_eval_batch returns); w_i is the
+ * weight of row i's constraint.  The rows are visited IN THAT ORDER, keeping an orthonormal basis q_1 .. q_p of the rows accepted
+ * so far, each q_k with a companion scalar s_k: the same linear combination applied to r.  For row i, a = J[i, :], rho = r_i:
+ *   1. ||a|| == 0 exactly (a degeneracy guard fired, or nothing depends on the row at x): the row is ZERO; next row.
+ *   2. classical Gram-Schmidt TWICE: per pass h = Q v, v <- v - h^T Q, rho <- rho - h . s, v starting as a.  Every dot product
+ *      and every update is a fixed-order sum: results are bit-identical from run to run, whatever the batch or the place in it.
+ *   3. tau = ||v|| / ||a||.  tau > rank_tol (and fewer basis vectors than the row's component has variables): INDEPENDENT,
+ *      q = v / ||v|| and s = rho / ||v|| join the basis.  Otherwise the row depends on earlier rows: CONFLICTING if
+ *      |rho| / w_i > conflict_tol (the linearised system cannot satisfy it together with the earlier rows), else REDUNDANT.
+ * Status values: 0 INDEPENDENT, 1 ZERO, 2 REDUNDANT, 3 CONFLICTING; a constraint's status is the maximum over its rows; rank[b]
+ * counts the INDEPENDENT rows.  The rule is relative per row, so a constraint's weight does not change its class -- on purpose
+ * unlike find_dof.rs, whose rank rule is relative to the largest pivot.  Which of two dependent constraints is flagged is decided
+ * by the order of the request: the later one.  rank_tol defaults to 1e-6 (an LM answer meets residual_tolerance 1e-8, so a
+ * dependency that holds on the solution set holds at x to that order: two decades of margin), conflict_tol to 1e-4 (the
+ * reference's own "satisfied" bar, lib.rs:43).  J is block diagonal over the connected components of its row / variable graph and
+ * the procedure runs per component (same result as on the whole matrix).
+ * Conflict groups: for focus[0 .. n_focus) (constraint positions, host memory in both entries, none listed twice)
+ * group[b][k][c] = 1 when c is focus[k] itself or owns an accepted row a_j that takes part in the expansion a_i = sum c_j a_j of a
+ * dependent row i of focus[k]: |c_j| ||a_j|| > group_tol ||a_i|| (group_tol defaults to 1e-6).  All zero when focus[k] has no
+ * dependent row.
+ * con_status [batch][n_cs]; row_status [batch][n_rows], rank [batch] optional (NULL); group [batch][n_focus][n_cs] uint8.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: x or con_status NULL with batch > 0, a focus position
+ * >= n_cs or listed twice, focus or group NULL with n_focus > 0, a tolerance negative or not finite.  batch == 0: EZPZ_OK, nothing
+ * written.  EZPZ_ERR_EMPTY_SYSTEM as for FreedomAnalysis; EZPZ_ERR_TOO_LARGE: a component whose workspace exceeds 2^31 doubles.
+ * The _device entry takes device pointers (focus stays a host pointer) and only enqueues on `stream`, like
+ * ezpz_system_freedom_batch_device, and follows its stream-capture rules; a call whose buffers have to grow or whose focus list
+ * differs from the last call's first waits for the system's previous launch of this entry.  Launches of this entry on one system
+ * run one behind the other whatever their streams: they share the plan's workspace.  A component runs on one lane or one
+ * workgroup; no workgroup waits for another. */
+typedef struct EzpzRedundancyConfig {
+    double rank_tol, conflict_tol, group_tol;
+} EzpzRedundancyConfig;
+#define EZPZ_ROW_INDEPENDENT 0
+#define EZPZ_ROW_ZERO 1
+#define EZPZ_ROW_REDUNDANT 2
+#define EZPZ_ROW_CONFLICTING 3
+void ezpz_default_redundancy_config(EzpzRedundancyConfig* cfg); /* 1e-6, 1e-4, 1e-6 */
+int ezpz_system_redundancy(EzpzSystem* sys, const double* x, size_t batch, const EzpzRedundancyConfig* cfg /* NULL = default */,
+                           uint8_t* con_status, uint8_t* row_status, uint32_t* rank, const uint32_t* focus, size_t n_focus,
+                           uint8_t* group);
+int ezpz_system_redundancy_device(EzpzSystem* sys, const double* x_dev, size_t batch, const EzpzRedundancyConfig* cfg,
+                                  uint8_t* con_status_dev, uint8_t* row_status_dev, uint32_t* rank_dev, const uint32_t* focus,
+                                  size_t n_focus, uint8_t* group_dev, void* stream);
+
 /* ---- ezpz::solve for a batch (new; SURVEY.md 8f #3: priority tiers + weights end-to-end on device batches) --------
  * `batch` systems share the request list and differ in their guesses (x0 AoS [batch][n_vars], id == index).  Per
  * system exactly the semantics of ezpz_solve: LineSide / CircleSide inferred from that system's own guesses
