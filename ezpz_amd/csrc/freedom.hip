@@ -125,10 +125,28 @@ namespace {
 // `done_flag` (optional): a word of mapped host memory; when the call fits ONE launch of one workgroup -- a small system's
 // analysis: values gathered, Jacobian evaluated and analysed by the same kernel -- the kernel stores `done_seq` there at its end and
 // *flagged says so (the caller polls the word instead of the stream: a stream query costs more than this kernel runs).
+// The launches share the system's one x_int, jv, part, gws, step_tau and step_done: they are ordered behind the system's last ones
+// on whatever stream (F.order) and recorded there at the end.  `host_waits`: the caller waits for these launches itself before it
+// lets go of sys->mu (the host entry) -- they are ordered behind a device call still in flight, and nothing is recorded for the
+// next call to wait for (the one-launch form stays one launch and no event).
 int freedom_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* mask_dev, double* part_dev,
-                   uint32_t* count_dev, hipStream_t stream, unsigned long long* done_flag = nullptr, unsigned long long done_seq = 0,
-                   bool* flagged = nullptr, bool chain_route = false) {
+                   uint32_t* count_dev, hipStream_t stream, bool host_waits, unsigned long long* done_flag = nullptr,
+                   unsigned long long done_seq = 0, bool* flagged = nullptr, bool chain_route = false) {
     auto& F = sys->freedom;
+    // (a buffer that has to grow is replaced behind the last launch that used it)
+    auto grow = [&F](auto& buf, size_t count) -> int {
+        if (count > buf.cap)
+            if (int rc = F.order.before_overwrite()) return rc;
+        return buf.ensure(count);
+    };
+    auto ordered = [&]() -> int {
+        if (host_waits) {
+            if (F.order.done) HIP_TRY(hipStreamWaitEvent(stream, F.order.done, 0));
+            return EZPZ_OK;
+        }
+        return F.order.order_behind(stream);
+    };
+    auto recorded = [&]() -> int { return host_waits ? EZPZ_OK : F.order.record(stream); };
     // (a kernel of the calling thread's one-call path that waits on the device for its next request holds hipStreamPerThread: work
     // put there would queue behind it until its lease runs out, so it is told to leave -- unless this call has a stream of its own)
     if (!done_flag) release_thread_kernel(sys->device);
@@ -138,10 +156,10 @@ int freedom_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* 
     if (n == 0 || sys->counts.n_rows == 0) return EZPZ_ERR_EMPTY_SYSTEM;  // find_dof.rs:43-44
     rc = build_freedom(sys);
     if (rc != EZPZ_OK) return rc;
-    if ((rc = F.x_int.ensure(batch * n)) != EZPZ_OK) return rc;
-    if ((rc = F.jv.ensure(batch * std::max<size_t>(zj, 1))) != EZPZ_OK) return rc;
+    if ((rc = grow(F.x_int, batch * n)) != EZPZ_OK) return rc;
+    if ((rc = grow(F.jv, batch * std::max<size_t>(zj, 1))) != EZPZ_OK) return rc;
     if (!part_dev) {
-        if ((rc = F.part.ensure(batch * n)) != EZPZ_OK) return rc;
+        if ((rc = grow(F.part, batch * n)) != EZPZ_OK) return rc;
         part_dev = F.part.p;
     }
     // Small calls whose components fit the LDS layouts (LANE, or TEAM with its workspace in LDS) are ONE launch: the kernel gathers
@@ -151,6 +169,7 @@ int freedom_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* 
     const bool in_lds = F.lane || head0 + (size_t)F.ws * sizeof(double) <= 128 * 1024;
     const bool fused = fuse_enabled && in_lds && batch <= 64 && (uint64_t)batch * sys->counts.n_cons <= 4096;
     if (flagged) *flagged = false;
+    if ((rc = ordered()) != EZPZ_OK) return rc;
     if (!fused) {
         const uint32_t* var_of = reinterpret_cast<const uint32_t*>(sys->view.base + sys->view.o_var_of);
         const uint64_t total = (uint64_t)batch * n;
@@ -202,13 +221,13 @@ int freedom_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* 
             lds = head;
             const size_t per = (size_t)F.ws * sizeof(double);
             grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(batch, 1024), (4ull << 30) / per));
-            if ((rc = F.gws.ensure((size_t)grid * F.ws)) != EZPZ_OK) return rc;
+            if ((rc = grow(F.gws, (size_t)grid * F.ws)) != EZPZ_OK) return rc;
             a.gws = F.gws.p;
             if (F.comp0.n >= 96) {
                 // A big component (the system's largest; the others, if any, follow on the ordinary kernel): its pivoted QR as a chain of step launches over the whole device (freedom.hip.hpp),
                 // `grid` systems side by side, then the ordinary kernel for rank / null space / participation.
-                if ((rc = F.step_done.ensure(grid)) != EZPZ_OK) return rc;
-                if ((rc = F.step_tau.ensure(grid)) != EZPZ_OK) return rc;
+                if ((rc = grow(F.step_done, grid)) != EZPZ_OK) return rc;
+                if ((rc = grow(F.step_tau, grid)) != EZPZ_OK) return rc;
                 HIP_TRY(hipFuncSetAttribute((const void*)freedom_kernel<false>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 const uint32_t m = F.comp0.m, nc = F.comp0.n, ndiag = std::min(m, nc);
@@ -323,7 +342,7 @@ int freedom_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* 
                     hipLaunchKernelGGL(freedom_kernel<false>, dim3(nb), dim3(F.threads), lds, stream, fa);
                 }
                 HIP_TRY(hipGetLastError());
-                return EZPZ_OK;
+                return recorded();
             }
         }
         static std::atomic<size_t> raised_team[16];
@@ -339,7 +358,7 @@ int freedom_device(EzpzSystem* sys, const double* x_dev, size_t batch, uint8_t* 
         hipLaunchKernelGGL(freedom_kernel<false>, dim3(grid), dim3(F.threads), lds, stream, a);
     }
     HIP_TRY(hipGetLastError());
-    return EZPZ_OK;
+    return recorded();
 }
 
 // ---- FreedomAnalysis of a system the FRONTS serve, without the pivoted QR --------------------------------------------------------------
@@ -656,7 +675,7 @@ int ezpz_system_freedom_batch_device(EzpzSystem* sys, const double* x_dev, size_
     if (batch == 0) return EZPZ_OK;
     std::lock_guard<std::mutex> lock(sys->mu);
     EZPZ_ON_DEVICE(sys->device);
-    return freedom_device(sys, x_dev, batch, under_mask_dev, participation_dev, n_under_dev, (hipStream_t)stream);
+    return freedom_device(sys, x_dev, batch, under_mask_dev, participation_dev, n_under_dev, (hipStream_t)stream, false);
 }
 
 int ezpz_system_freedom_batch(EzpzSystem* sys, const double* x, size_t batch, uint8_t* under_mask,
@@ -693,7 +712,7 @@ int ezpz_system_freedom_batch(EzpzSystem* sys, const double* x, size_t batch, ui
         static thread_local unsigned long long t_seq = 0;
         const unsigned long long seq = ++t_seq;
         bool flagged = false;
-        if ((rc = freedom_device(sys, reinterpret_cast<const double*>(h), batch, hmask, hpart, nullptr, fstream, flag, seq, &flagged)) != EZPZ_OK) return rc;
+        if ((rc = freedom_device(sys, reinterpret_cast<const double*>(h), batch, hmask, hpart, nullptr, fstream, true, flag, seq, &flagged)) != EZPZ_OK) return rc;
         hipError_t q = hipSuccess;
         int spins = 0;
         if (flagged) {
@@ -715,7 +734,7 @@ int ezpz_system_freedom_batch(EzpzSystem* sys, const double* x, size_t batch, ui
         if (mask_poisoned(hmask, batch, n)) {
             // the resident QR gave up waiting for workgroups that never became resident (a co-tenant): once more by the chain of launches
             if (hip_debug()) std::fprintf(stderr, "[ezpz hip] the resident QR timed out -> the chain of launches\n");
-            if ((rc = freedom_device(sys, reinterpret_cast<const double*>(h), batch, hmask, hpart, nullptr, fstream, nullptr, 0, nullptr, true)) != EZPZ_OK) return rc;
+            if ((rc = freedom_device(sys, reinterpret_cast<const double*>(h), batch, hmask, hpart, nullptr, fstream, true, nullptr, 0, nullptr, true)) != EZPZ_OK) return rc;
             if (hipStreamSynchronize(fstream) != hipSuccess) {
                 (void)hipGetLastError();
                 return EZPZ_ERR_HIP;
@@ -727,13 +746,14 @@ int ezpz_system_freedom_batch(EzpzSystem* sys, const double* x, size_t batch, ui
     }
     if ((rc = F.x_in.ensure(batch * n)) != EZPZ_OK) return rc;
     if ((rc = F.mask.ensure(batch * n)) != EZPZ_OK) return rc;
+    if (batch * n > F.part.cap && (rc = F.order.before_overwrite()) != EZPZ_OK) return rc;  // (a device call may be writing it)
     if ((rc = F.part.ensure(batch * n)) != EZPZ_OK) return rc;
     HIP_TRY(hipMemcpy(F.x_in.p, x, batch * n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = freedom_device(sys, F.x_in.p, batch, F.mask.p, F.part.p, nullptr, nullptr)) != EZPZ_OK) return rc;
+    if ((rc = freedom_device(sys, F.x_in.p, batch, F.mask.p, F.part.p, nullptr, nullptr, true)) != EZPZ_OK) return rc;
     HIP_TRY(hipMemcpy(under_mask, F.mask.p, batch * n, hipMemcpyDeviceToHost));
     if (mask_poisoned(under_mask, batch, n)) {  // (as above: the resident QR timed out -> the chain of launches)
         if (hip_debug()) std::fprintf(stderr, "[ezpz hip] the resident QR timed out -> the chain of launches\n");
-        if ((rc = freedom_device(sys, F.x_in.p, batch, F.mask.p, F.part.p, nullptr, nullptr, nullptr, 0, nullptr, true)) != EZPZ_OK) return rc;
+        if ((rc = freedom_device(sys, F.x_in.p, batch, F.mask.p, F.part.p, nullptr, nullptr, true, nullptr, 0, nullptr, true)) != EZPZ_OK) return rc;
         HIP_TRY(hipMemcpy(under_mask, F.mask.p, batch * n, hipMemcpyDeviceToHost));
     }
     if (participation) HIP_TRY(hipMemcpy(participation, F.part.p, batch * n * sizeof(double), hipMemcpyDeviceToHost));

@@ -136,20 +136,12 @@ struct DevBuf {
     }
 };
 
-// A `positions` list of driven constraints whose device tables a system keeps for a caller that repeats it (touched under the
-// system's launch_mu), and the completion of the last launch that read the tables.  The launches that read them run one behind the
-// other whatever their streams (order_behind, then record), so that one event is what a call with another list waits for before it
-// overwrites them.  `take_part` = false: a launch that stays out of the event (the frontal sensitivity route while its stream is
+// The completion of the last launch that used some per-system device state.  The launches that use it run one behind the other
+// whatever their streams (order_behind, then record); whoever replaces the state from the host waits for the event first
+// (before_overwrite).  `take_part` = false: a launch that stays out of the event (the frontal sensitivity route while its stream is
 // being captured: front_sens.hip); everybody else takes part under capture too.
-struct KeptList {
-    std::vector<uint32_t> positions;
-    bool valid = false;
+struct LaunchOrder {
     hipEvent_t done = nullptr;
-    bool same(const uint32_t* p, size_t n) const { return valid && positions.size() == n && std::equal(p, p + n, positions.begin()); }
-    void keep(const uint32_t* p, size_t n) {
-        positions.assign(p, p + n);
-        valid = true;
-    }
     int before_overwrite() {
         if (done) HIP_TRY(hipEventSynchronize(done));
         return EZPZ_OK;
@@ -162,8 +154,24 @@ struct KeptList {
         if (take_part) HIP_TRY(hipEventRecord(done, stream));
         return EZPZ_OK;
     }
-    ~KeptList() {
+    LaunchOrder() = default;
+    LaunchOrder(const LaunchOrder&) = delete;
+    LaunchOrder& operator=(const LaunchOrder&) = delete;
+    ~LaunchOrder() {
         if (done) (void)hipEventDestroy(done);
+    }
+};
+
+// A `positions` list of driven constraints whose device tables a system keeps for a caller that repeats it (touched under the
+// system's launch_mu), and the completion of the last launch that read the tables: one event is what a call with another list waits
+// for before it overwrites them.
+struct KeptList : LaunchOrder {
+    std::vector<uint32_t> positions;
+    bool valid = false;
+    bool same(const uint32_t* p, size_t n) const { return valid && positions.size() == n && std::equal(p, p + n, positions.begin()); }
+    void keep(const uint32_t* p, size_t n) {
+        positions.assign(p, p + n);
+        valid = true;
     }
 };
 
@@ -374,6 +382,9 @@ struct EzpzSystem {
         DevBuf<uint32_t> count;
         std::vector<FreedomComp> host_comps;  // what `comps` and the items of `lists` hold (redundancy.hip derives its row tables)
         std::vector<uint32_t> host_items;
+        // x_int, jv, part, gws, step_tau and step_done are one of each per system: the launches of freedom_device (freedom.hip) that
+        // use them run one behind the other, whatever their streams
+        LaunchOrder order;
     } freedom;
     // ezpz_system_redundancy (redundancy.hip): its RedundancyPlan -- row tables beside the freedom lists, workspace, the host
     // entry's buffers (built on first use; touched under mu, like `freedom`)

@@ -498,7 +498,8 @@ int ezpz_solve(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_id
  * of them give up waiting (workgroups that never became resident beside another process's or stream's kernels), the host entries
  * run the analysis once more as a chain of launches that wait for nobody (EZPZ_ERR_HIP only if that fails too), and the
  * asynchronous _device entry marks the system: 0xFF in every byte of its mask, 0xFFFFFFFF as its count -- as a timed-out grid
- * team's solve reports EZPZ_ITERATIONS_TEAM_TIMEOUT. */
+ * team's solve reports EZPZ_ITERATIONS_TEAM_TIMEOUT.  Launches of ezpz_system_freedom_batch[_device] on one system run one behind
+ * the other whatever their streams: they share the system's gathered values, Jacobian and workspace. */
 int ezpz_solve_analysis(const EzpzConstraint* reqs, size_t n_reqs, const uint32_t* var_ids, const double* guesses,
                         size_t n_guesses, const EzpzConfig* cfg, double* x_out, uint64_t* unsat_ids,
                         EzpzWarning* warn_buf, size_t warn_cap, EzpzOutcome* out, uint32_t* under_out,
