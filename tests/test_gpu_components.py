@@ -442,7 +442,7 @@ def test_verdicts_not_waited_for_on_two_streams(E):
 
 def test_random_linear_classes_on_the_kernels_that_do_not_wait(E):
     """The generator splits a linear class's `solve` into the factorisation of J^T J + lambda I (lambda only: once per launch, in
-    scalar registers) and the substitutions (comp_program.cpp: factor / solve_f) for the kernels that do not wait for the LM
+    scalar registers) and the substitutions (comp_source.cpp: factor / solve_f) for the kernels that do not wait for the LM
     control's verdicts.  gen_big_problem.py's two classes are a 2 x 2 and a 1 x 1 matrix; here: random little systems of the nine
     LINEAR kinds (3 ... 8 variables, 2 ... 7 constraints: several elimination levels, fill, free variables, duplicated and
     contradictory constraints -- whose systems do not converge in two iterations and go through the redo list), each replicated 130 ...

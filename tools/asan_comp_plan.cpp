@@ -1,6 +1,6 @@
-// g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Iezpz_amd/csrc -Iinclude tools/asan_comp_plan.cpp ezpz_amd/csrc/comp_program.cpp ezpz_amd/csrc/program.cpp -o /tmp/asan_comp && /tmp/asan_comp
-// round 6: comp_plan_build (comp_program.cpp: classes, slots, the source of the run-time compiled kernels, the per-wavefront ranges of
-// the rows the kernels that do not wait for verdicts move as whole lines) under ASan + UBSan on random BLOCK systems: blocks of
+// g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Iezpz_amd/csrc -Iinclude tools/asan_comp_plan.cpp ezpz_amd/csrc/comp_program.cpp ezpz_amd/csrc/comp_source.cpp ezpz_amd/csrc/program.cpp -o /tmp/asan_comp && /tmp/asan_comp
+// round 6: comp_plan_build (comp_program.cpp: classes, slots, the per-wavefront ranges of the rows the kernels that do not wait for
+// verdicts move as whole lines; comp_source.cpp: the source of the run-time compiled kernels) under ASan + UBSan on random BLOCK systems: blocks of
 // 1-6 variables drawn from a few random topologies of linear and non-linear kinds, 1 ... 60 000 blocks, shuffled or in order.
 #include <algorithm>
 #include <cstdio>

@@ -1,6 +1,6 @@
-// g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Iezpz_amd/csrc -Iinclude tools/asan_lane_plan.cpp ezpz_amd/csrc/comp_program.cpp ezpz_amd/csrc/program.cpp -o /tmp/asan_lane && /tmp/asan_lane
+// g++ -std=c++17 -O1 -g -fsanitize=address,undefined -Iezpz_amd/csrc -Iinclude tools/asan_lane_plan.cpp ezpz_amd/csrc/comp_program.cpp ezpz_amd/csrc/comp_source.cpp ezpz_amd/csrc/program.cpp -o /tmp/asan_lane && /tmp/asan_lane
 // round 4: "lane plans 1399, with a wave source 1235, with the elimination across lanes 1235", no reports.
-// lane_plan_build (comp_program.cpp: lane class, wave tables, the elimination across lanes) under ASan + UBSan on random small systems
+// lane_plan_build (comp_program.cpp; comp_source.cpp: lane class, wave tables, the elimination across lanes) under ASan + UBSan on random small systems
 #include <cstdio>
 #include <cstring>
 #include <random>
