@@ -118,6 +118,8 @@ EXPORTS = [
     "ezpz_system_set_params_route",
     "ezpz_system_set_sensitivity_route", "ezpz_debug_front_sens_tables",
     "ezpz_default_redundancy_config", "ezpz_system_redundancy", "ezpz_system_redundancy_device",
+    "ezpz_constraint_measure", "ezpz_system_measure", "ezpz_system_measure_device", "ezpz_system_measure_response",
+    "ezpz_system_measure_response_device", "ezpz_system_measure_vjp", "ezpz_system_measure_vjp_device",
 ]
 
 _lib = None
@@ -160,6 +162,20 @@ def lib():
     L.ezpz_system_redundancy.argtypes = [vp, vp, sz, C.POINTER(CRedundancyConfig), vp, vp, vp, vp, sz, vp]
     L.ezpz_system_redundancy_device.restype = C.c_int
     L.ezpz_system_redundancy_device.argtypes = [vp, vp, sz, C.POINTER(CRedundancyConfig), vp, vp, vp, vp, sz, vp, vp]
+    L.ezpz_constraint_measure.restype = C.c_int
+    L.ezpz_constraint_measure.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int)]
+    L.ezpz_system_measure.restype = C.c_int
+    L.ezpz_system_measure.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp]
+    L.ezpz_system_measure_device.restype = C.c_int
+    L.ezpz_system_measure_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
+    L.ezpz_system_measure_response.restype = C.c_int
+    L.ezpz_system_measure_response.argtypes = [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.ezpz_system_measure_response_device.restype = C.c_int
+    L.ezpz_system_measure_response_device.argtypes = [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.ezpz_system_measure_vjp.restype = C.c_int
+    L.ezpz_system_measure_vjp.argtypes = [vp, vp, sz, vp, vp, sz, vp]
+    L.ezpz_system_measure_vjp_device.restype = C.c_int
+    L.ezpz_system_measure_vjp_device.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
     L.ezpz_current_device.restype = C.c_int
     L.ezpz_current_device.argtypes = []
     L.ezpz_host_register.restype = C.c_int

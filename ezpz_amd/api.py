@@ -998,6 +998,112 @@ class System:
             raise NonLinearSystemError(rc)
         return {f: getattr(p, f) for f, _ in CSensitivityPlan._fields_}
 
+    # ---- reference dimensions (ezpz_system_measure and its siblings) ----------------------------------------------------------
+    def _measure_x(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim == 0 or x.shape[-1] != self.n_vars:
+            raise ValueError(f"x: expected [..., {self.n_vars}], got {x.shape}")
+        return x, x.shape[:-1], int(np.prod(x.shape[:-1], dtype=np.int64))
+
+    def measure(self, x: np.ndarray, records, want_grad: bool = False, want_flags: bool = False):
+        """`ezpz_system_measure`: the reference dimensions `records` (measurable constraint records: only kind, tag and ids are read)
+        at the values x [..., n_vars] -- any leading shape, e.g. [steps, batch, n_vars] from a sweep, which the outputs keep.
+        Returns m [..., n_meas] in the units of the records' `param` field; with want_grad also grad [..., n_meas, 8] (d m / d
+        x[ids[slot]]), with want_flags also flags [..., n_meas] uint8 (bit 0: the residual's guard fired, m and grad are 0; bit 1:
+        a gradient guard fired) -- as a tuple in that order."""
+        x, lead, batch = self._measure_x(x)
+        recs = stack_records(records)
+        k = len(recs)
+        m = np.zeros(lead + (k,))
+        grad = np.zeros(lead + (k, 8)) if want_grad else None
+        flags = np.zeros(lead + (k,), np.uint8) if want_flags else None
+        rc = lib().ezpz_system_measure(self._h, recs.ctypes.data if k else None, k, x.ctypes.data if x.size else None, batch,
+                                       m.ctypes.data if m.size else None, flags.ctypes.data if want_flags and flags.size else None,
+                                       grad.ctypes.data if want_grad and grad.size else None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        if not (want_grad or want_flags):
+            return m
+        return (m,) + ((grad,) if want_grad else ()) + ((flags,) if want_flags else ())
+
+    def measure_response(self, x: np.ndarray, records, S: np.ndarray, tol=None):
+        """`ezpz_system_measure_response`: D [..., n_meas, n_param] = how each reference dimension answers to each driving dimension,
+        from S [..., n_param, n_vars] (`param_sensitivity` at the same x).  With tol [n_param] (non-negative) also the tolerance
+        stack-up: returns (D, worst [..., n_meas], rss [..., n_meas])."""
+        x, lead, batch = self._measure_x(x)
+        recs = stack_records(records)
+        k = len(recs)
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.ndim < 2 or S.shape[:-2] != lead or S.shape[-1] != self.n_vars:
+            raise ValueError(f"S: expected {lead + ('n_param', self.n_vars)}, got {S.shape}")
+        n_param = S.shape[-2]
+        D = np.zeros(lead + (k, n_param))
+        if tol is not None:
+            tol = np.ascontiguousarray(tol, dtype=np.float64)
+            if tol.shape != (n_param,):
+                raise ValueError(f"tol: expected shape ({n_param},), got {tol.shape}")
+            worst, rss = np.zeros(lead + (k,)), np.zeros(lead + (k,))
+        rc = lib().ezpz_system_measure_response(self._h, recs.ctypes.data if k else None, k, x.ctypes.data if x.size else None,
+                                                S.ctypes.data if S.size else None, n_param, batch,
+                                                tol.ctypes.data if tol is not None else None, D.ctypes.data if D.size else None,
+                                                worst.ctypes.data if tol is not None else None,
+                                                rss.ctypes.data if tol is not None else None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return (D, worst, rss) if tol is not None else D
+
+    def measure_vjp(self, x: np.ndarray, records, grad_m: np.ndarray) -> np.ndarray:
+        """`ezpz_system_measure_vjp`: grad_x [..., n_vars] = grad_m [..., n_meas] pulled back through `measure` at x."""
+        x, lead, batch = self._measure_x(x)
+        recs = stack_records(records)
+        k = len(recs)
+        grad_m = np.ascontiguousarray(grad_m, dtype=np.float64)
+        if grad_m.shape != lead + (k,):
+            raise ValueError(f"grad_m: expected {lead + (k,)}, got {grad_m.shape}")
+        gx = np.zeros(x.shape)
+        rc = lib().ezpz_system_measure_vjp(self._h, recs.ctypes.data if k else None, k, x.ctypes.data if x.size else None,
+                                           grad_m.ctypes.data if grad_m.size else None, batch, gx.ctypes.data if gx.size else None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return gx
+
+    def measure_device(self, x_ptr: int, records, batch: int, m_ptr: int, flags_ptr: int = 0, grad_ptr: int = 0, stream: int = 0) -> None:
+        """Device pointers and a hipStream_t handle; enqueue only (a record list other than the last one is packed and uploaded
+        first).  `records` stays a host array."""
+        recs = stack_records(records)
+        rc = lib().ezpz_system_measure_device(self._h, recs.ctypes.data if len(recs) else None, len(recs), x_ptr or None, batch,
+                                              m_ptr or None, flags_ptr or None, grad_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+    def measure_response_device(self, x_ptr: int, records, S_ptr: int, n_param: int, batch: int, D_ptr: int, tol_ptr: int = 0,
+                                worst_ptr: int = 0, rss_ptr: int = 0, stream: int = 0) -> None:
+        """Device pointers (tol included) and a hipStream_t handle; enqueue only."""
+        recs = stack_records(records)
+        rc = lib().ezpz_system_measure_response_device(self._h, recs.ctypes.data if len(recs) else None, len(recs), x_ptr or None,
+                                                       S_ptr or None, n_param, batch, tol_ptr or None, D_ptr or None,
+                                                       worst_ptr or None, rss_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+    def measure_vjp_device(self, x_ptr: int, records, grad_m_ptr: int, batch: int, grad_x_ptr: int, stream: int = 0) -> None:
+        """Device pointers and a hipStream_t handle; enqueue only."""
+        recs = stack_records(records)
+        rc = lib().ezpz_system_measure_vjp_device(self._h, recs.ctypes.data if len(recs) else None, len(recs), x_ptr or None,
+                                                  grad_m_ptr or None, batch, grad_x_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+
+def constraint_measure(record, x):
+    """`ezpz_constraint_measure`: (m, grad [n_ids], flags) of one measurement record at the values x indexed by the record's ids;
+    (0.0, an empty grad, 0) for a record that is not measurable.  Host only."""
+    rec = stack_records([record])
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    m, g, fl = C.c_double(0.0), np.zeros(8), C.c_int(0)
+    n_ids = lib().ezpz_constraint_measure(rec.ctypes.data, x.ctypes.data, C.byref(m), g.ctypes.data, C.byref(fl))
+    return m.value, g[:n_ids], fl.value
+
 
 def constraint_param_derivative(record, x):
     """`ezpz_constraint_param_derivative`: (g [rows] = weight * d residual / d param at the values x indexed by the record's

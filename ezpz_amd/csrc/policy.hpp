@@ -35,6 +35,21 @@ inline bool debug_topic(const char* topic) {
 // K / 2 times the work of one right-hand side's two substitutions on a front of K pivots; not yet measured on a device: DESIGN.md 3g.)
 constexpr uint32_t kFrontSensMinRhsPerItem = 8;
 
+// Reference dimensions (measure.hip): a system's row x[b][:] is staged into LDS (ROW) between these numbers of variables, and
+// gathered from global memory (DIRECT) below and above.  Properties of one workgroup's LDS and of a row's cache lines, not scaled.
+// Measured (profiles/measure_rate.txt, ROW's time over DIRECT's): rows of 48 variables 1.06-1.09 however often the list gathers
+// them, 300 a tie (0.97), 1024 0.99 at one gather per variable and 0.82-0.69 at 4-32, 2048 0.92 on scattered ids but the block
+// system's contiguous ids at 2000 1.09, from 3072 1.16-1.94.  Both thresholds lie between measured points: 512 between
+// the tie at 300 and ROW at 1024, 1536 between ROW at 1024 and the split at 2000 / 2048 (which gives the block system, the workload
+// with the most bytes, its faster placement).  kMeasureRowLdsMaxVars is what the ROW kernel can hold at all (56 KiB of a launch that
+// stays under the 64 KiB a kernel gets without asking): EZPZ_MEASURE_ROUTE=row forces ROW up to there, =direct forces DIRECT
+// everywhere (tools/measure_rate.py measures both sides of the thresholds that way).
+constexpr uint32_t kMeasureRowMinVars = 512;
+constexpr uint32_t kMeasureRowMaxVars = 1536;
+constexpr uint32_t kMeasureRowLdsMaxVars = 7168;
+constexpr uint32_t kMeasureRowGroupDoubles = 2048;  // several small systems per workgroup: up to this many doubles of rows at a time
+constexpr uint32_t kMeasureTableLdsBytes = 16 * 1024;  // the record table rides in LDS up to this size (455 records)
+
 inline EzpzLaunchPolicy launch_policy_for(int compute_units) {
     const uint64_t cus = (uint64_t)std::max(compute_units, 1);
     EzpzLaunchPolicy p{};

@@ -7,6 +7,7 @@
 //   pipeline.cpp  host-pointer entry points: the one-call path (resident kernels), zero-copy, the three-stage pipeline
 //   freedom.hip   FreedomAnalysis
 //   redundancy.hip  redundant / conflicting constraints and conflict groups (the row-space counterpart, on freedom.hip's components)
+//   measure.hip   reference dimensions: a record list measured at given values, its response to S, stack-up and vjp
 //   driven.cpp    the entries that take a `positions` list of driven constraints: the list check, and the one call path behind
 //                 params.hip and sweep.hip (driven_params.hpp); sensitivity.hip and front_sens.hip keep their lists in a KeptList
 //   mixed.hip, multi.cpp, solve.cpp  on top of the C ABI (heterogeneous batches, several devices, solve / solve_inner)
@@ -171,6 +172,18 @@ struct KeptList : LaunchOrder {
     bool same(const uint32_t* p, size_t n) const { return valid && positions.size() == n && std::equal(p, p + n, positions.begin()); }
     void keep(const uint32_t* p, size_t n) {
         positions.assign(p, p + n);
+        valid = true;
+    }
+};
+
+// KeptList's sibling for a list of measurement records (measure.hip): what is compared is the packed records -- kind | tag | ids, the
+// only bytes of a record the entries read (measure_tables.hpp: measure_pack_records) -- in place of positions.
+struct KeptRecords : LaunchOrder {
+    std::vector<uint32_t> words;
+    bool valid = false;
+    bool same(const std::vector<uint32_t>& w) const { return valid && words == w; }
+    void keep(std::vector<uint32_t>&& w) {
+        words = std::move(w);
         valid = true;
     }
 };
@@ -389,6 +402,9 @@ struct EzpzSystem {
     // ezpz_system_redundancy (redundancy.hip): its RedundancyPlan -- row tables beside the freedom lists, workspace, the host
     // entry's buffers (built on first use; touched under mu, like `freedom`)
     std::shared_ptr<void> redundancy;
+    // ezpz_system_measure and its siblings (measure.hip): the MeasurePlan -- the KeptRecords of the last call's record list, its
+    // device tables, the gradient workspace and the host entries' buffers (built on first use; touched under mu)
+    std::shared_ptr<void> measure;
     ~EzpzSystem() {
         if (dev_program) (void)hipFree(dev_program);
         if (dev_grid_blob) (void)hipFree(dev_grid_blob);

@@ -10,11 +10,18 @@ Forward is `System.solve_batch_params_device`; backward evaluates `System.param_
 converged solve is a root of the constraints, which the start selects (which root, on a system that has several) but does not
 move -- dx*/dx0 is zero wherever it exists; on an under-determined system the start does slide the answer along the free
 directions, which this layer does not differentiate (it returns None for x0, like for every non-tensor argument).
+
+`measure` reads reference dimensions back inside the graph:
+
+    m = measure(system, x, records)                      # [..., n_meas] of x [..., n_vars], on the current stream
+    measure(solve_params(system, x0, positions, params), records).sum().backward()   # fills params.grad
+
+Forward is `System.measure_device`, backward `System.measure_vjp_device` (a per-variable sum in a fixed order: no atomics).
 """
 import numpy as np
 import torch
 
-from .api import Config
+from .api import Config, stack_records
 from ._lib import STATUS_DTYPE
 
 
@@ -49,6 +56,42 @@ class _SolveParams(torch.autograd.Function):
                                             stream=stream)
         grad_params = torch.bmm(S, grad_x.contiguous().unsqueeze(2)).squeeze(2)
         return None, None, None, grad_params, None, None
+
+
+class _Measure(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, system, x, records):
+        if not x.is_cuda or x.dtype != torch.float64 or x.dim() < 1 or x.shape[-1] != system.n_vars:
+            raise ValueError(f"measure: x must be a float64 tensor [..., {system.n_vars}] on the system's device")
+        recs = stack_records(records)
+        xc = x.detach().contiguous()
+        lead = tuple(xc.shape[:-1])
+        batch = int(np.prod(lead, dtype=np.int64))
+        m = torch.zeros(lead + (len(recs),), dtype=torch.float64, device=xc.device)
+        flags = torch.zeros(lead + (len(recs),), dtype=torch.uint8, device=xc.device)
+        stream = torch.cuda.current_stream(xc.device).cuda_stream
+        system.measure_device(xc.data_ptr(), recs, batch, m.data_ptr(), flags_ptr=flags.data_ptr(), stream=stream)
+        ctx.system, ctx.recs, ctx.batch = system, recs, batch
+        ctx.save_for_backward(xc)
+        ctx.mark_non_differentiable(flags)
+        return m, flags
+
+    @staticmethod
+    def backward(ctx, grad_m, _grad_flags):
+        (xc,) = ctx.saved_tensors
+        gm = grad_m.contiguous()
+        gx = torch.zeros_like(xc)
+        stream = torch.cuda.current_stream(xc.device).cuda_stream
+        ctx.system.measure_vjp_device(xc.data_ptr(), ctx.recs, gm.data_ptr(), ctx.batch, gx.data_ptr(), stream=stream)
+        return None, gx, None
+
+
+def measure(system, x, records, return_flags=False):
+    """m [..., n_meas] = the reference dimensions `records` of `system` at x [..., n_vars] (`System.measure_device` on the current
+    stream); differentiable in x (`System.measure_vjp_device`), so measure(solve_params(system, x0, positions, params),
+    records).sum().backward() fills params.grad.  return_flags: also the flags [..., n_meas] uint8."""
+    m, flags = _Measure.apply(system, x, records)
+    return (m, flags) if return_flags else m
 
 
 def solve_params(system, x0, positions, params, config=None, lam=None, return_status=False):

@@ -556,6 +556,73 @@ int ezpz_system_redundancy_device(EzpzSystem* sys, const double* x_dev, size_t b
                                   uint8_t* con_status_dev, uint8_t* row_status_dev, uint32_t* rank_dev, const uint32_t* focus,
                                   size_t n_focus, uint8_t* group_dev, void* stream);
 
+/* ---- Reference dimensions: measure, gradient, response to the driving dimensions (a project extension: the reference has none) ----
+ * A MEASUREMENT RECORD is an EzpzConstraint of which only kind, tag and ids are read; param, weight, priority and flags are
+ * ignored.  It must be MEASURABLE: ezpz_constraint_has_param(record) != 0 -- the ten kinds with a length or a value, and the three
+ * angle kinds with tag EZPZ_ANGLE_OTHER_DEG or EZPZ_ANGLE_OTHER_RAD.  Its ids index the system's variables, in the caller's order;
+ * it need not be, and normally is not, one of the system's constraints: it is a measurement of the solution, not a condition on it.
+ * m(record, x) is the value of `param` at which the record's unweighted residual vanishes at x -- for the two kinds with two rows
+ * and one parameter (ArcRadius, ArcLength; PointsAtAngle's rows vanish together) the param that minimises the sum of the squares
+ * of the two rows -- in the units of the `param` field: degrees where the tag says degrees.  XV(i) = x[ids[i]]:
+ *   Fixed, CircleRadius                   the variable                                                       no guard
+ *   VerticalDistance, HorizontalDistance  XV(1) - XV(3), XV(0) - XV(2)                                       no guard
+ *   Distance                              mag(p0 - p1)                                                       none on the value
+ *   ArcRadius                             (mag(c - start) + mag(c - end)) / 2                                none on the value
+ *   PointLineDistance, Vertical..., Horizontal...   the residual's own expression without `- param`          the residual's
+ *   LinesAtAngle, ArcAngle, PointsAtAngle theta = atan2(cross(u, v), dot(u, v)) in (-pi, pi], u and v the vectors the residual
+ *                                         uses; x 180 / pi for the DEG tag                                   the residual's
+ *   ArcLength                             mag(u) * rem_euclid(theta(u, w), 2 pi), u = start - c, w = end - c the residual's (r2 <= EPS^2)
+ * in the residual's operand order.  The ArcLength value lies in [0, 2 pi r): an arc runs counter-clockwise from start to end.  A
+ * guard is the residual's guard of the kind, same comparison, same operands; where it fires m = 0, every gradient slot is 0 and
+ * flag bit 0 is set -- exactly where the residual reports degenerate.  grad[slot] = d m / d x[ids[slot]] for slot < the kind's
+ * number of ids; the slots from there up to 7 are +0.0.  Gradient guard, flag bit 1, with m still valid: Distance with dist < EPS,
+ * and each row of ArcRadius on its own (the guards of the Jacobian's Distance rows); the guarded row contributes zeros.  The
+ * branch cuts are documented, not smoothed: theta = +-pi for the angle kinds (opposite arms give +pi), theta = 0 for ArcLength;
+ * an arc whose end lies on its centre has no finite gradient.
+ * ezpz_constraint_measure (host only, no device): m, grad[8] and the flags of one record at the values x (indexed by c->ids; each
+ * output optional).  Returns the kind's number of ids for a measurable record, 0 otherwise or on NULL c / x.
+ * ezpz_system_measure[_device]: `batch` value vectors x (AoS [batch][n_vars], normally a solve's or a sweep's answers) against
+ * records[0 .. n_meas): m_out [batch][n_meas]; flags_out [batch][n_meas] bytes and grad_out [batch][n_meas][8] optional (NULL).
+ * ezpz_system_measure_response[_device]: with S [batch][n_param][n_vars] as ezpz_system_param_sensitivity_device wrote it,
+ *     D[b, i, j] = sum over slot of grad[b, i, slot] * S[b, j, ids_i[slot]]      slots ascending, left to right from the first product
+ * D_out [batch][n_meas][n_param]: how reference dimension i answers to driving dimension j.  With tol [n_param] (optional) the
+ * tolerance stack-up, worst_out and rss_out [batch][n_meas] (both or neither, only with tol):
+ *     worst[b, i] = sum_j |D[b, i, j]| * tol[j]        rss[b, i] = sqrt(sum_j (D[b, i, j] * tol[j])^2)       j ascending from +0.0
+ * ezpz_system_measure_vjp[_device]: grad_x_out [batch][n_vars],
+ *     grad_x[b, v] = sum of grad_m[b, i] * grad[b, i, slot] over the pairs (i, slot) with ids_i[slot] == v, ascending (i, slot) from +0.0
+ * +0.0 for a variable no record names: the vector-Jacobian product that makes measure(solve(...)) differentiable end to end.
+ * A flagged measurement contributes zeros.  NaN in S propagates: a system whose sensitivity status was 1 gives NaN responses.
+ * m[b, i], grad[b, i, :] and D[b, i, :] depend on x_b, S_b and record i alone: bit-identical from run to run, whatever the batch,
+ * the system's place in it, the rest of the list and its order; grad_x depends on the list's order only through the order of its
+ * sum.  No sum uses atomics; no workgroup waits for another.
+ * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: a record that is not measurable, an id >= n_vars,
+ * records NULL with n_meas > 0, a required pointer NULL with a non-empty call, worst_out / rss_out without tol or only one of the
+ * two, a negative or non-finite tol (host form).  EZPZ_ERR_TOO_LARGE: more than 2^20 records.  batch == 0, n_meas == 0, or
+ * n_param == 0 for the response: EZPZ_OK, nothing written -- after the checks above that need no values: a list with a record that
+ * is not measurable, an id >= n_vars, worst_out / rss_out without tol, or a bad tol is EZPZ_ERR_INVALID_ARGUMENT even with batch == 0.
+ * `records` is host memory in both forms.  The _device forms take device pointers (tol included) and only enqueue on `stream`; a
+ * list other than the system's last one is first checked, packed and uploaded behind the last launch that read the tables (repeat
+ * the list, and calls only enqueue), as is the vjp's variable -> (i, slot) table the first time a list needs it, and a workspace
+ * that has to grow.  Launches of these entries on one EzpzSystem run one behind the other whatever their streams; stream capture
+ * follows ezpz_system_redundancy_device.  A row x_b of 512 to 1536 variables is staged in LDS, shorter and longer ones are gathered
+ * from global memory; EZPZ_MEASURE_ROUTE=row / direct forces either placement (row: up to 7168 variables) -- same bits.
+ * Staging loads 16 bytes per lane: an x_dev that is not 16-byte aligned is gathered from global memory whatever its size and
+ * whatever EZPZ_MEASURE_ROUTE says; a grad_out_dev that is not 16-byte aligned is written in 8-byte stores.  Same bits again. */
+int ezpz_constraint_measure(const EzpzConstraint* c, const double* x, double* m_out, double grad_out[8], int* flags);
+int ezpz_system_measure(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x, size_t batch, double* m_out,
+                        uint8_t* flags_out, double* grad_out);
+int ezpz_system_measure_device(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x_dev, size_t batch,
+                               double* m_out_dev, uint8_t* flags_out_dev, double* grad_out_dev, void* stream);
+int ezpz_system_measure_response(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x, const double* S,
+                                 size_t n_param, size_t batch, const double* tol, double* D_out, double* worst_out, double* rss_out);
+int ezpz_system_measure_response_device(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x_dev,
+                                        const double* S_dev, size_t n_param, size_t batch, const double* tol_dev, double* D_out_dev,
+                                        double* worst_out_dev, double* rss_out_dev, void* stream);
+int ezpz_system_measure_vjp(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x, const double* grad_m,
+                            size_t batch, double* grad_x_out);
+int ezpz_system_measure_vjp_device(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x_dev,
+                                   const double* grad_m_dev, size_t batch, double* grad_x_out_dev, void* stream);
+
 /* ---- ezpz::solve for a batch (new; SURVEY.md 8f #3: priority tiers + weights end-to-end on device batches) --------
  * `batch` systems share the request list and differ in their guesses (x0 AoS [batch][n_vars], id == index).  Per
  * system exactly the semantics of ezpz_solve: LineSide / CircleSide inferred from that system's own guesses
