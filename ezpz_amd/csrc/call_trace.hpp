@@ -31,6 +31,9 @@ enum CallStage : uint32_t {
     // ezpz_system_redundancy_device (redundancy.hip)
     REDUNDANCY_PREPARED = 40,  // something blocking first: tables built, a focus list other than the last one's, a buffer that had to grow
     REDUNDANCY_LAUNCHED = 41,  // gather, evaluation and the analysis kernel enqueued
+    REDUNDANCY_PLACED_LANE = 42,         // ... the analysis with one lane per (system, component)
+    REDUNDANCY_PLACED_TEAM_LDS = 43,     // ... or one workgroup per system, its workspace in LDS
+    REDUNDANCY_PLACED_TEAM_GLOBAL = 44,  // ... or in global memory
     // ezpz_system_measure_device and its siblings (measure.hip)
     MEASURE_TABLE_UPLOADED = 50,  // a record list other than the system's last one (or its CSR, first asked for): waited, packed, copied
     MEASURE_LAUNCHED = 51,        // the entry's kernels enqueued

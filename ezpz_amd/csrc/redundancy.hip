@@ -210,6 +210,7 @@ int redundancy_device(EzpzSystem* sys, const double* x_dev, size_t batch, const 
         hipLaunchKernelGGL(redundancy_kernel<false>, dim3(grid), dim3(threads), lds, stream, a);
     HIP_TRY(hipGetLastError());
     call_stamp(REDUNDANCY_LAUNCHED);
+    call_stamp(lane ? REDUNDANCY_PLACED_LANE : global_ws ? REDUNDANCY_PLACED_TEAM_GLOBAL : REDUNDANCY_PLACED_TEAM_LDS);
     return R.focus.record(stream);
 }
 

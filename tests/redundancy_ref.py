@@ -198,12 +198,240 @@ CASES["sketch24"] = (sketch, (24, 5, 0, 3))          # TEAM, workspace in LDS, m
 CASES["sketch24:dropped"] = (sketch, (24, 5, 10, 3))  # ... fewer rows than variables
 CASES["sketch150"] = (sketch, (150, 7, 0, 3))        # TEAM, workspace in global memory
 
+# ---- drawn inputs: every placement and batch grouping (tests/test_gpu_redundancy.py: fuzz, grouping, grid loop) ------------------
+def relabel(recs, perm):
+    """The records with variable v renamed perm[v]."""
+    out = O.stack(recs).copy()
+    perm = np.asarray(perm, dtype=np.uint32)
+    for c in out:
+        k = O.KIND_NUM_IDS[int(c["kind"])]
+        c["ids"][:k] = perm[c["ids"][:k]]
+    return out
+
+
+def components(recs, n_vars):
+    """[(m, n)] of the connected components of the Jacobian's row / variable graph (O.nonzeroes: the variables a row depends on,
+    fewer than the record names for the axis-aligned kinds), by union-find: what csrc/freedom.hip: build_freedom finds,
+    restated.  A variable in no row is no component."""
+    parent = list(range(n_vars))
+
+    def find(v):
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+
+    rows = [[int(v) for v in row] for c in recs for row in O.nonzeroes(c)]
+    for row in rows:
+        for v in row[1:]:
+            parent[find(v)] = find(row[0])
+    m, n = {}, {}
+    for row in rows:
+        m[find(row[0])] = m.get(find(row[0]), 0) + 1
+    for v in {v for row in rows for v in row}:
+        n[find(v)] = n.get(find(v), 0) + 1
+    return [(m[k], n[k]) for k in sorted(m)]
+
+
+LANE, TEAM_LDS, TEAM_GLOBAL = "lane", "team_lds", "team_global"
+
+
+def component_ws(m, n, shared, with_l):
+    """csrc/redundancy.hip.hpp: component_ws, restated."""
+    pm = min(m, n)
+    ld = ((n + 1) | 1) if shared else n + 1
+    return m * ld + m + 3 * pm + (pm * pm if with_l else 0)
+
+
+def placement(recs, n_vars, with_focus):
+    """Where csrc/redundancy.hip: redundancy_device runs the call, restated: (placement, systems per workgroup, threads, largest n).
+    LANE while the largest private workspace is at most 64 doubles; else one workgroup per system, the workspace in LDS while it
+    fits 128 KiB beside the 17 doubles in front of it."""
+    comps = components(recs, n_vars)
+    max_n = max(n for _, n in comps)
+    if max(component_ws(m, n, False, with_focus) for m, n in comps) <= 64:
+        return LANE, (1 if len(comps) >= 128 else 128 // len(comps)), 128, max_n
+    ws = max(component_ws(m, n, True, with_focus) for m, n in comps)
+    return (TEAM_LDS if (17 + ws) * 8 <= 128 * 1024 else TEAM_GLOBAL), 1, (1024 if max_n > 64 else 256), max_n
+
+
+REPEAT_WEIGHTS = (1.0, 2.5, 0.5)
+
+
+def mosaic(sizes, seed, shuffle=True, blocks=()):
+    """Several components of different sizes in one system.  A size of 1 is one fixed variable, any other size a
+    gen.connected_sketch of that many points at its polished values, each on a variable range of its own; three records of every
+    part (drawn) come again: the first as it is, the second with its parameter moved by 0.3 where that offsets the residual, the
+    third as it is, each with a weight from REPEAT_WEIGHTS.  `blocks`: ready parts (recs, n_vars, x [n_vars]) taken as they are.  The
+    record list is permuted, so the components' rows interleave in request order; `origin` [(part, record of the part)] says where
+    every record came from.  The focus list: the first six constraints the reference calls redundant or conflicting."""
+    rng = np.random.default_rng([seed, 77])
+    parts = []
+    for k, size in enumerate(sizes):
+        if size == 1:
+            value = float(rng.uniform(0.5, 4.0))
+            recs, x = O.stack([O.fixed(0, value)]), np.asarray([value])
+        else:
+            recs, g = gen.connected_sketch(size, seed * 131 + k)
+            x = polished(recs, g)[0]
+        extra = []
+        for j, i in enumerate(rng.choice(len(recs), 3, replace=len(recs) < 3)):
+            c = recs[i].copy()
+            if j == 1 and int(c["kind"]) in VALUE_KINDS:
+                c["param"] = float(c["param"]) + 0.3
+            c["weight"] = REPEAT_WEIGHTS[int(rng.integers(0, 3))]
+            extra.append(c)
+        parts.append((O.stack(list(recs) + extra), len(x), x))
+    parts += [(O.stack(r), int(n), np.asarray(x, dtype=np.float64)) for r, n, x in blocks]
+    all_recs, xs, origin, off = [], [], [], 0
+    for k, (recs, n, x) in enumerate(parts):
+        all_recs += list(relabel(recs, off + np.arange(n)))
+        origin += [(k, i) for i in range(len(recs))]
+        xs.append(x)
+        off += n
+    order = rng.permutation(len(all_recs)) if shuffle else np.arange(len(all_recs))
+    recs = O.stack([all_recs[i] for i in order])
+    x = np.concatenate(xs)[None, :]
+    flagged = np.nonzero(analyse(recs, off, x[0])["con_status"] >= REDUNDANT)[0]
+    return dict(recs=recs, n_vars=off, x=x, focus=[int(f) for f in flagged[:6]], origin=[origin[i] for i in order])
+
+
+def _draw_fuzz(count=44, seed=20240611):
+    """(sizes, seed) pairs: the largest part goes round LARGEST (every lane-group width, thread count and workspace home; a largest
+    part of two points is LANE without a focus list and TEAM with one), one to four more parts no larger are drawn."""
+    largest = (1, 2, 2, 4, 7, 12, 17, 28, 36, 45)
+    pool = (1, 1, 2, 3, 5, 7, 9, 12, 17, 24, 36)
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(count):
+        top = largest[k % len(largest)]
+        rest = [int(v) for v in rng.choice([p for p in pool if p <= top], int(rng.integers(1, 5)))]
+        sizes = rest + [top]
+        rng.shuffle(sizes)
+        out.append((tuple(int(v) for v in sizes), int(rng.integers(0, 10000))))
+    return out
+
+
+FUZZ_DRAWN = _draw_fuzz()
+# the drawn systems with a row inside a band of test_inputs_keep_their_distance_from_the_tolerances (test_redundancy_cpu.py holds
+# this list to what the reference finds, and to a tenth of the draws)
+FUZZ_REJECTED = ()
+FUZZ = [f for k, f in enumerate(FUZZ_DRAWN) if k not in FUZZ_REJECTED]
+
+
+def within_margins(ref):
+    """The bands of test_inputs_keep_their_distance_from_the_tolerances: what lies inside them ([] when the input is fair)."""
+    bad = []
+    tau = ref["tau"][~np.isnan(ref["tau"])]
+    bad += [("tau", v) for v in tau[(tau >= 1e-11) & (tau <= 1e-3)]]
+    rho = ref["rho_w"][~np.isnan(ref["rho_w"])]
+    bad += [("rho", v) for v in rho[(rho >= 1e-7) & (rho <= 1e-2)]]
+    for per_focus in ref["ratios"]:
+        for ratio in per_focus:
+            bad += [("ratio", v) for v in ratio[(ratio >= 1e-9) & (ratio <= 1e-3)]]
+    return bad
+
+
+def coincident(b, c, seed):
+    """About a third of the (system, component) pairs of pairs(), by a keyed hash."""
+    h = (b * 2654435761 + c * 40503 + seed * 7919 + 12345) & 0xFFFFFFFF
+    h ^= h >> 15
+    h = (h * 2246822519) & 0xFFFFFFFF
+    h ^= h >> 13
+    return h % 3 == 0
+
+
+def pairs(ncomp, batch, seed):
+    """The LANE batch whose systems differ: `ncomp` components of two points p, q with distance(p, q, d) and distance(p, q, d'),
+    d' = d (REDUNDANT) or d + 0.3 (CONFLICTING) by component; values drawn in [0.5, 4], and q = p where coincident() says so -- the
+    guard leaves both rows without entries there, ZERO, in that system only.  18 workspace doubles per component, 22 with groups."""
+    rng = np.random.default_rng([seed, ncomp])
+    recs, moved = [], []
+    for c in range(ncomp):
+        d = float(rng.uniform(0.5, 4.0))
+        moved.append(bool(rng.integers(0, 2)))
+        p, q = (4 * c, 4 * c + 1), (4 * c + 2, 4 * c + 3)
+        recs += [O.distance(p, q, d), O.distance(p, q, d + 0.3 if moved[-1] else d, weight=REPEAT_WEIGHTS[c % 3])]
+    x = gen.keyed_uniform(seed, batch, 4 * ncomp, 0.5, 4.0)
+    for b in range(batch):
+        for c in range(ncomp):
+            if coincident(b, c, seed):
+                x[b, 4 * c + 2: 4 * c + 4] = x[b, 4 * c: 4 * c + 2]
+    focus = sorted({1, 2 * (ncomp // 2) + 1, 2 * ncomp - 1}) + [0]
+    return dict(recs=O.stack(recs), n_vars=4 * ncomp, x=x, focus=focus, moved=moved, seed=seed)
+
+
+def pairs_expected(c):
+    """con_status [batch, 2 ncomp] of a pairs() case from how it was built."""
+    want = np.zeros((len(c["x"]), len(c["recs"])), np.uint8)
+    for b in range(len(c["x"])):
+        for k, moved in enumerate(c["moved"]):
+            want[b, 2 * k: 2 * k + 2] = [ZERO, ZERO] if coincident(b, k, c["seed"]) else [INDEPENDENT, CONFLICTING if moved else REDUNDANT]
+    return want
+
+
+def embedded():
+    """The records of pairs:3 as one part of a mosaic beside a 24-point sketch (TEAM) and a fixed variable: `at` [6] says where they
+    are; both systems of the block, the other parts' values twice; the block's focus list at its new positions."""
+    block = case("pairs:3")
+    m = mosaic([24, 1], 9, blocks=[(block["recs"], block["n_vars"], block["x"][0])])
+    at = [m["origin"].index((2, i)) for i in range(len(block["recs"]))]
+    x = np.repeat(m["x"], len(block["x"]), axis=0)
+    x[:, -block["n_vars"]:] = block["x"]
+    return dict(recs=m["recs"], n_vars=m["n_vars"], x=x, focus=[at[f] for f in block["focus"]], at=at)
+
+
+def grid_lane():
+    """65 components (G = 1) for the LANE grid loop: 64 fixed variables, each fixed once more (every third to another value), and
+    one pairs() component in the middle of the record list; six systems, the pair coincident in three of them."""
+    rng = np.random.default_rng(65)
+    recs = []
+    for v in range(64):
+        value = float(rng.uniform(0.5, 4.0))
+        recs += [O.fixed(v, value), O.fixed(v, value + (0.3 if v % 3 == 0 else 0.0), weight=REPEAT_WEIGHTS[v % 3])]
+    p, q = (64, 65), (66, 67)
+    recs[64:64] = [O.distance(p, q, 2.0), O.distance(p, q, 2.3, weight=2.5)]
+    x = rng.uniform(0.5, 4.0, (6, 68))
+    for b in (0, 3, 4):  # (no shift of the six repeats the pattern)
+        x[b, 66:68] = x[b, 64:66]
+    return dict(recs=O.stack(recs), n_vars=68, x=x, focus=[65, 1, 3, 129])
+
+
+def grid_rectangle():
+    """rectangle:side_conflict at three value vectors: polished, all zeros (the guards of the three distances fire) and polished with one
+    corner moved up by 0.5: the long side that cannot hold leans, and the horizontal joins what it is made of."""
+    c = rectangle("side_conflict")
+    moved = c["x"][0].copy()
+    moved[7] += 0.5
+    return dict(c, x=np.stack([c["x"][0], np.zeros(8), moved]))
+
+
+def grid_sketch():
+    """The 45-point sketch (workspace in global memory with its focus list): three polished starts and all zeros, the zeros twice: a period
+    of five does not divide the 1024 workgroups, so a workgroup's second round differs from its first."""
+    c = sketch(45, 11, 0, 3)
+    zero = np.zeros((1, c["n_vars"]))
+    return dict(c, x=np.vstack([c["x"][:1], zero, c["x"][1:], zero]))
+
+
+# (components, batch): 3 G + 1 systems at G = 128 / components systems per workgroup; 150 components: lanes 0 .. 21 take two
+PAIRS = {f"pairs:{n}": (pairs, (n, b, 3)) for n, b in ((30, 13), (63, 7), (1, 385), (150, 3))}
+DRAWN = dict(PAIRS)
+DRAWN["pairs:3"] = (pairs, (3, 2, 15))
+DRAWN["pairs:3:embedded"] = (embedded, ())
+DRAWN["grid:lane"] = (grid_lane, ())
+DRAWN["grid:rectangle"] = (grid_rectangle, ())
+DRAWN["grid:sketch45"] = (grid_sketch, ())
+for _k, (_sizes, _seed) in enumerate(FUZZ_DRAWN):
+    DRAWN[f"fuzz:{_k}"] = (mosaic, (list(_sizes), _seed))
+FUZZ_NAMES = [f"fuzz:{k}" for k in range(len(FUZZ_DRAWN)) if k not in FUZZ_REJECTED]
+
 _BUILT, _REFS = {}, {}
 
 
 def case(name):
     if name not in _BUILT:
-        fn, args = CASES[name]
+        fn, args = CASES[name] if name in CASES else DRAWN[name]
         _BUILT[name] = fn(*args)
     return _BUILT[name]
 
