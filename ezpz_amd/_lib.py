@@ -16,6 +16,8 @@ STATUS_DTYPE = np.dtype(
      ("final_residual_inf", "<f8"), ("final_lambda", "<f8")]
 )
 assert STATUS_DTYPE.itemsize == 32
+GUARD_STEP_DTYPE = np.dtype([("reached", "<f8"), ("attempts", "<u4"), ("accepted", "<u4")])  # EzpzGuardStep
+assert GUARD_STEP_DTYPE.itemsize == 16
 
 
 class CConfig(C.Structure):
@@ -70,6 +72,14 @@ class CSweepPlan(C.Structure):
     _fields_ = [("route", C.c_uint32), ("in_kernel", C.c_uint32), ("params_in_lds", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
+class CGuardConfig(C.Structure):
+    _fields_ = [("max_halvings", C.c_uint32), ("max_attempts", C.c_uint32), ("max_move", C.c_double)]
+
+
+class CGuardStep(C.Structure):
+    _fields_ = [("reached", C.c_double), ("attempts", C.c_uint32), ("accepted", C.c_uint32)]
+
+
 SWEEP_ROUTES = ("interpreter", "sub-wavefront teams", "partitioned workgroup", "barrier workgroup", "record walk")  # EZPZ_SWEEP_*
 SWEEP_FRONTS = len(SWEEP_ROUTES)  # EZPZ_SWEEP_FRONTS: the route a caller opts into (ezpz_system_set_params_route), behind the entry's own
 SWEEP_ROUTE_NAMES = SWEEP_ROUTES + ("fronts",)
@@ -115,6 +125,7 @@ EXPORTS = [
     "ezpz_constraint_param_derivative", "ezpz_system_param_sensitivity_plan", "ezpz_system_param_sensitivity_device",
     "ezpz_system_param_sensitivity",
     "ezpz_system_sweep_params_plan", "ezpz_system_sweep_params_device", "ezpz_system_sweep_params",
+    "ezpz_default_guard_config", "ezpz_system_sweep_guarded_plan", "ezpz_system_sweep_guarded_device", "ezpz_system_sweep_guarded",
     "ezpz_system_set_params_route",
     "ezpz_system_set_sensitivity_route", "ezpz_debug_front_sens_tables",
     "ezpz_default_redundancy_config", "ezpz_system_redundancy", "ezpz_system_redundancy_device",
@@ -278,6 +289,16 @@ def lib():
     L.ezpz_system_sweep_params_device.argtypes = [vp, vp, vp, sz, vp, sz, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32, vp]
     L.ezpz_system_sweep_params.restype = C.c_int
     L.ezpz_system_sweep_params.argtypes = [vp, vp, vp, sz, vp, sz, sz, C.POINTER(CConfig), vp, vp, vp, vp, u32]
+    L.ezpz_default_guard_config.restype = None
+    L.ezpz_default_guard_config.argtypes = [C.POINTER(CGuardConfig)]
+    L.ezpz_system_sweep_guarded_plan.restype = C.c_int
+    L.ezpz_system_sweep_guarded_plan.argtypes = [vp, vp, sz, C.POINTER(CSweepPlan)]
+    L.ezpz_system_sweep_guarded_device.restype = C.c_int
+    L.ezpz_system_sweep_guarded_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, C.POINTER(CConfig), C.POINTER(CGuardConfig), vp, vp, vp,
+                                                   vp, vp, vp, u32, vp]
+    L.ezpz_system_sweep_guarded.restype = C.c_int
+    L.ezpz_system_sweep_guarded.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, C.POINTER(CConfig), C.POINTER(CGuardConfig), vp, vp, vp, vp, vp,
+                                            vp, u32]
     L.ezpz_solve_inner.restype = C.c_int
     L.ezpz_solve_inner.argtypes = [vp, vp, sz, vp, vp, sz, C.POINTER(CConfig), vp, vp, vp, sz, C.POINTER(COutcome)]
     L.ezpz_solve.restype = C.c_int

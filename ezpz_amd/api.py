@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, STATUS_DTYPE, CConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, STATUS_DTYPE, CConfig, CGuardConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -388,6 +388,22 @@ class Config:
 
     def _c(self) -> CConfig:
         return CConfig(self.max_iterations, self.residual_tolerance, self.step_tolerance, self.initial_lambda)
+
+
+@dataclass(frozen=True)
+class GuardConfig:
+    """EzpzGuardConfig, the policy of a guarded sweep: a step's fraction is halved at most max_halvings times (0 .. 20), a step
+    takes at most max_attempts solves (>= 1), and an attempt that moves any value further than max_move from the last accepted
+    ones is rejected (0: no such test).  Policy defaults (ezpz_default_guard_config), not measurements."""
+
+    max_halvings: int = 4
+    max_attempts: int = 12
+    max_move: float = 0.0
+
+    def _c(self) -> CGuardConfig:
+        if not (0 <= int(self.max_halvings) <= 20 and 1 <= int(self.max_attempts) <= 0xFFFFFFFF and math.isfinite(self.max_move)):
+            raise ValueError(f"guard: max_halvings in 0..20, max_attempts >= 1, a finite max_move, got {self}")
+        return CGuardConfig(int(self.max_halvings), int(self.max_attempts), float(self.max_move))
 
 
 @dataclass
@@ -935,6 +951,81 @@ class System:
         pos = self._positions(positions)
         p = CSweepPlan()
         rc = lib().ezpz_system_sweep_params_plan(self._h, pos.ctypes.data if len(pos) else None, len(pos), C.byref(p))
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        out = {f: getattr(p, f) for f, _ in CSweepPlan._fields_}
+        out["route_name"] = SWEEP_ROUTE_NAMES[p.route]
+        return out
+
+    def driven_values(self, positions) -> np.ndarray:
+        """The records' own values of the constraints at `positions`: what a system's guesses belong to before anything is driven."""
+        pos = self._positions(positions)
+        return np.array([self.records[int(p)]["param"] for p in pos], dtype=np.float64)
+
+    def sweep_guarded(self, x0: np.ndarray, positions, params0, params: np.ndarray, guard: Optional[GuardConfig] = None,
+                      config: Optional[Config] = None, want_mask: bool = False, warn_log: Optional[np.ndarray] = None):
+        """`ezpz_system_sweep_guarded`: sweep_params with step control -- a step whose solve fails, leaves constraints unsatisfied
+        or moves a value by more than guard.max_move is halved and tried again, and a sweep holds on to its last accepted answer
+        (the rule: include/ezpz_amd.h).  x0 [batch, n_vars]; params0 [batch, len(positions)] the driven values x0 belongs to (None:
+        the records' own, for every sweep); params [steps, batch, len(positions)] the targets.  Returns (x [steps, batch, n_vars],
+        status [steps, batch] of each step's LAST attempt, mask [steps, batch, n_cs] or None, guard [steps, batch] with fields
+        reached / attempts / accepted, params_reached [steps, batch, len(positions)]).  warn_log: as for sweep_params."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, max(self.n_vars, 1))
+        batch = x0.shape[0]
+        pos = self._positions(positions)
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        if len(pos) == 0 or params.ndim != 3 or params.shape[1:] != (batch, len(pos)):
+            raise ValueError(f"params: expected shape (steps, {batch}, {len(pos)}) with at least one position, got {params.shape}")
+        steps = params.shape[0]
+        if params0 is None:
+            params0 = np.tile(self.driven_values(pos), (batch, 1))
+        params0 = np.ascontiguousarray(params0, dtype=np.float64)
+        if params0.shape != (batch, len(pos)):
+            raise ValueError(f"params0: expected shape ({batch}, {len(pos)}), got {params0.shape}")
+        warn_cap = 0
+        if warn_log is not None:
+            if (not isinstance(warn_log, np.ndarray) or warn_log.dtype != np.uint64 or not warn_log.flags.c_contiguous
+                    or not warn_log.flags.writeable or warn_log.ndim != 3 or warn_log.shape[:2] != (steps, batch)):
+                raise ValueError(f"warn_log: expected a writeable C-contiguous uint64 array of shape ({steps}, {batch}, warn_cap)")
+            warn_cap = warn_log.shape[2]
+        cfg = (config or Config())._c()
+        g = (guard or GuardConfig())._c()
+        x = np.empty((steps, batch, x0.shape[1]))
+        st = np.zeros((steps, batch), dtype=STATUS_DTYPE)
+        gs = np.zeros((steps, batch), dtype=GUARD_STEP_DTYPE)
+        reached = np.empty((steps, batch, len(pos)))
+        mask = np.zeros((steps, batch, max(len(self.records), 1)), dtype=np.uint8) if want_mask else None
+        rc = lib().ezpz_system_sweep_guarded(self._h, x0.ctypes.data, pos.ctypes.data, len(pos), params0.ctypes.data, params.ctypes.data,
+                                             steps, batch, C.byref(cfg), C.byref(g), x.ctypes.data, st.ctypes.data, gs.ctypes.data,
+                                             reached.ctypes.data, mask.ctypes.data if want_mask else None,
+                                             warn_log.ctypes.data if warn_cap else None, warn_cap)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return x, st, mask, gs, reached
+
+    def sweep_guarded_device(self, x0_ptr: int, positions, params0_ptr: int, params_ptr: int, steps: int, batch: int, x_out_ptr: int,
+                             status_ptr: int, guard_ptr: int, params_reached_ptr: int, mask_ptr: int = 0, log_ptr: int = 0,
+                             warn_cap: int = 0, stream: int = 0, guard: Optional[GuardConfig] = None,
+                             config: Optional[Config] = None) -> None:
+        """Device pointers and a hipStream_t handle; one launch, enqueue only (routes without a guarded kernel are declined: see
+        sweep_guarded_plan).  The layouts of sweep_params_device, with params0_ptr [batch, len(positions)], guard_ptr [steps, batch]
+        EzpzGuardStep (GUARD_STEP_DTYPE) and params_reached_ptr [steps, batch, len(positions)]; x0_ptr must not overlap x_out_ptr."""
+        pos = self._positions(positions)
+        cfg = (config or Config())._c()
+        g = (guard or GuardConfig())._c()
+        rc = lib().ezpz_system_sweep_guarded_device(self._h, x0_ptr or None, pos.ctypes.data if len(pos) else None, len(pos),
+                                                    params0_ptr or None, params_ptr or None, steps, batch, C.byref(cfg), C.byref(g),
+                                                    x_out_ptr or None, status_ptr or None, guard_ptr or None, params_reached_ptr or None,
+                                                    mask_ptr or None, log_ptr or None, warn_cap if log_ptr else 0, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+    def sweep_guarded_plan(self, positions) -> dict:
+        """`ezpz_system_sweep_guarded_plan`: sweep_params_plan's fields for a guarded sweep; `in_kernel` is 1 where the device form
+        serves the route in one launch and 0 where only the host form does.  Diagnostic."""
+        pos = self._positions(positions)
+        p = CSweepPlan()
+        rc = lib().ezpz_system_sweep_guarded_plan(self._h, pos.ctypes.data if len(pos) else None, len(pos), C.byref(p))
         if rc != 0:
             raise NonLinearSystemError(rc)
         out = {f: getattr(p, f) for f, _ in CSweepPlan._fields_}

@@ -1,7 +1,7 @@
 // The one path behind ezpz_system_solve_batch_params and ezpz_system_sweep_params (driven_params.hpp): the
 // check of a `positions` list, the request that resolves a list into its routes, the device table a list becomes (kept on the
 // system), the enqueue and the host form.  Host code only: the kernels are launched by the route launchers of params.hip,
-// sweep.hip, front_params.hip and comp.hip, which instantiate them.
+// sweep.hip, guarded_sweep.hip (a sweep with a GuardLaunch: DESIGN.md 3j), front_params.hip and comp.hip, which instantiate them.
 #include "driven_params.hpp"
 
 namespace ezpz {
@@ -72,7 +72,7 @@ int driven_table(EzpzSystem& s, const DrivenRequest& r, const uint32_t* position
 
 int driven_enqueue(EzpzSystem* sys, const DrivenRequest& r, const double* x0_dev, const uint32_t* positions, size_t n_param,
                    const double* params_dev, size_t steps, size_t batch, const EzpzConfig* cfg, double* x_out_dev, EzpzStatus* status_dev,
-                   uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, hipStream_t st) {
+                   uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, hipStream_t st, const GuardLaunch* guard) {
     const bool fronts = r.params_route == EZPZ_PARAMS_ROUTE_FRONTS;
     // fronts on several workgroups allocate their scratch on first use and chain their launches on an event: never inside a capture.
     // (A params call is told so before anything else, even one of no systems; a sweep once the thread's resident kernel is released.)
@@ -99,7 +99,18 @@ int driven_enqueue(EzpzSystem* sys, const DrivenRequest& r, const double* x0_dev
     KeptList& list = sys->driven.list;
     if (int rc = list.order_behind(st)) return rc;
     int rc;
-    if (fronts)
+    if (guard) {
+        if (fronts || r.for_comp || !steps) return EZPZ_ERR_INVALID_ARGUMENT;
+        GuardedSolveArgs ga{};
+        static_cast<SolveArgs&>(ga) = a;
+        ga.params0 = guard->params0;
+        ga.params_reached = guard->params_reached;
+        ga.guard = guard->guard;
+        ga.max_move = guard->max_move;
+        ga.h_min = guard->h_min;
+        ga.max_attempts = guard->max_attempts;
+        rc = list_walk_guarded_launch(*sys, ga, r.sweep_route, st);
+    } else if (fronts)
         rc = front_params_launch(*sys, a, steps != 0, st);
     else if (r.for_comp)
         rc = steps ? comp_sweep_launch(*sys, a, st)

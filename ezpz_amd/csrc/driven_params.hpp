@@ -22,9 +22,19 @@ struct DrivenRequest {
 int driven_request(EzpzSystem* sys, const uint32_t* positions, size_t n_param, DrivenRequest& r);
 // The device form of both entries behind their argument checks: steps == 0 a params call of `batch` systems, steps >= 1 `batch`
 // sweeps of `steps` solves in one launch (n_param, and for a sweep batch, not zero).
+// `guard`: the sweep is a guarded one (guarded_sweep.hip; a list-walk route that has a GRD build, steps >= 1) -- the guard's part of
+// GuardedSolveArgs, whose SolveArgs part the enqueue fills as for every sweep.
+struct GuardLaunch {
+    const double* params0;
+    double* params_reached;
+    EzpzGuardStep* guard;
+    double max_move, h_min;
+    uint32_t max_attempts;
+};
 int driven_enqueue(EzpzSystem* sys, const DrivenRequest& r, const double* x0_dev, const uint32_t* positions, size_t n_param,
                    const double* params_dev, size_t steps, size_t batch, const EzpzConfig* cfg, double* x_out_dev, EzpzStatus* status_dev,
-                   uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, hipStream_t stream);
+                   uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, hipStream_t stream,
+                   const GuardLaunch* guard = nullptr);
 // The host form of both: stages max(steps, 1) * batch rows in the system's scratch, runs `device_form` on them (values in place) on
 // hipStreamPerThread, waits and reads back -- statuses first (a team timeout: EZPZ_ERR_HIP), the log cut to n_warnings per row.
 using DrivenDeviceForm = std::function<int(double* x_dev, const double* params_dev, EzpzStatus* status_dev, uint8_t* mask_dev, uint64_t* log_dev)>;
@@ -34,6 +44,7 @@ int driven_host_form(EzpzSystem* sys, const double* x0, size_t n_param, const do
 // ---- the route launchers (launch_mu is held, the device current; a.params / par_slot / n_param set, a.steps for a sweep) -------
 int list_walk_params_launch(EzpzSystem& s, SolveArgs& a, hipStream_t stream);                  // params.hip: the PAR builds
 int list_walk_sweep_launch(EzpzSystem& s, SolveArgs& a, uint32_t route, hipStream_t stream);   // sweep.hip: the SWP builds
+int list_walk_guarded_launch(EzpzSystem& s, GuardedSolveArgs& a, uint32_t route, hipStream_t stream);  // guarded_sweep.hip: the GRD builds
 int comp_sweep_launch(EzpzSystem& s, const SolveArgs& a, hipStream_t stream);                  // sweep.hip: the interpreter's SWP builds
 int front_params_launch(EzpzSystem& s, SolveArgs& a, bool sweep, hipStream_t stream);          // front_params.hip: PAR, or SWP
 // (the interpreter's PAR builds: comp_launch of comp.hip with these arguments -- the one place that hands it the driven ones)

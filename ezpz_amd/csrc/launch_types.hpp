@@ -115,6 +115,28 @@ struct SolveArgs {
 };
 constexpr uint32_t kNoParamSlot = 0xFFFFFFFFu;
 
+// The argument block of the GRD builds (guarded_sweep.hip): SolveArgs, then the guard's.  A type of its own, like
+// FrontParArgs: more fields in SolveArgs would move the arguments the runtime appends behind it, and with them the code of every
+// build that never reads these.  Row q of params0 holds the driven values x0's row q was solved at; row k * batch + q of
+// params_reached and of guard is step k's of sweep q.
+struct GuardedSolveArgs : SolveArgs {
+    const double* params0;
+    double* params_reached;
+    EzpzGuardStep* guard;
+    double max_move;        // <= 0: no displacement test
+    double h_min;           // 2^-max_halvings: a step is given up once its fraction falls below
+    uint32_t max_attempts;  // solves per step at most
+    uint32_t pad;
+};
+template <bool GRD>
+struct SolveArgsOf {
+    typedef SolveArgs type;
+};
+template <>
+struct SolveArgsOf<true> {
+    typedef GuardedSolveArgs type;
+};
+
 // a round's descriptor (per wavefront): chunks to load (0 = the wavefront has no item), log2 of the lanes per list, ...
 constexpr uint32_t REC_NCH_MASK = 7u, REC_LG_SHIFT = 3u, REC_BARRIER = 1u << 7, REC_BWD = 1u << 8;
 // ... and a lane's own flags (high half of the record's second word)

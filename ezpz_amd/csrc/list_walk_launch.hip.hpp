@@ -1,9 +1,10 @@
 // Which instantiation of lm_solve_kernel a launch of a system on ONE workgroup per system (or less) takes: sub-wavefront teams,
 // the wavefront-partitioned workgroup, the barrier workgroup with its workspace in LDS or in global memory, the record walk.
-// Included by the three translation units that instantiate those kernels: launch.hip (PAR = false: every entry point but two),
-// params.hip (PAR = true: ezpz_system_solve_batch_params, whose systems bring their own constraint parameters) and sweep.hip
-// (PAR and SWP: ezpz_system_sweep_params, a chain of such solves per system in one launch; `batch` counts sweeps there) -- the
-// three sets of builds compile side by side.  (The caller holds the system's launch lock.)
+// Included by the four translation units that instantiate those kernels: launch.hip (PAR = false: every entry point but two),
+// params.hip (PAR = true: ezpz_system_solve_batch_params, whose systems bring their own constraint parameters), sweep.hip
+// (PAR and SWP: ezpz_system_sweep_params, a chain of such solves per system in one launch; `batch` counts sweeps there) and
+// guarded_sweep.hip (GRD: ezpz_system_sweep_guarded, the sweep with step control in the team; no partitioned workgroup) -- the
+// four sets of builds compile side by side.  (The caller holds the system's launch lock.)
 #pragma once
 #include "system.hpp"
 
@@ -12,9 +13,11 @@
 namespace ezpz {
 
 // `lds_bytes`: the launch's dynamic LDS -- the system's, plus the teams' parameter copies of a PAR launch.
-template <bool PAR, bool SWP, int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool DENSE = false, int REC = 0>
-int launch_kernel(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
-    auto kernel = lm_solve_kernel<TEAM, MODE, LDSWS, PLDS, LIN, false, DENSE, REC, PAR, SWP>;
+// (ARGS: SolveArgs, or the guarded builds' GuardedSolveArgs -- guarded_sweep.hip, the one place that passes it)
+template <bool PAR, bool SWP, int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool DENSE = false, int REC = 0, class ARGS>
+int launch_kernel(EzpzSystem& s, const ARGS& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
+    constexpr bool GRD = std::is_same<ARGS, GuardedSolveArgs>::value;
+    auto kernel = lm_solve_kernel<TEAM, MODE, LDSWS, PLDS, LIN, false, DENSE, REC, PAR, SWP, GRD>;
     // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel, not to the system: raised once per kernel
     // build and device, to everything the device allows, so that systems of different sizes sharing a build never
     // lower each other's limit
@@ -30,14 +33,14 @@ int launch_kernel(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t ld
 }
 
 // Every team shape comes in two builds: all 25 kinds, or the nine linear kinds only (`linear_only` topologies).
-template <bool PAR, bool SWP, int TEAM, int MODE, bool LDSWS, bool PLDS>
-int launch_variant(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
+template <bool PAR, bool SWP, int TEAM, int MODE, bool LDSWS, bool PLDS, class ARGS>
+int launch_variant(EzpzSystem& s, const ARGS& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
     if (s.linear_only) return launch_kernel<PAR, SWP, TEAM, MODE, LDSWS, PLDS, true>(s, args, grid, lds_bytes, stream);
     return launch_kernel<PAR, SWP, TEAM, MODE, LDSWS, PLDS, false>(s, args, grid, lds_bytes, stream);
 }
 
-template <bool PAR, bool SWP, int TEAM>
-int launch_sub(EzpzSystem& s, const SolveArgs& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
+template <bool PAR, bool SWP, int TEAM, class ARGS>
+int launch_sub(EzpzSystem& s, const ARGS& args, uint32_t grid, size_t lds_bytes, hipStream_t stream) {
     if constexpr (TEAM == 4) {  // <= 8 variables: dense factor layout, solved in registers (always staged)
         if (s.counts.dense)
             return s.linear_only ? launch_kernel<PAR, SWP, TEAM, MODE_SUB, true, true, true, true>(s, args, grid, lds_bytes, stream)
@@ -58,8 +61,12 @@ int on_workspace(EzpzSystem& s, hipStream_t stream, Launch&& launch) {
     return rc;
 }
 
-template <bool PAR, bool SWP = false>
-int list_walk_one_workgroup(EzpzSystem& s, SolveArgs& args, size_t lds_bytes, hipStream_t stream) {
+template <bool PAR, bool SWP = false, class ARGS>
+int list_walk_one_workgroup(EzpzSystem& s, ARGS& args, size_t lds_bytes, hipStream_t stream) {
+    constexpr bool GRD = std::is_same<ARGS, GuardedSolveArgs>::value;
+    if constexpr (GRD) {  // (no guarded build of the partitioned workgroup: its wavefronts are an item apart)
+        if (s.mode == MODE_PART) return EZPZ_ERR_INVALID_ARGUMENT;
+    }
     uint32_t grid;
     if (s.mode == MODE_SUB) {
         const uint32_t tpb = s.block_threads / s.team_size;
@@ -94,16 +101,20 @@ int list_walk_one_workgroup(EzpzSystem& s, SolveArgs& args, size_t lds_bytes, hi
         if (rc != EZPZ_OK) return rc;
         args.gws = s.gws_dev.p;
         return on_workspace(s, stream, [&] {
-            return s.mode == MODE_PART ? launch_variant<PAR, SWP, 64, MODE_PART, false, false>(s, args, grid, lds_bytes, stream)
-                   : !s.rec            ? launch_variant<PAR, SWP, 64, MODE_WGB, false, false>(s, args, grid, lds_bytes, stream)
+            if constexpr (!GRD) {
+                if (s.mode == MODE_PART) return launch_variant<PAR, SWP, 64, MODE_PART, false, false>(s, args, grid, lds_bytes, stream);
+            }
+            return !s.rec              ? launch_variant<PAR, SWP, 64, MODE_WGB, false, false>(s, args, grid, lds_bytes, stream)
                    : s.linear_only     ? launch_kernel<PAR, SWP, 64, MODE_WGB, false, false, true, false, 2>(s, args, grid, lds_bytes, stream)
                                        : launch_kernel<PAR, SWP, 64, MODE_WGB, false, false, false, false, 2>(s, args, grid, lds_bytes, stream);
         });
     }
     const bool staged = s.prog_in_lds;
-    if (s.mode == MODE_PART)
-        return staged ? launch_variant<PAR, SWP, 64, MODE_PART, true, true>(s, args, grid, lds_bytes, stream)
-                      : launch_variant<PAR, SWP, 64, MODE_PART, true, false>(s, args, grid, lds_bytes, stream);
+    if constexpr (!GRD) {
+        if (s.mode == MODE_PART)
+            return staged ? launch_variant<PAR, SWP, 64, MODE_PART, true, true>(s, args, grid, lds_bytes, stream)
+                          : launch_variant<PAR, SWP, 64, MODE_PART, true, false>(s, args, grid, lds_bytes, stream);
+    }
     if (!s.rec)
         return staged ? launch_variant<PAR, SWP, 64, MODE_WGB, true, true>(s, args, grid, lds_bytes, stream)
                       : launch_variant<PAR, SWP, 64, MODE_WGB, true, false>(s, args, grid, lds_bytes, stream);

@@ -297,6 +297,24 @@ __device__ __forceinline__ void next_item(uint64_t& q, uint32_t& step, uint32_t 
     q += stride;
 }
 
+// A guarded build's (GRD) state of the step its team is on -- the fraction reached and the one to add, the attempts and accepts so
+// far, whether the workspace does NOT hold the last accepted values (they are gathered again), whether this item ended the step
+// -- and its walk: an item is an ATTEMPT, and the walk stays where it is until the step is over.  Empty in every other build.
+template <bool GRD>
+struct GuardState {};
+template <>
+struct GuardState<true> {
+    double t = 0.0, h = 1.0;
+    uint32_t attempts = 0, accepted = 0;
+    bool gather = true, over = true;
+};
+__device__ __forceinline__ void next_attempt(uint64_t& q, uint32_t& step, uint32_t steps, uint64_t stride, const GuardState<true>& g) {
+    if (g.over) next_item<true>(q, step, steps, stride);
+}
+__device__ __forceinline__ void next_attempt(uint64_t&, uint32_t&, uint32_t, uint64_t, const GuardState<false>&) {}
+__device__ __forceinline__ bool gather_again(const GuardState<true>& g) { return g.gather; }
+__device__ __forceinline__ bool gather_again(const GuardState<false>&) { return false; }
+
 template <int TEAM, int MODE, bool GRID = false>
 struct Team {
     int lane;     // lane inside the unit that walks a phase (team for SUB, wave for PART, workgroup for WGB)
@@ -473,10 +491,21 @@ struct ConRef<2, PROG> {
 // else (the driven values, the warning counter, the LM state) starts afresh per item exactly as it does per system.  A
 // partitioned workgroup's wavefronts stay at most one ITEM apart (the rendezvous behind the load), so its two copies of the
 // driven values alternate by item, and a wavefront that is a step ahead has touched only its own partition's values.
+// GRD: the build of ezpz_system_sweep_guarded (implies SWP; instantiated in guarded_sweep.hip only, with an argument
+// block of its own, GuardedSolveArgs) -- the sweep with step control in the team that owns it.  An item of the loop is an ATTEMPT
+// at the fraction u = t + h of step k: the team forms p_u from the row the step started at (params_reached[k - 1], or params0) and
+// params[k] -- into its LDS copy of the driven values, or into the params_reached[k] row, which is its own -- solves exactly as a
+// SWP item does (status, mask and log go to row k every time: the last attempt's stay), and accepts the answer when it converged
+// with nothing unsatisfied and moved no value by more than max_move from the last accepted row; only then are the values stored.
+// After a reject h halves and x is gathered again from the last accepted row (x_out[k] once this step had an accept, else
+// x_out[k - 1] or x0: each thread reads back what it stored itself), the way step 0 gathers.  `step` advances when the step is
+// over: t reached 1, the attempts ran out or h fell below h_min; the team then writes guard[k], params_reached[k] and, if nothing
+// was accepted, copies the last accepted row into x_out[k].  Teams that share a wavefront or a workgroup run different numbers
+// of items; nothing in the item loop is wider than the team but the program values behind uni(), which every team shares.
 template <int TEAM, int MODE, bool LDSWS, bool PLDS, bool LIN, bool GRID = false, bool DENSE = false, int RECF = 0, bool PAR = false,
-          bool SWP = false>
+          bool SWP = false, bool GRD = false>
 __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1024 : 512), MODE == MODE_SUB ? (DENSE ? 2 : 4) : 1)
-    lm_solve_kernel(const SolveArgs a) {
+    lm_solve_kernel(const typename SolveArgsOf<GRD>::type a) {
     // RECF: the record walk's form -- 0 none, 1 state in LDS (16-bit addresses), 2 state in global memory (32-bit addresses)
     constexpr bool REC = RECF != 0;
     constexpr int RCH = RECF == 2 ? REC_WIDE_CHUNKS : REC_MAX_CHUNKS;  // chunks per lane and round
@@ -484,6 +513,7 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
     static_assert(!REC || (MODE == MODE_WGB && !GRID && !DENSE && (RECF == 1) == LDSWS), "the record walk is for one barrier workgroup");
     static_assert(!GRID || (MODE == MODE_PART && LDSWS && PLDS), "grid teams are partitioned teams with staged lists");
     static_assert(!PAR || !GRID, "driven parameters are served by one-workgroup teams");
+    static_assert(!GRD || (SWP && MODE != MODE_PART), "a guarded sweep is a sweep, and not for wavefronts that are an item apart");
     static_assert(!SWP || PAR, "a sweep drives parameters");  // (and takes no list of systems, no resumed state, no resident requests: sweep.hip)
     extern __shared__ __attribute__((aligned(16))) double smem[];
     using namespace dev;
@@ -663,12 +693,13 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
     do {
     x_have = false;
     uint32_t step = 0;  // (sweep builds: the step of sweep q this item is)
+    GuardState<GRD> g;
     for (uint64_t q = (uint64_t)grid_slot * teams_per_block + team_in_block; q < n_sys;
-         next_item<SWP>(q, step, a.steps, n_teams), sys_parity ^= 1u) {
+         GRD ? next_attempt(q, step, a.steps, n_teams, g) : next_item<SWP>(q, step, a.steps, n_teams), sys_parity ^= 1u) {
         // (the row of everything a solve reads or writes per system; a sweep's values start from row q of x0)
         const uint64_t sys = SWP ? (uint64_t)step * a.batch + q : a.sys_list ? (uint64_t)a.sys_list[q] : q;
         const uint64_t x_row = SWP ? q : sys;
-        const bool load_x = !SWP || step == 0;
+        const bool load_x = GRD ? gather_again(g) : (!SWP || step == 0);
         // ---- load the initial values (AoS row, coalesced) ------------------------------------------------------------
 #ifdef EZPZ_STAMPS
         int stamp_n = 0;
@@ -676,6 +707,12 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
         EZPZ_STAMP(1);
         const bool resuming = !SWP && a.resume != nullptr;
         const double* x0 = (resuming ? a.x_out : a.x0) + x_row * n_row;
+        if constexpr (GRD) {  // (the last accepted row)
+            if (g.accepted)
+                x0 = a.x_out + sys * n_row;
+            else if (step)
+                x0 = a.x_out + (sys - a.batch) * n_row;
+        }
         if constexpr (MODE == MODE_PART) {
             // each wavefront loads (and later stores) its own partition's variables only: a wavefront that is already
             // on the next system never touches values another one has not stored yet.  The first four values per lane
@@ -704,7 +741,18 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
         } else if (load_x) {
             for (uint32_t i = tlane; i < n; i += tsize) ws[o_x + i] = x0[P.var_of[i]];
         }
-        if constexpr (PAR) {
+        if constexpr (GRD) {
+            // p_u = p_a + u (p_b - p_a), each operation rounded by itself (the build never contracts), and p_b itself at u == 1
+            const double u = g.t + g.h;  // (dyadic: exact)
+            const double* pa = step ? a.params_reached + (sys - a.batch) * a.n_param : a.params0 + q * a.n_param;
+            const double* pb = a.params + sys * a.n_param;
+            double* dst = par_lds ? par_lds : a.params_reached + sys * a.n_param;
+            for (uint32_t i = tlane; i < a.n_param; i += tsize) {
+                const double va = pa[i], vb = pb[i];
+                dst[i] = u == 1.0 ? vb : va + u * (vb - va);
+            }
+            par_vals = dst;
+        } else if constexpr (PAR) {
             const double* src = a.params + sys * a.n_param;
             par_vals = src;
             if (par_lds) {  // (uniform per launch: a scalar branch)
@@ -1726,6 +1774,27 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
         if (!skip_count) tm.reduce2(unsat_cnt, dummy, OpSum(), OpSum());
         EZPZ_STAMP(31);
         double* xo = a.x_out + sys * n_row;
+        if constexpr (GRD) {
+            // the verdict on this attempt (uniform in the team: every term is a reduced value or an argument)
+            bool accept = converged == 1 && (uint32_t)unsat_cnt == 0;
+            if (accept && a.max_move > 0.0) {  // (against the last accepted row, before the store; a NaN rejects)
+                double moved = 0.0, none = 0.0;
+                for (uint32_t i = tlane; i < n; i += tsize)
+                    if (!(fabs(ws[o_x + i] - x0[P.var_of[i]]) <= a.max_move)) moved = 1.0;
+                tm.reduce2(moved, none, OpSum(), OpSum());
+                accept = moved == 0.0;
+            }
+            ++g.attempts;
+            if (accept) {
+                g.t += g.h;
+                ++g.accepted;
+            } else {
+                g.h *= 0.5;
+            }
+            g.gather = !accept;
+            g.over = g.t >= 1.0 || g.attempts >= a.max_attempts || (!accept && g.h < a.h_min);
+        }
+        if (!GRD || !gather_again(g)) {  // (guarded builds: only an accepted attempt's values)
         if constexpr (OWN_STORE) {
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j) {
@@ -1735,6 +1804,31 @@ __global__ void __launch_bounds__(MODE == MODE_SUB ? 256 : (LIN && RECF == 0 ? 1
             for (uint32_t ci = call0 + tm.lane + 4 * 64; ci < call1; ci += tm.stride) xo[P.var_of[ci]] = ws[o_x + ci];
         } else {
             for (uint32_t i = tlane; i < n; i += tsize) xo[P.var_of[i]] = ws[o_x + i];
+        }
+        }
+        if constexpr (GRD) {
+            if (g.over) {  // the step's own rows: what was reached, and -- when nothing was accepted -- the values it holds on to
+                const double* pa = step ? a.params_reached + (sys - a.batch) * a.n_param : a.params0 + q * a.n_param;
+                const double* pb = a.params + sys * a.n_param;
+                for (uint32_t i = tlane; i < a.n_param; i += tsize) {
+                    const double va = pa[i], vb = pb[i];
+                    a.params_reached[sys * a.n_param + i] = g.t == 0.0 ? va : g.t == 1.0 ? vb : va + g.t * (vb - va);
+                }
+                if (!g.accepted)
+                    for (uint32_t i = tlane; i < n; i += tsize) xo[P.var_of[i]] = x0[P.var_of[i]];
+                if (tlane == 0) {
+                    EzpzGuardStep gs;
+                    gs.reached = g.t;
+                    gs.attempts = g.attempts;
+                    gs.accepted = g.accepted;
+                    a.guard[sys] = gs;
+                }
+                g.t = 0.0;
+                g.h = 1.0;
+                g.attempts = 0;
+                g.accepted = 0;
+                if (step + 1 == a.steps) g.gather = true;  // (the team's next sweep starts from its own row of x0)
+            }
         }
         if (tlane == 0 && grid_wg == 0) {
             EzpzStatus st;

@@ -393,6 +393,63 @@ int ezpz_system_sweep_params(EzpzSystem* sys, const double* x0, const uint32_t* 
                              size_t steps, size_t batch, const EzpzConfig* cfg, double* x_out, EzpzStatus* status,
                              uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
 
+/* ---- guarded sweeps: the sweep with step control where the values live ---------------------------------------
+ * ezpz_system_sweep_params is policy-free; this entry carries one policy: a step that fails, lands on another configuration or
+ * moves too far is cut in half and tried again, and a sweep never leaves its last accepted answer.  Sweep b carries the state
+ * (x_s, p_s): the last accepted values and the driven values they were solved at; it starts as (x0[b], params0[b]) -- params0
+ * [batch][n_param] is required: the system's own values of the driven constraints, or params_reached of an earlier call.  Step k
+ * has the target p_b = params[k][b] and is BY DEFINITION:
+ *     p_a = p_s; t = 0; h = 1; attempts = 0; accepted = 0
+ *     while t < 1 and attempts < max_attempts:
+ *         u = t + h                                                    (dyadic, exact)
+ *         p_u[j] = p_b[j] if u == 1, else p_a[j] + u * (p_b[j] - p_a[j])   (three operations, each rounded by itself)
+ *         (x, status, mask, log) = ezpz_system_solve_batch_params' solve of this system from x_s with p_u      (bit for bit)
+ *         attempts += 1
+ *         accept iff status.converged == 1 and status.n_unsatisfied == 0
+ *                    and (max_move <= 0 or |x[i] - x_s[i]| <= max_move for every i)                        (a NaN rejects)
+ *         if accept: x_s = x; p_s = p_u; t = u; accepted += 1
+ *         else:      h /= 2; if h < 2^-max_halvings: break
+ *     x_out[k][b] = x_s; params_reached[k][b] = p_s; guard[k][b] = {reached = t, attempts, accepted}
+ *     status[k][b], unsat_mask[k][b], warn_log[k][b] = those of the LAST attempt, accepted or not
+ * h starts at 1 again at every step and never grows within one; a step that stops short leaves (x_s, p_s) where they are and the
+ * next step tries to catch up from there.  The state across steps is (x_s, p_s) alone: a sweep of 2K steps equals a sweep of K
+ * steps and a second one of K steps from (x_out[K - 1], params_reached[K - 1]).  max_halvings == 0 with max_move == 0 is the plain
+ * sweep that holds the last good answer.  Layouts are the sweep's (step-major), with guard[steps][batch] and
+ * params_reached[steps][batch][n_param]; of a row of warn_log the first min(status.n_warnings, warn_cap) entries are the last
+ * attempt's, the others unspecified.  x0 must not overlap x_out (a later step may read it again).
+ * EZPZ_ERR_INVALID_ARGUMENT, with nothing enqueued and no output touched: the argument errors of the sweep entry; n_param == 0; a
+ * NULL params0, guard or params_reached with work to do; a guard configuration out of range (max_halvings > 20, max_attempts == 0,
+ * a max_move that is not finite).  guard_cfg == NULL: ezpz_default_guard_config's values -- policy defaults, not measurements.
+ * The _device form runs in ONE launch -- the team that owns a sweep forms p_u, judges the attempt and gathers the last accepted
+ * values again after a reject -- on the sub-wavefront teams, the barrier workgroup (workspace in LDS or in global memory) and the
+ * record walk, and declines every other route with EZPZ_ERR_INVALID_ARGUMENT (the component interpreter, the partitioned
+ * workgroup, a system whose params route is the fronts; grid teams, like the params entry): ezpz_system_sweep_guarded_plan
+ * (host only, diagnostic) reports in_kernel == 0 for them.  The host form serves every route the params entry serves: where
+ * in_kernel is 1 it stages and calls the device form, elsewhere it runs the rule from the host as rounds of
+ * ezpz_system_solve_batch_params over the whole batch, one attempt per round for every sweep still inside its step -- the same
+ * bits either way.  Ordering among launches on one EzpzSystem and the `positions` table: as for ezpz_system_sweep_params. */
+typedef struct EzpzGuardConfig {
+    uint32_t max_halvings; /* 0 .. 20: a step's fraction h is halved at most this often (4) */
+    uint32_t max_attempts; /* >= 1: solves per step at most (12) */
+    double max_move;       /* finite; > 0: an attempt that moves a value further than this from the last accepted ones is rejected (0: off) */
+} EzpzGuardConfig;
+typedef struct EzpzGuardStep {
+    double reached;    /* t: the fraction of the step from where it started to its target that was accepted, 0 .. 1 */
+    uint32_t attempts; /* solves the step took */
+    uint32_t accepted; /* ... and how many of them were accepted */
+} EzpzGuardStep;
+void ezpz_default_guard_config(EzpzGuardConfig* out);
+int ezpz_system_sweep_guarded_plan(EzpzSystem* sys, const uint32_t* positions, size_t n_param, EzpzSweepPlan* out);
+int ezpz_system_sweep_guarded_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                     const double* params0_dev, const double* params_dev, size_t steps, size_t batch,
+                                     const EzpzConfig* cfg, const EzpzGuardConfig* guard_cfg, double* x_out_dev,
+                                     EzpzStatus* status_dev, EzpzGuardStep* guard_dev, double* params_reached_dev,
+                                     uint8_t* unsat_mask_dev, uint64_t* warn_log_dev, uint32_t warn_cap, void* stream);
+int ezpz_system_sweep_guarded(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const double* params0,
+                              const double* params, size_t steps, size_t batch, const EzpzConfig* cfg,
+                              const EzpzGuardConfig* guard_cfg, double* x_out, EzpzStatus* status, EzpzGuardStep* guard,
+                              double* params_reached, uint8_t* unsat_mask, uint64_t* warn_log, uint32_t warn_cap);
+
 /* ---- dimension sensitivities: dx/d(param) of a batch, on the device ------------------------------------------
  * For system b the caller passes values x_b (normally a solve's answer) and a parameter row p_b.  r(x, p) is the weighted
  * residual vector in the reference's row order with p overlaid exactly as ezpz_system_solve_batch_params overlays it,
