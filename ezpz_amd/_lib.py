@@ -18,6 +18,11 @@ STATUS_DTYPE = np.dtype(
 assert STATUS_DTYPE.itemsize == 32
 GUARD_STEP_DTYPE = np.dtype([("reached", "<f8"), ("attempts", "<u4"), ("accepted", "<u4")])  # EzpzGuardStep
 assert GUARD_STEP_DTYPE.itemsize == 16
+MC_DIST_DTYPE = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("a", "<f8"), ("b", "<f8")])  # EzpzMcDist
+MC_STATS_DTYPE = np.dtype([("n_valid", "<u8"), ("n_in", "<u8"), ("argmin", "<u8"), ("argmax", "<u8"), ("nominal", "<f8"),
+                           ("sum_d", "<f8"), ("sum_d2", "<f8"), ("mean", "<f8"), ("var", "<f8"), ("min", "<f8"), ("max", "<f8")])  # EzpzMcStats
+MC_TOTALS_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_all_in", "<u8")])  # EzpzMcTotals
+assert MC_DIST_DTYPE.itemsize == 24 and MC_STATS_DTYPE.itemsize == 88 and MC_TOTALS_DTYPE.itemsize == 24
 
 
 class CConfig(C.Structure):
@@ -76,6 +81,10 @@ class CGuardConfig(C.Structure):
     _fields_ = [("max_halvings", C.c_uint32), ("max_attempts", C.c_uint32), ("max_move", C.c_double)]
 
 
+class CMcConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("hist_bins", C.c_uint32)]
+
+
 class CGuardStep(C.Structure):
     _fields_ = [("reached", C.c_double), ("attempts", C.c_uint32), ("accepted", C.c_uint32)]
 
@@ -131,6 +140,7 @@ EXPORTS = [
     "ezpz_default_redundancy_config", "ezpz_system_redundancy", "ezpz_system_redundancy_device",
     "ezpz_constraint_measure", "ezpz_system_measure", "ezpz_system_measure_device", "ezpz_system_measure_response",
     "ezpz_system_measure_response_device", "ezpz_system_measure_vjp", "ezpz_system_measure_vjp_device",
+    "ezpz_default_mc_config", "ezpz_mc_sample", "ezpz_system_tolerance_mc", "ezpz_system_tolerance_mc_device",
 ]
 
 _lib = None
@@ -187,6 +197,15 @@ def lib():
     L.ezpz_system_measure_vjp.argtypes = [vp, vp, sz, vp, vp, sz, vp]
     L.ezpz_system_measure_vjp_device.restype = C.c_int
     L.ezpz_system_measure_vjp_device.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
+    L.ezpz_default_mc_config.restype = None
+    L.ezpz_default_mc_config.argtypes = [C.POINTER(CMcConfig)]
+    L.ezpz_mc_sample.restype = C.c_int
+    L.ezpz_mc_sample.argtypes = [C.c_uint64, vp, vp, sz, C.c_uint64, sz, vp]
+    L.ezpz_system_tolerance_mc.restype = C.c_int
+    L.ezpz_system_tolerance_mc.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, C.c_uint64, C.POINTER(CMcConfig),
+                                           C.POINTER(CConfig), vp, vp, vp, vp, vp, vp, vp]
+    L.ezpz_system_tolerance_mc_device.restype = C.c_int
+    L.ezpz_system_tolerance_mc_device.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp]
     L.ezpz_current_device.restype = C.c_int
     L.ezpz_current_device.argtypes = []
     L.ezpz_host_register.restype = C.c_int

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, STATUS_DTYPE, CConfig, CGuardConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, MC_DIST_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, CConfig, CGuardConfig, CMcConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1184,6 +1184,149 @@ class System:
                                                   grad_m_ptr or None, batch, grad_x_ptr or None, stream or None)
         if rc != 0:
             raise NonLinearSystemError(rc)
+
+    # ---- Monte-Carlo tolerance analysis (ezpz_system_tolerance_mc) ---------------------------------------------------------------
+    def _mc_request(self, positions, dists, records, nominal, limits, hist, seed, chunk):
+        pos = self._positions(positions)
+        d = mc_dists(dists)
+        if len(d) != len(pos):
+            raise ValueError(f"dists: one per position ({len(pos)}), got {len(d)}")
+        recs = stack_records(records)
+        k = len(recs)
+        if nominal is not None:
+            nominal = np.ascontiguousarray(nominal, dtype=np.float64)
+            if nominal.shape != (len(pos),):
+                raise ValueError(f"nominal: expected shape ({len(pos)},), got {nominal.shape}")
+
+        def pair(what, value, extra=0):
+            if value is None:
+                return None, None
+            if len(value) != 2 + extra:
+                raise ValueError(f"{what}: (lo [n_meas], hi [n_meas]{', bins' if extra else ''})")
+            lo, hi = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (k,))) for v in value[:2])
+            return lo, hi
+
+        lim_lo, lim_hi = pair("limits", limits)
+        hist_lo, hist_hi = pair("hist", hist, 1)
+        mc = CMcConfig(seed, chunk, int(hist[2]) if hist is not None else 0)
+        return pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc
+
+    def tolerance_mc(self, x0, positions, dists, records, samples: int, seed: int = 0, nominal=None, limits=None, hist=None,
+                     chunk: int = 0, keep: bool = False, config: Optional[Config] = None) -> "McResult":
+        """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
+        solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
+        statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
+        limits = (lo, hi), each [n_meas] or a scalar: the yield's limits; hist = (lo, hi, bins): a histogram of `bins` <= 64 bins per
+        record with an under and an over count; chunk: samples per round (0: the library's choice); keep: also every sample's
+        params, m, flags and ok.  The sums' order is fixed: the same bits whatever the chunk."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if x0.size != self.n_vars:
+            raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
+        pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
+                                                                                     seed, chunk)
+        k, n_param, samples = len(recs), len(pos), int(samples)
+        stats = np.zeros(k, dtype=MC_STATS_DTYPE)
+        totals = np.zeros(1, dtype=MC_TOTALS_DTYPE)
+        counts = np.zeros((k, mc.hist_bins + 2), dtype=np.uint64) if mc.hist_bins else None
+        kept = (np.zeros((samples, n_param)), np.zeros((samples, k)), np.zeros((samples, k), np.uint8),
+                np.zeros(samples, np.uint8)) if keep else (None,) * 4
+        cfg = (config or Config())._c()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_tolerance_mc(self._h, ptr(x0), ptr(pos), n_param, ptr(d), ptr(nominal), ptr(recs), k, ptr(lim_lo), ptr(lim_hi),
+                                            ptr(hist_lo), ptr(hist_hi), samples, C.byref(mc), C.byref(cfg), stats.ctypes.data,
+                                            totals.ctypes.data, ptr(counts), *(ptr(a) for a in kept))
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return McResult(stats, totals, counts, kept if keep else None)
+
+    def tolerance_mc_device(self, x0_ptr: int, positions, dists, records, samples: int, stats_ptr: int, totals_ptr: int, hist_ptr: int = 0,
+                            seed: int = 0, nominal=None, limits=None, hist=None, chunk: int = 0, keep_params_ptr: int = 0,
+                            keep_m_ptr: int = 0, keep_flags_ptr: int = 0, keep_ok_ptr: int = 0, stream: int = 0,
+                            config: Optional[Config] = None) -> None:
+        """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], hist: uint64
+        [n_meas, bins + 2]) and a hipStream_t handle; positions, dists, records, nominal, limits and hist = (lo, hi, bins) stay host
+        values.  Enqueues only once the run's tables are the last run's."""
+        pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
+                                                                                     seed, chunk)
+        cfg = (config or Config())._c()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_tolerance_mc_device(self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs),
+                                                   ptr(lim_lo), ptr(lim_hi), ptr(hist_lo), ptr(hist_hi), int(samples), C.byref(mc),
+                                                   C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
+                                                   keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None,
+                                                   stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+
+class McDist:
+    """A driving dimension's tolerance distribution (EzpzMcDist): the deviation added to its nominal value."""
+    FIXED, UNIFORM, NORMAL, CORNER = range(4)
+
+    def __init__(self, kind: int, a: float = 0.0, b: float = 0.0):
+        self.kind, self.a, self.b = int(kind), float(a), float(b)
+
+    def __repr__(self):
+        return "McDist.%s(%r, %r)" % (("fixed", "uniform", "normal", "corner")[self.kind] if 0 <= self.kind < 4 else self.kind, self.a, self.b)
+
+    @staticmethod
+    def fixed() -> "McDist":
+        return McDist(McDist.FIXED)
+
+    @staticmethod
+    def uniform(lo: float, hi: float) -> "McDist":
+        """A deviation uniform in [lo, hi)."""
+        return McDist(McDist.UNIFORM, lo, hi)
+
+    @staticmethod
+    def normal(sigma: float, trunc: float = 0.0) -> "McDist":
+        """A normal deviation of standard deviation sigma, truncated at +-trunc sigmas (0: not truncated, else >= 1)."""
+        return McDist(McDist.NORMAL, sigma, trunc)
+
+    @staticmethod
+    def corner(lo: float, hi: float) -> "McDist":
+        """The deviation lo or hi by a bit of the sample index: k such dimensions make samples 0 .. 2^k - 1 the 2^k corners."""
+        return McDist(McDist.CORNER, lo, hi)
+
+
+def mc_dists(dists) -> np.ndarray:
+    """A sequence of McDist (or an MC_DIST_DTYPE array) as the array the library reads."""
+    if isinstance(dists, np.ndarray) and dists.dtype == MC_DIST_DTYPE:
+        return np.ascontiguousarray(dists)
+    out = np.zeros(len(dists), dtype=MC_DIST_DTYPE)
+    for j, d in enumerate(dists):
+        out[j] = (d.kind, 0, d.a, d.b)
+    return out
+
+
+def mc_sample(seed: int, dists, nominal, first: int, count: int) -> np.ndarray:
+    """`ezpz_mc_sample`: params [count, n_param] of the samples first .. first + count - 1 -- what a tolerance_mc run of that
+    seed draws for them.  Host only."""
+    d = mc_dists(dists)
+    nominal = np.ascontiguousarray(nominal, dtype=np.float64)
+    if nominal.shape != (len(d),):
+        raise ValueError(f"nominal: expected shape ({len(d)},), got {nominal.shape}")
+    out = np.zeros((int(count), len(d)))
+    rc = lib().ezpz_mc_sample(int(seed), d.ctypes.data if len(d) else None, nominal.ctypes.data if len(d) else None, len(d), int(first),
+                              int(count), out.ctypes.data if out.size else None)
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return out
+
+
+class McResult:
+    """What `System.tolerance_mc` returns: numpy fields per measurement record -- n_valid, mean, std, var, min, max, argmin, argmax,
+    n_in, nominal, sum_d, sum_d2 -- hist [n_meas, bins + 2] (under, the bins, over; None without a histogram), the totals samples,
+    n_ok and n_all_in, and with keep the samples: params, m, flags, ok.  `stats` and `totals` are the library's records."""
+
+    def __init__(self, stats, totals, hist, kept):
+        self.stats, self.totals, self.hist = stats, totals, hist
+        for f in MC_STATS_DTYPE.names:
+            setattr(self, f, stats[f])
+        self.std = np.sqrt(stats["var"])
+        self.samples, self.n_ok, self.n_all_in = (int(totals[f][0]) for f in MC_TOTALS_DTYPE.names)
+        if kept is not None:
+            self.params, self.m, self.flags, self.ok = kept
 
 
 def constraint_measure(record, x):

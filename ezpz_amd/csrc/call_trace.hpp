@@ -39,6 +39,9 @@ enum CallStage : uint32_t {
     MEASURE_LAUNCHED = 51,        // the entry's kernels enqueued
     MEASURE_PLACED_ROW = 52,      // ... its measure launch staged the rows in LDS
     MEASURE_PLACED_DIRECT = 53,   // ... or gathered them from global memory
+    // ezpz_system_tolerance_mc_device (tolerance_mc.hip), around the stamps of the entries its rounds are made of
+    MC_TABLES_UPLOADED = 60,  // other distributions, limits or ranges than the last run's, or a workspace that had to grow: waited, copied
+    MC_LAUNCHED = 61,         // every round of the run enqueued
 };
 
 struct CallTrace {

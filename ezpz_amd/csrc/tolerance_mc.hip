@@ -1,0 +1,320 @@
+// Monte-Carlo tolerance analysis (include/ezpz_amd.h: ezpz_mc_sample, ezpz_system_tolerance_mc and its _device form; DESIGN.md
+// 3k): the host side of tolerance_mc.hip.hpp's kernels -- the check of a request, the plan a system keeps (the round's workspace,
+// the sampler's and the limits' tables, the host form's buffers) and the rounds.  A round is sampler -> copies of x0 ->
+// ezpz_system_solve_batch_params_device -> ezpz_system_measure_device -> reduction, all on the caller's stream: the driven solve
+// and the measurement are those entries themselves, with their routes, their locks and their ordering.
+#include "driven_params.hpp"
+#include "measure_tables.hpp"
+#include "tolerance_mc.hip.hpp"
+
+using namespace ezpz;
+
+namespace {
+
+static_assert(sizeof(EzpzMcDist) == 24 && sizeof(EzpzMcStats) == 88 && sizeof(EzpzMcTotals) == 24 && sizeof(EzpzMcConfig) == 16,
+              "the layouts include/ezpz_amd.h documents");
+
+constexpr uint32_t kBlock = 256;              // samples per block of the sums: fixed by the interface
+constexpr uint32_t kMaxHistBins = 64;
+constexpr uint64_t kDefaultChunk = 65536;     // samples per round where the caller leaves the choice ...
+constexpr uint64_t kChunkValueBytes = 256ull << 20;  // ... while one of the round's two value arrays stays below this
+
+struct McPlan {
+    std::mutex mu;  // a run holds it from its first upload to its last enqueue
+    // The completion of the last run's launches: a run on another stream goes behind it, and whatever a run overwrites from the
+    // host -- the tables, a buffer that has to grow -- waits for it first
+    LaunchOrder order;
+    std::vector<unsigned char> tables_kept;  // what `dist` and `tab` hold
+    DevBuf<mc::Dist> dist;
+    DevBuf<double> tab;  // lim_lo | lim_hi | hist_lo | hist_scale, [n_meas] each
+    DevBuf<double> x_in, x_out, params, m, nominal, part_f;
+    DevBuf<uint64_t> part_arg;
+    DevBuf<uint32_t> part_n;
+    DevBuf<uint8_t> flags, ok;
+    DevBuf<EzpzStatus> status;
+    DevBuf<unsigned int> ticket;
+    // the host form's buffers
+    DevBuf<double> x0_in;
+    DevBuf<EzpzMcStats> stats_out;
+    DevBuf<EzpzMcTotals> totals_out;
+    DevBuf<uint64_t> hist_out;
+};
+
+McPlan& plan_of(EzpzSystem* sys) {
+    std::lock_guard<std::mutex> lock(sys->mu);
+    if (!sys->tolerance_mc) sys->tolerance_mc = std::make_shared<McPlan>();
+    return *static_cast<McPlan*>(sys->tolerance_mc.get());
+}
+
+// The argument errors of the distributions, and the sampler's table.
+int check_dists(const EzpzMcDist* dist, const double* nominal, size_t n_param, std::vector<mc::Dist>& out) {
+    out.clear();
+    if (n_param == 0) return EZPZ_OK;
+    if (!dist || !nominal || n_param > 0xFFFFFFFEull) return EZPZ_ERR_INVALID_ARGUMENT;
+    out.resize(n_param);
+    uint32_t corners = 0;
+    for (size_t j = 0; j < n_param; ++j) {
+        const EzpzMcDist& d = dist[j];
+        if (d.kind > EZPZ_MC_CORNER || !std::isfinite(d.a) || !std::isfinite(d.b) || !std::isfinite(nominal[j]))
+            return EZPZ_ERR_INVALID_ARGUMENT;
+        if (d.kind == EZPZ_MC_UNIFORM && d.a > d.b) return EZPZ_ERR_INVALID_ARGUMENT;
+        if (d.kind == EZPZ_MC_NORMAL && (d.a < 0.0 || d.b < 0.0 || (d.b > 0.0 && d.b < 1.0))) return EZPZ_ERR_INVALID_ARGUMENT;
+        uint32_t rank = 0;
+        if (d.kind == EZPZ_MC_CORNER) {
+            if (corners == mc::kMaxCorners) return EZPZ_ERR_INVALID_ARGUMENT;
+            rank = corners++;
+        }
+        out[j] = mc::Dist{d.kind, rank, d.a, d.b, nominal[j]};
+    }
+    return EZPZ_OK;
+}
+
+struct Request {
+    std::vector<mc::Dist> dists;
+    std::vector<uint32_t> words;  // the packed measurement records (compared by the measure entry against its kept list)
+    std::vector<double> tab;      // lim_lo | lim_hi | hist_lo | hist_scale
+    bool limits = false;
+    uint32_t hist_bins = 0;
+    uint64_t seed = 0, chunk = 0;
+};
+
+// Every argument error of a run, before anything is enqueued or written.  `x0`, `stats`, `totals`, `hist` are only compared with NULL.
+int check_run(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist, const double* nominal,
+              const EzpzConstraint* records, size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
+              const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const void* stats, const void* totals, const void* hist,
+              hipStream_t stream, Request& r) {
+    if (!sys) return EZPZ_ERR_INVALID_ARGUMENT;
+    EzpzMcConfig c;
+    ezpz_default_mc_config(&c);
+    if (mc_cfg) c = *mc_cfg;
+    if (c.hist_bins > kMaxHistBins) return EZPZ_ERR_INVALID_ARGUMENT;
+    if ((lim_lo != nullptr) != (lim_hi != nullptr)) return EZPZ_ERR_INVALID_ARGUMENT;
+    if (c.hist_bins && n_meas && (!hist_lo || !hist_hi)) return EZPZ_ERR_INVALID_ARGUMENT;
+    if (int rc = measure_pack_records(records, n_meas, sys->counts.n_vars, r.words)) return rc;
+    r.tab.assign(4 * n_meas, 0.0);
+    for (size_t i = 0; i < n_meas; ++i) {
+        if (lim_lo) {
+            if (!(lim_lo[i] <= lim_hi[i])) return EZPZ_ERR_INVALID_ARGUMENT;
+            r.tab[i] = lim_lo[i], r.tab[n_meas + i] = lim_hi[i];
+        }
+        if (c.hist_bins) {
+            if (!(hist_hi[i] > hist_lo[i]) || !std::isfinite(hist_lo[i]) || !std::isfinite(hist_hi[i])) return EZPZ_ERR_INVALID_ARGUMENT;
+            r.tab[2 * n_meas + i] = hist_lo[i];
+            r.tab[3 * n_meas + i] = (double)c.hist_bins / (hist_hi[i] - hist_lo[i]);
+        }
+    }
+    // the params entry's errors: the list, a system it declines, a capture its fronts refuse
+    DrivenRequest driven;
+    if (n_param) {
+        if (int rc = driven_request(sys, positions, n_param, driven)) return rc;
+        if (driven.params_route == EZPZ_PARAMS_ROUTE_FRONTS && sys->fronts->n_wgs > 1 && stream_capturing(stream))
+            return EZPZ_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<double> own;
+    if (n_param && !nominal) {
+        own.resize(n_param);
+        for (size_t j = 0; j < n_param; ++j) own[j] = sys->host_cs[positions[j]].param;
+        nominal = own.data();
+    }
+    if (int rc = check_dists(dist, nominal, n_param, r.dists)) return rc;
+    if (samples && (!stats || !totals || (c.hist_bins && n_meas && !hist) || (sys->counts.n_vars && !x0))) return EZPZ_ERR_INVALID_ARGUMENT;
+    r.limits = lim_lo != nullptr;
+    r.hist_bins = c.hist_bins;
+    r.seed = c.seed;
+    uint64_t chunk = c.chunk;
+    if (chunk == 0) {
+        chunk = kDefaultChunk;
+        while (chunk > kBlock && chunk * std::max<uint64_t>(sys->counts.n_vars, 1) * sizeof(double) > kChunkValueBytes) chunk /= 2;
+    }
+    chunk = (chunk + kBlock - 1) / kBlock * kBlock;
+    r.chunk = std::min<uint64_t>(chunk, (std::max<uint64_t>(samples, 1) + kBlock - 1) / kBlock * kBlock);
+    return EZPZ_OK;
+}
+
+uint32_t stride_grid(uint64_t items, const EzpzSystem* sys) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, (uint64_t)sys->lim.cus * 16));
+}
+
+struct Keep {
+    double* params;
+    double* m;
+    uint8_t* flags;
+    uint8_t* ok;
+    bool host;  // the keep_* pointers are host memory: a round waits for its launches and copies out
+};
+
+int copy_out(void* dst, const void* src, size_t bytes, bool host, hipStream_t stream) {
+    if (!dst || !bytes) return EZPZ_OK;
+    if (host)
+        HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    else
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+    return EZPZ_OK;
+}
+
+// The run, device pointers throughout (but Keep's, see there): the plan's mutex is held, the system's device current, the request
+// checked and samples > 0.
+int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint32_t* positions, const EzpzConstraint* records,
+        uint64_t samples, const EzpzConfig* cfg, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev, const Keep& keep,
+        hipStream_t stream) {
+    release_thread_kernel(sys->device);
+    const size_t n = sys->counts.n_vars, n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords;
+    const uint64_t chunk = r.chunk, blocks = chunk / kBlock;
+    int rc;
+    // ---- what the host writes: behind the last run's launches ----
+    std::vector<unsigned char> tables(r.dists.size() * sizeof(mc::Dist) + r.tab.size() * sizeof(double));
+    if (!r.dists.empty()) std::memcpy(tables.data(), r.dists.data(), r.dists.size() * sizeof(mc::Dist));
+    if (!r.tab.empty()) std::memcpy(tables.data() + r.dists.size() * sizeof(mc::Dist), r.tab.data(), r.tab.size() * sizeof(double));
+    const bool new_tables = tables != P.tables_kept;
+    const bool grows = chunk * n > P.x_in.cap || chunk * n_param > P.params.cap || chunk * n_meas > P.m.cap || chunk > P.status.cap ||
+                       blocks * n_meas * 4 > P.part_f.cap || blocks * (2 * n_meas + 2) > P.part_n.cap || n_meas > P.nominal.cap ||
+                       !P.ticket.p;
+    if (new_tables || grows) {
+        if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
+        P.tables_kept.clear();
+        if ((rc = P.dist.ensure(n_param)) != EZPZ_OK || (rc = P.tab.ensure(4 * n_meas)) != EZPZ_OK) return rc;
+        if (n_param) HIP_TRY(hipMemcpy(P.dist.p, r.dists.data(), n_param * sizeof(mc::Dist), hipMemcpyHostToDevice));
+        if (n_meas) HIP_TRY(hipMemcpy(P.tab.p, r.tab.data(), 4 * n_meas * sizeof(double), hipMemcpyHostToDevice));
+        if ((rc = P.x_in.ensure(chunk * n)) != EZPZ_OK || (rc = P.x_out.ensure(chunk * n)) != EZPZ_OK ||
+            (rc = P.params.ensure(chunk * n_param)) != EZPZ_OK || (rc = P.m.ensure(chunk * n_meas)) != EZPZ_OK ||
+            (rc = P.flags.ensure(chunk * n_meas)) != EZPZ_OK || (rc = P.status.ensure(chunk)) != EZPZ_OK ||
+            (rc = P.ok.ensure(chunk)) != EZPZ_OK || (rc = P.nominal.ensure(n_meas)) != EZPZ_OK ||
+            (rc = P.part_f.ensure(blocks * n_meas * 4)) != EZPZ_OK || (rc = P.part_arg.ensure(blocks * n_meas * 2)) != EZPZ_OK ||
+            (rc = P.part_n.ensure(blocks * (2 * n_meas + 2))) != EZPZ_OK)
+            return rc;
+        if (!P.ticket.p) {
+            if ((rc = P.ticket.ensure(1)) != EZPZ_OK) return rc;
+            HIP_TRY(hipMemset(P.ticket.p, 0, P.ticket.cap * sizeof(unsigned int)));
+        }
+        P.tables_kept = std::move(tables);
+        call_stamp(MC_TABLES_UPLOADED);
+    }
+    if ((rc = P.order.order_behind(stream)) != EZPZ_OK) return rc;
+    // ---- nominal[i] = m(record i, x0), 0 where the guard fires ----
+    if (n_meas && (rc = ezpz_system_measure_device(sys, records, n_meas, x0_dev, 1, P.nominal.p, nullptr, nullptr, stream)) != EZPZ_OK) return rc;
+    if (r.hist_bins && n_meas) HIP_TRY(hipMemsetAsync(hist_dev, 0, n_meas * (r.hist_bins + 2) * sizeof(uint64_t), stream));
+    mc::ReduceArgs a{};
+    a.m = P.m.p;
+    a.flags = P.flags.p;
+    a.status = P.status.p;
+    a.nominal = P.nominal.p;
+    a.lim_lo = r.limits ? P.tab.p : nullptr;
+    a.lim_hi = r.limits ? P.tab.p + n_meas : nullptr;
+    a.hist_lo = P.tab.p + 2 * n_meas;
+    a.hist_scale = P.tab.p + 3 * n_meas;
+    a.samples = samples;
+    a.n_meas = (uint32_t)n_meas;
+    a.hist_bins = n_meas ? r.hist_bins : 0;
+    a.part_d = P.part_f.p;
+    a.part_d2 = a.part_d + blocks * n_meas;
+    a.part_min = a.part_d2 + blocks * n_meas;
+    a.part_max = a.part_min + blocks * n_meas;
+    a.part_argmin = P.part_arg.p;
+    a.part_argmax = a.part_argmin + blocks * n_meas;
+    a.part_valid = P.part_n.p;
+    a.part_in = a.part_valid + blocks * n_meas;
+    a.part_ok = a.part_in + blocks * n_meas;
+    a.part_all_in = a.part_ok + blocks;
+    a.ticket = P.ticket.p;
+    a.ok = P.ok.p;
+    a.stats = stats_dev;
+    a.totals = totals_dev;
+    a.hist = hist_dev;
+    for (uint64_t first = 0; first < samples; first += chunk) {
+        const uint64_t count = std::min<uint64_t>(chunk, samples - first);
+        if (n_param) hipLaunchKernelGGL(mc::mc_sample_kernel, dim3(stride_grid(count * n_param, sys)), dim3(256), 0, stream, P.dist.p, r.seed, first, count, (uint32_t)n_param, P.params.p);
+        if (n) hipLaunchKernelGGL(mc::mc_broadcast_kernel, dim3(stride_grid(count * n, sys)), dim3(256), 0, stream, x0_dev, (uint32_t)n, count, P.x_in.p);
+        HIP_TRY(hipGetLastError());
+        if ((rc = ezpz_system_solve_batch_params_device(sys, P.x_in.p, positions, n_param, P.params.p, count, cfg, P.x_out.p, P.status.p,
+                                                        nullptr, nullptr, 0, stream)) != EZPZ_OK)
+            return rc;
+        if (n_meas && (rc = ezpz_system_measure_device(sys, records, n_meas, P.x_out.p, count, P.m.p, P.flags.p, nullptr, stream)) != EZPZ_OK)
+            return rc;
+        a.first = first;
+        a.count = count;
+        a.first_round = first == 0;
+        hipLaunchKernelGGL(mc::mc_reduce_kernel, dim3((uint32_t)((count + kBlock - 1) / kBlock)), dim3(256), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+        if (keep.params || keep.m || keep.flags || keep.ok) {
+            if (keep.host) HIP_TRY(hipStreamSynchronize(stream));
+            if ((rc = copy_out(keep.params ? keep.params + first * n_param : nullptr, P.params.p, count * n_param * sizeof(double), keep.host, stream)) != EZPZ_OK ||
+                (rc = copy_out(keep.m ? keep.m + first * n_meas : nullptr, P.m.p, count * n_meas * sizeof(double), keep.host, stream)) != EZPZ_OK ||
+                (rc = copy_out(keep.flags ? keep.flags + first * n_meas : nullptr, P.flags.p, count * n_meas, keep.host, stream)) != EZPZ_OK ||
+                (rc = copy_out(keep.ok ? keep.ok + first : nullptr, P.ok.p, count, keep.host, stream)) != EZPZ_OK)
+                return rc;
+        }
+    }
+    call_stamp(MC_LAUNCHED);
+    return P.order.record(stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+void ezpz_default_mc_config(EzpzMcConfig* mc_cfg) {
+    if (!mc_cfg) return;
+    mc_cfg->seed = 0;
+    mc_cfg->chunk = 0;
+    mc_cfg->hist_bins = 0;
+}
+
+int ezpz_mc_sample(uint64_t seed, const EzpzMcDist* dist, const double* nominal, size_t n_param, uint64_t first, size_t count,
+                   double* params_out) {
+    std::vector<mc::Dist> dists;
+    if (int rc = check_dists(dist, nominal, n_param, dists)) return rc;
+    if (count && n_param && !params_out) return EZPZ_ERR_INVALID_ARGUMENT;
+    for (size_t s = 0; s < count; ++s)
+        for (size_t j = 0; j < n_param; ++j) params_out[s * n_param + j] = mc::draw(seed, first + s, (uint32_t)j, dists[j]);
+    return EZPZ_OK;
+}
+
+int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                    const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                    const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                    const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev,
+                                    uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev, uint8_t* keep_flags_dev,
+                                    uint8_t* keep_ok_dev, void* stream) {
+    Request r;
+    if (int rc = check_run(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg,
+                           stats_dev, totals_dev, hist_dev, (hipStream_t)stream, r))
+        return rc;
+    if (samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(sys->device);
+    return run(sys, P, r, x0_dev, positions, records, samples, cfg, stats_dev, totals_dev, hist_dev,
+               Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, (hipStream_t)stream);
+}
+
+int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                             const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo, const double* lim_hi,
+                             const double* hist_lo, const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg,
+                             EzpzMcStats* stats, EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m,
+                             uint8_t* keep_flags, uint8_t* keep_ok) {
+    Request r;
+    if (int rc = check_run(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, stats,
+                           totals, hist, hipStreamPerThread, r))
+        return rc;
+    if (samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(sys->device);
+    const size_t n = sys->counts.n_vars, hist_words = n_meas * (r.hist_bins ? r.hist_bins + 2 : 0);
+    int rc;
+    // (the buffers of an earlier host call are idle: it waited for its launches)
+    if ((rc = P.x0_in.ensure(n)) != EZPZ_OK || (rc = P.stats_out.ensure(n_meas)) != EZPZ_OK || (rc = P.totals_out.ensure(1)) != EZPZ_OK ||
+        (rc = P.hist_out.ensure(hist_words)) != EZPZ_OK)
+        return rc;
+    if (n) HIP_TRY(hipMemcpy(P.x0_in.p, x0, n * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = run(sys, P, r, P.x0_in.p, positions, records, samples, cfg, P.stats_out.p, P.totals_out.p, P.hist_out.p,
+                  Keep{keep_params, keep_m, keep_flags, keep_ok, true}, hipStreamPerThread)) != EZPZ_OK)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
+    if (n_meas) HIP_TRY(hipMemcpy(stats, P.stats_out.p, n_meas * sizeof(EzpzMcStats), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(totals, P.totals_out.p, sizeof(EzpzMcTotals), hipMemcpyDeviceToHost));
+    if (hist_words) HIP_TRY(hipMemcpy(hist, P.hist_out.p, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return EZPZ_OK;
+}
+
+}  // extern "C"

@@ -680,6 +680,102 @@ int ezpz_system_measure_vjp(EzpzSystem* sys, const EzpzConstraint* records, size
 int ezpz_system_measure_vjp_device(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x_dev,
                                    const double* grad_m_dev, size_t batch, double* grad_x_out_dev, void* stream);
 
+/* ---- Monte-Carlo tolerance analysis: sampled driven solves, measured, with statistics reduced on the device (a project
+ * extension) -- the non-linear counterpart of ezpz_system_measure_response's stack-up.  Every driving dimension (the constraints at
+ * `positions`, as ezpz_system_solve_batch_params takes them) is drawn from its tolerance distribution `samples` times, every variant
+ * is solved from x0, the reference dimensions `records` (measurement records, as ezpz_system_measure takes them) are read off each
+ * answer, and what comes back is one EzpzMcStats per record, the totals and an optional histogram: n_meas small records, not
+ * samples x n_vars values.  x0 [n_vars] is expected to be the NOMINAL SOLUTION -- the answer for the nominal values: every variant
+ * starts from it, and nominal[i] of the statistics is measured on it.
+ * THE DRAW.  p[b][j] = nominal[j] + deviation, the deviation of sample b (0-based, 64 bits) for dimension j by dist[j]:
+ *   EZPZ_MC_FIXED    p = nominal[j], as given (nothing is added)
+ *   EZPZ_MC_UNIFORM  a + (b - a) * u,  a <= b the deviations' ends, u in [0, 1)
+ *   EZPZ_MC_NORMAL   a * z,  a = sigma >= 0,  b = the truncation in sigmas: 0 = none, else >= 1
+ *   EZPZ_MC_CORNER   bit c of the sample index ? b : a,  c = the rank of j among the CORNER dimensions of the list (at most 20 of them):
+ *                    samples 0 .. 2^k - 1 are the 2^k corners of k such dimensions
+ * u and z come from Philox4x32-10 with counter (b & 0xffffffff, b >> 32, j, t), t the attempt, and key (seed & 0xffffffff,
+ * seed >> 32), whose words w0..w3 give
+ *   u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53     u1 = ((w0 >> 5) * 2^26 + (w1 >> 6) + 1) * 2^-53     u2 = ((w2 >> 5) * 2^26 + (w3 >> 6)) * 2^-53
+ * (each exact in a double).  UNIFORM takes u of attempt 0.  NORMAL: z = sqrt(-2 * log(u1)) * cos(TWO_PI * u2), TWO_PI the double
+ * nearest 2 pi and the product TWO_PI * u2 rounded once; with a truncation T the attempts 0 .. 15 are tried in order and the first z
+ * with |z| <= T is taken, and if none is, z = copysign(T, z of attempt 15).  No product is contracted into a fused multiply-add, on
+ * the host or on the device.  A draw depends on (seed, b, j) and dist[j] alone: never on the batch, the round, the other dimensions.
+ * ezpz_mc_sample (host only, no device): params_out [count][n_param] = the draws of the samples first .. first + count - 1, from the
+ * sampler's one source.  FIXED, UNIFORM and CORNER draws are bit-identical on the host and on the device; a NORMAL draw can differ
+ * there in the last bits of log, cos and sqrt -- the ONLY thing in this section that is not bit-reproducible between the two.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing written: an unknown kind, a non-finite a, b or nominal, a > b for UNIFORM, sigma < 0, a
+ * truncation in (0, 1) (or negative), more than 20 CORNER dimensions, dist or nominal NULL with n_param > 0.
+ * THE RUN.  ezpz_system_tolerance_mc[_device] works in rounds of `chunk` samples (rounded up to a multiple of 256; 0: the library's
+ * choice, 65536 or less for a large system), everything on one stream: the sampler writes the round's params, a second kernel its
+ * copies of x0, ezpz_system_solve_batch_params_device solves them -- that entry itself: whatever params route the system has, the
+ * fronts included, and a system it declines is declined here with the same error -- ezpz_system_measure_device measures the answers
+ * (m and flags), and the reduction kernel folds the round into the results.  Memory is bounded by chunk, not by samples.
+ * nominal == NULL: the system's own params at `positions`.  n_param == 0 is legal: every sample is the same solve.
+ * Sample b is OK when its EzpzStatus has converged != 0 and n_unsatisfied == 0.  It is VALID FOR record i when it is ok, flag bit 0
+ * of (b, i) is clear and m is finite.  stats[i], over the samples valid for i, with d = m - nominal[i] and nominal[i] = m(record
+ * i, x0) measured once before round 0 (0 where the guard fires):
+ *   n_valid;  sum_d = sum of d;  sum_d2 = sum of (d * d), the product rounded, then added;  min, max;  argmin, argmax: the sample
+ *   indices, the lowest among equals;  n_in: the count with lim_lo[i] <= m <= lim_hi[i] (n_valid without limits);
+ *   mean = nominal + sum_d / n_valid;  var = (sum_d2 - sum_d * sum_d / n_valid) / (n_valid - 1).
+ * No valid sample: mean and var NaN, min = +inf, max = -inf, argmin = argmax = UINT64_MAX; one: var NaN.
+ * hist [n_meas][hist_bins + 2] (hist_bins > 0): under, the bins, over -- a valid m counts in bin floor((m - hist_lo[i]) * scale_i),
+ * scale_i = hist_bins / (hist_hi[i] - hist_lo[i]) computed once on the host; m < hist_lo[i] is under, a bin >= hist_bins over.
+ * totals: samples; n_ok, the ok samples; n_all_in, the samples valid for and inside the limits of EVERY record.  Variants that do not
+ * assemble are counted (samples - n_ok), never averaged.  The angle kinds' branch cut at +-pi is the measurement's and is not
+ * unwrapped: a reference angle that straddles it has samples near both ends, and its mean says little.
+ * THE ORDER OF EVERY FLOATING SUM is fixed by this interface.  Block q is the samples [256 q, 256 q + 256).  Inside a block the 256
+ * leaves -- +0.0 for a sample that is invalid or past `samples` -- are summed by the adjacent-pair tree: for h = 1, 2, .. 128,
+ * v[t] += v[t + h] for every t that is a multiple of 2 h.  The blocks' sums are then added left to right from +0.0.  There are no
+ * floating-point atomics (counts and histogram bins are integers).  Therefore every output has the same bits for any chunk, any
+ * stream and any device, and the host form gives exactly the device form's bits -- given the same draws and the same answers of
+ * the two entries above, which are reproducible themselves.
+ * keep_params [samples][n_param], keep_m [samples][n_meas], keep_flags [samples][n_meas], keep_ok [samples] bytes (each optional,
+ * NULL): the samples themselves.  m and flags of a sample that is not ok are those of whatever the solve left.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: every argument error of the params entry (the list, a
+ * system it declines, a capture its fronts refuse) and of the measure entry (the records); every error of ezpz_mc_sample;
+ * hist_bins > 64; hist_bins > 0 without ranges or with hist_hi <= hist_lo; one limit array without the other, or lim_lo > lim_hi;
+ * stats or totals (or x0, or hist with hist_bins > 0) NULL with samples > 0.  samples == 0: EZPZ_OK after those checks, nothing written.
+ * The _device form takes device pointers for x0 and every output (keep_* included) and host pointers for positions, dist, nominal,
+ * records, limits and ranges.  It enqueues on `stream`; distributions, limits or ranges other than the last run's, or a workspace
+ * that has to grow, are first uploaded behind the last run's launches (repeat them, and a run only enqueues -- as far as the two
+ * entries do).  Runs on one EzpzSystem go one behind the other whatever their streams.  Stream capture, thread safety and the
+ * ordering against other launches on the system: those of the two entries it is made of.  mc == NULL: ezpz_default_mc_config's
+ * values (seed 0, chunk 0, hist_bins 0); cfg as for the params entry. */
+#define EZPZ_MC_FIXED 0u
+#define EZPZ_MC_UNIFORM 1u
+#define EZPZ_MC_NORMAL 2u
+#define EZPZ_MC_CORNER 3u
+typedef struct EzpzMcDist { /* 24 bytes */
+    uint32_t kind, reserved;
+    double a, b;
+} EzpzMcDist;
+typedef struct EzpzMcConfig { /* 16 bytes */
+    uint64_t seed;
+    uint32_t chunk;     /* samples per round; 0 = the library's choice */
+    uint32_t hist_bins; /* 0 .. 64 */
+} EzpzMcConfig;
+typedef struct EzpzMcStats { /* one per measurement record; 88 bytes */
+    uint64_t n_valid, n_in, argmin, argmax;
+    double nominal, sum_d, sum_d2, mean, var, min, max;
+} EzpzMcStats;
+typedef struct EzpzMcTotals { /* 24 bytes */
+    uint64_t samples, n_ok, n_all_in;
+} EzpzMcTotals;
+void ezpz_default_mc_config(EzpzMcConfig* mc);
+int ezpz_mc_sample(uint64_t seed, const EzpzMcDist* dist, const double* nominal, size_t n_param, uint64_t first, size_t count,
+                   double* params_out);
+int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                             const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                             const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                             const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals, uint64_t* hist,
+                             double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok);
+int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                    const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                    const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                    uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                    EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                    uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, void* stream);
+
 /* ---- ezpz::solve for a batch (new; SURVEY.md 8f #3: priority tiers + weights end-to-end on device batches) --------
  * `batch` systems share the request list and differ in their guesses (x0 AoS [batch][n_vars], id == index).  Per
  * system exactly the semantics of ezpz_solve: LineSide / CircleSide inferred from that system's own guesses
