@@ -85,6 +85,20 @@ class CMcConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("hist_bins", C.c_uint32)]
 
 
+class CSeekConfig(C.Structure):  # EzpzSeekConfig; the arrays are host pointers, NULL = the default for every entry
+    _fields_ = [("weight", C.c_void_p), ("tol", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p), ("scale", C.c_void_p),
+                ("max_iterations", C.c_uint32), ("chunk", C.c_uint32), ("mu0", C.c_double), ("mu_up", C.c_double),
+                ("mu_down", C.c_double), ("mu_min", C.c_double), ("mu_max", C.c_double), ("step_tol", C.c_double),
+                ("sens_lambda", C.c_double), ("inner", CConfig)]
+
+
+SEEK_INFO_DTYPE = np.dtype([("status", "<u4"), ("iterations", "<u4"), ("accepted", "<u4"), ("rejected", "<u4"), ("cost0", "<f8"),
+                            ("cost", "<f8"), ("worst", "<f8"), ("mu", "<f8")])  # EzpzSeekInfo
+assert C.sizeof(CSeekConfig) == 136 and SEEK_INFO_DTYPE.itemsize == 48
+SEEK_STATUS = ("REACHED", "MINIMUM", "ITERATIONS", "STALLED", "START_FAILED")  # EZPZ_SEEK_*
+SEEK_STEP = ("TRIAL", "MINIMUM", "PIVOT")  # EZPZ_SEEK_STEP_*
+
+
 class CGuardStep(C.Structure):
     _fields_ = [("reached", C.c_double), ("attempts", C.c_uint32), ("accepted", C.c_uint32)]
 
@@ -141,6 +155,7 @@ EXPORTS = [
     "ezpz_constraint_measure", "ezpz_system_measure", "ezpz_system_measure_device", "ezpz_system_measure_response",
     "ezpz_system_measure_response_device", "ezpz_system_measure_vjp", "ezpz_system_measure_vjp_device",
     "ezpz_default_mc_config", "ezpz_mc_sample", "ezpz_system_tolerance_mc", "ezpz_system_tolerance_mc_device",
+    "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
 ]
 
 _lib = None
@@ -206,6 +221,13 @@ def lib():
                                            C.POINTER(CConfig), vp, vp, vp, vp, vp, vp, vp]
     L.ezpz_system_tolerance_mc_device.restype = C.c_int
     L.ezpz_system_tolerance_mc_device.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp]
+    L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
+    L.ezpz_seek_step.restype = C.c_int
+    L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]
+    L.ezpz_system_seek_targets.restype = C.c_int
+    L.ezpz_system_seek_targets.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, sz, C.POINTER(CSeekConfig), vp, vp, vp, vp, vp]
+    L.ezpz_system_seek_targets_device.restype = C.c_int
+    L.ezpz_system_seek_targets_device.argtypes = L.ezpz_system_seek_targets.argtypes + [vp]
     L.ezpz_current_device.restype = C.c_int
     L.ezpz_current_device.argtypes = []
     L.ezpz_host_register.restype = C.c_int

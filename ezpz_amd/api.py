@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, MC_DIST_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, CConfig, CGuardConfig, CMcConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, MC_DIST_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CConfig, CGuardConfig, CMcConfig, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1257,6 +1257,130 @@ class System:
                                                    stream or None)
         if rc != 0:
             raise NonLinearSystemError(rc)
+
+    # ---- dimension targets (ezpz_system_seek_targets) ---------------------------------------------------------------------------
+    def seek_targets(self, x0, positions, params0, records, targets, config: Optional["SeekConfig"] = None,
+                     want_trace: bool = False) -> "SeekResult":
+        """`ezpz_system_seek_targets`: which values of the driving dimensions (`positions`) put the reference dimensions `records`
+        on `targets` [batch, n_meas]?  x0 [batch, n_vars] are the starts (normally the current solution), params0 [batch, n_param]
+        the dimensions' current values.  A projected Levenberg-Marquardt iteration per system, its rounds on the device; a seek
+        never leaves its last accepted, assembled answer.  Returns a `SeekResult`."""
+        pos = self._positions(positions)
+        recs = stack_records(records)
+        k, n_param = len(recs), len(pos)
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
+        if targets.ndim != 2 or targets.shape[1] != k:
+            raise ValueError(f"targets: expected [batch, {k}], got {targets.shape}")
+        batch = targets.shape[0]
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        params0 = np.ascontiguousarray(params0, dtype=np.float64)
+        if x0.shape != (batch, self.n_vars) or params0.shape != (batch, n_param):
+            raise ValueError(f"x0, params0: expected ({batch}, {self.n_vars}) and ({batch}, {n_param}), got {x0.shape} and {params0.shape}")
+        c, keep = (config or SeekConfig())._c(n_param, k)
+        params, x, m = np.zeros((batch, n_param)), np.zeros((batch, self.n_vars)), np.zeros((batch, k))
+        info = np.zeros(batch, dtype=SEEK_INFO_DTYPE)
+        trace = np.zeros((batch, c.max_iterations + 1)) if want_trace else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_seek_targets(self._h, ptr(x0), ptr(pos), n_param, ptr(params0), ptr(recs), k, ptr(targets), batch,
+                                            C.byref(c), ptr(params), ptr(x), ptr(m), ptr(info), ptr(trace))
+        del keep
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return SeekResult(params, x, m, info, trace)
+
+    def seek_targets_device(self, x0_ptr: int, positions, params0_ptr: int, records, targets_ptr: int, batch: int, params_ptr: int,
+                            x_ptr: int, m_ptr: int, info_ptr: int, trace_ptr: int = 0, config: Optional["SeekConfig"] = None,
+                            stream: int = 0) -> None:
+        """Device pointers for x0, params0, targets and every output (info: SEEK_INFO_DTYPE [batch], trace: [batch, 1 +
+        max_iterations]) and a hipStream_t handle; positions, records and the configuration stay host values.  Enqueues 1 +
+        max_iterations rounds per chunk, with no host read-back between them."""
+        pos = self._positions(positions)
+        recs = stack_records(records)
+        c, keep = (config or SeekConfig())._c(len(pos), len(recs))
+        rc = lib().ezpz_system_seek_targets_device(self._h, x0_ptr or None, pos.ctypes.data if len(pos) else None, len(pos),
+                                                   params0_ptr or None, recs.ctypes.data if len(recs) else None, len(recs),
+                                                   targets_ptr or None, int(batch), C.byref(c), params_ptr or None, x_ptr or None,
+                                                   m_ptr or None, info_ptr or None, trace_ptr or None, stream or None)
+        del keep
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
+
+@dataclass
+class SeekConfig:
+    """EzpzSeekConfig, the policy of a seek: weight, tol [n_meas] and lo, hi, scale [n_param] (a scalar is every entry's value;
+    None: the library's default -- 1, 1e-6, -inf, +inf, 1), the damping's schedule, the step's end test, the lambda of the
+    sensitivities (None: the inner config's initial_lambda), the inner solves' Config and the systems per pass (0: the library's
+    choice).  Policy defaults (ezpz_default_seek_config), not measurements."""
+
+    weight: object = None
+    tol: object = None
+    lo: object = None
+    hi: object = None
+    scale: object = None
+    max_iterations: int = 40
+    mu0: float = 1e-3
+    mu_up: float = 10.0
+    mu_down: float = 0.1
+    mu_min: float = 1e-12
+    mu_max: float = 1e12
+    step_tol: float = 1e-12
+    sens_lambda: Optional[float] = None
+    inner: Optional[Config] = None
+    chunk: int = 0
+
+    def _c(self, n_param: int, n_meas: int):
+        """(the C record, the arrays it points into: keep them alive for the call)."""
+        keep = []
+
+        def table(what, value, n):
+            if value is None:
+                return None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=np.float64), (n,)))
+            keep.append(a)
+            return a.ctypes.data if n else None
+
+        inner = self.inner or Config()
+        lam = inner.initial_lambda if self.sens_lambda is None else float(self.sens_lambda)
+        c = CSeekConfig(table("weight", self.weight, n_meas), table("tol", self.tol, n_meas), table("lo", self.lo, n_param),
+                        table("hi", self.hi, n_param), table("scale", self.scale, n_param), int(self.max_iterations), int(self.chunk),
+                        float(self.mu0), float(self.mu_up), float(self.mu_down), float(self.mu_min), float(self.mu_max),
+                        float(self.step_tol), lam, inner._c())
+        return c, keep
+
+
+class SeekResult:
+    """What `System.seek_targets` returns: params [batch, n_param], x [batch, n_vars] and m [batch, n_meas] of every system's
+    last accepted answer, info (SEEK_INFO_DTYPE [batch]: status, iterations, accepted, rejected, cost0, cost, worst, mu) with its
+    fields as attributes, status_names, and cost_trace [batch, 1 + max_iterations] (None unless asked for)."""
+
+    def __init__(self, params, x, m, info, cost_trace):
+        self.params, self.x, self.m, self.info, self.cost_trace = params, x, m, info, cost_trace
+        for f in SEEK_INFO_DTYPE.names:
+            setattr(self, f, info[f])
+
+    @property
+    def status_names(self):
+        return [SEEK_STATUS[s] if s < len(SEEK_STATUS) else str(s) for s in self.info["status"]]
+
+
+def seek_step(p, m, D, targets, mu: float, config: Optional[SeekConfig] = None):
+    """`ezpz_seek_step`: one step of the seek's iteration from (p [n_param], m [n_meas], D [n_meas, n_param]) towards targets
+    [n_meas] with the damping mu -- (kind, p_trial, delta, held) with kind one of "TRIAL", "MINIMUM", "PIVOT" and held a bit per
+    dimension.  Host only."""
+    p, m, targets = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (p, m, targets))
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.shape != (len(m), len(p)) or len(targets) != len(m):
+        raise ValueError(f"D, targets: expected ({len(m)}, {len(p)}) and ({len(m)},), got {D.shape} and {targets.shape}")
+    c, keep = (config or SeekConfig())._c(len(p), len(m))
+    p_trial, delta, held = np.zeros(len(p)), np.zeros(len(p)), C.c_uint32(0)
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    rc = lib().ezpz_seek_step(len(p), len(m), ptr(p), ptr(m), ptr(D), ptr(targets), C.byref(c), float(mu), ptr(p_trial), ptr(delta),
+                              C.byref(held))
+    del keep
+    if rc < 0:
+        raise NonLinearSystemError(rc)
+    return SEEK_STEP[rc], p_trial, delta, held.value
 
 
 class McDist:

@@ -42,6 +42,9 @@ enum CallStage : uint32_t {
     // ezpz_system_tolerance_mc_device (tolerance_mc.hip), around the stamps of the entries its rounds are made of
     MC_TABLES_UPLOADED = 60,  // other distributions, limits or ranges than the last run's, or a workspace that had to grow: waited, copied
     MC_LAUNCHED = 61,         // every round of the run enqueued
+    // ezpz_system_seek_targets_device (seek.hip), around the stamps of the entries its rounds are made of
+    SEEK_TABLES_UPLOADED = 70,  // other tables than the last run's, or a workspace that had to grow: waited, copied
+    SEEK_LAUNCHED = 71,         // every round of every chunk enqueued (the host form: run)
 };
 
 struct CallTrace {

@@ -776,6 +776,111 @@ int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const
                                     EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
                                     uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, void* stream);
 
+/* ---- Dimension targets: solve driving dimensions for measured targets (a project extension) -- the inverse of the
+ * entries above: which values of the driving dimensions (the constraints at `positions`, as ezpz_system_solve_batch_params takes
+ * them) put the reference dimensions `records` (measurement records, as ezpz_system_measure takes them; host memory in both forms)
+ * on targets[b][i]?  A projected Levenberg-Marquardt iteration in parameter space, per system, every system of the batch on its
+ * own.  x0 [batch][n_vars]: the starts, normally the current solution; params0 [batch][n_param]; targets [batch][n_meas].
+ * EzpzSeekConfig: weight [n_meas] (>= 0; 0: the record is reported, not sought), tol [n_meas] (absolute, in the record's unit),
+ * lo, hi [n_param] (+-inf allowed; lo == hi freezes a dimension), scale [n_param] (> 0: the size of a typical change, so degrees and
+ * lengths mix) -- each array host memory, NULL = the default for every entry (1, 1e-6, -inf, +inf, 1).  ezpz_default_seek_config
+ * fills: the arrays NULL, max_iterations 40, mu0 1e-3, mu_up 10, mu_down 0.1, mu_min 1e-12, mu_max 1e12, step_tol 1e-12, inner =
+ * ezpz_default_config, sens_lambda = inner.initial_lambda, chunk 0.  These are POLICY DEFAULTS, not measurements.
+ * THE ALGORITHM, for one system; w, t, tol indexed by record i, lo, hi, s (scale) by dimension r.  Only + - * /, comparisons and fabs
+ * are used, no product is contracted into a fused multiply-add on either side, every sum runs i ascending from +0.0: the step is
+ * the same bits on the host, on the device and in Python floats.  finite(v) is fabs(v) <= DBL_MAX.
+ * EVALUATE(x_from, q): x = the solve of ezpz_system_solve_batch_params from x_from with q (cfg->inner); S, sens = the answer of
+ *   ezpz_system_param_sensitivity at (x, q) with lambda = sens_lambda; m, flags = ezpz_system_measure at x; D = ezpz_system_
+ *   measure_response of (x, S).  It is GOOD iff the solve has converged != 0 and n_unsatisfied == 0, sens == 0, no record with
+ *   w > 0 has flag bit 0, and every m[i] and D[i][r] is finite.  e_i = w_i * (t_i - m_i); cost = sum of e_i * e_i; worst = the
+ *   largest fabs(t_i - m_i) over the records with w_i > 0 (from +0.0); REACHED(m) iff fabs(t_i - m_i) <= tol_i for each of them.
+ * START: p = clamp(params0) (v < lo ? lo : v > hi ? hi : v); EVALUATE(x0, p).  Not good: status START_FAILED, params_out = p, x_out =
+ *   the x0 row, m_out NaN, cost0 = cost = worst = NaN, mu = mu0, and the system is finished.  Else commit (x, m, D, cost), cost0 =
+ *   cost, mu = mu0, it = 0, and if REACHED(m): status REACHED.  Else go to NEXT.
+ * NEXT, from the committed (p, m, D) with mu -- STEP is ezpz_seek_step:
+ *   D'[i][r] = (w_i * D[i][r]) * s_r;  A[r][c] = sum_i D'[i][r] * D'[i][c];  g[r] = sum_i D'[i][r] * e_i.
+ *   Dimension r is HELD for this step iff lo_r == hi_r, or p_r == lo_r and g_r < 0, or p_r == hi_r and g_r > 0; held dimensions are
+ *   taken out of the system (the bound would only clip the step: a step along the others keeps the bound and still descends).
+ *   amax = the largest A[r][r] over the free r (from +0.0; a NaN never wins);  f = 1e-2 * amax, raised to 1e-300 if below;
+ *   M = A over the free dimensions with M[r][r] = A[r][r] + mu * (A[r][r] > f ? A[r][r] : f).  The relative floor keeps a dimension
+ *   whose column of D (nearly) vanishes at this point from taking an unbounded step.
+ *   M = L diag(d) L^T without square roots, free k ascending: d_k = M[k][k]; a d_k that is not > 0 or not finite: PIVOT.  Then for the
+ *   free i > k and free j > k: M[i][j] = M[i][j] - (M[i][k] * M[j][k]) / d_k (the product first: both triangles keep the same bits).
+ *   y = g; free k ascending: y_i = y_i - (M[i][k] / d_k) * y_k for the free i > k.  v_r = y_r / d_r.  Then free i descending:
+ *   v_k = v_k - (M[i][k] / d_k) * v_i for the free k < i (M[i][k] as it stood when k was the pivot).  A v_r that is not finite: PIVOT.
+ *   delta_r = s_r * v_r (held: +0.0);  q = p_r + delta_r;  p_trial_r = clamp(q) (held: p_r).
+ *   MINIMUM iff no dimension is free, or fabs(delta_r) <= step_tol * (fabs(p_r) + step_tol) for every free r, or p_trial == p.
+ *   The end tests, in this order: STEP says MINIMUM: status MINIMUM.  `stalled` is set: status STALLED.  it == max_iterations:
+ *   status ITERATIONS.  Else it += 1, and on PIVOT the iteration is REJECTED (below) without a trial and NEXT runs again; else
+ *   EVALUATE(the committed x, p_trial) and the iteration is ACCEPTED iff it is good and its cost < the committed cost.
+ *   ACCEPTED: commit (p_trial, x, m, D, cost, worst); accepted += 1; mu = mu * mu_down, raised to mu_min if below; REACHED(m):
+ *   status REACHED.  REJECTED: rejected += 1; if mu >= mu_max: stalled is set, else mu = mu * mu_up, lowered to mu_max if above.
+ *   cost_trace[it] = the committed cost after iteration it, either way.  Then NEXT.
+ * A seek never leaves its last accepted, assembled answer -- the promise guarded sweeps make: params_out, x_out, m_out are the last
+ * commit's.  EzpzSeekInfo (48 bytes): status, iterations (it), accepted, rejected, cost0, cost, worst, mu.  cost_trace_out
+ * (optional) [batch][1 + max_iterations]: [0] = cost0, [k] as above for k <= iterations, NaN beyond (all NaN on START_FAILED).
+ * A finished system is frozen: later rounds evaluate it again and nothing of it is read, so a system's outputs depend on its own
+ * inputs alone -- not on the batch, its place in it, the chunk, the stream, or how many rounds its neighbours need.
+ * ezpz_seek_step (host only, no device; the lanes' one __host__ __device__ body, run lane after lane): STEP for p, m, targets and D
+ * [n_meas][n_param] as ezpz_system_measure_response writes it, with cfg's weight, lo, hi, scale and step_tol.  Returns
+ * EZPZ_SEEK_STEP_TRIAL, _MINIMUM or _PIVOT (on PIVOT p_trial = p and delta = +0.0), or an error; held_out (optional): bit r set
+ * where dimension r was held.  Non-finite m, D entries are legal here and end, as the rules say, in PIVOT or a held dimension.
+ * THE RUN is rounds on one stream.  A round is ezpz_system_solve_batch_params_device, ezpz_system_param_sensitivity_device,
+ * ezpz_system_measure_device and ezpz_system_measure_response_device -- those entries themselves, with their routes (the fronts
+ * included), locks, kept tables and ordering; a system the params or the sensitivity entry declines is declined here with the
+ * same error before anything is enqueued -- then seek_step_kernel (verdict, bookkeeping, the next STEP; a team of 4, 8 or 16 lanes
+ * per system by n_param) and seek_commit_kernel (the accepted rows of x).  The _device form enqueues 1 + max_iterations rounds per
+ * chunk with no host read-back between them; the host form reads one counter of unfinished systems per round and stops at zero:
+ * the same bytes, because finished systems are frozen.  chunk: systems per pass, rounded up to a multiple of 64 (0: the library's
+ * choice, at most 65536 and few enough that S [chunk][n_param][n_vars] stays within 256 MiB); each chunk runs its whole loop.
+ * EZPZ_ERR_TOO_LARGE: n_param > EZPZ_SEEK_MAX_PARAMS or n_meas > EZPZ_SEEK_MAX_TARGETS, max_iterations > 65535.  EZPZ_ERR_INVALID_ARGUMENT,
+ * nothing enqueued, no output touched: the argument errors of the four entries (the list, the records, a system they decline, a
+ * capture the fronts refuse); lo > hi or a NaN bound; a negative or non-finite weight or tol; a scale that is not > 0 and finite; a
+ * non-finite target or params0 (host form); mu_up <= 1, mu_down >= 1 or <= 0, mu_min <= 0, mu_min > mu0 or mu0 > mu_max or any of
+ * them not finite; a negative or non-finite step_tol or sens_lambda; a required pointer NULL (x0 with n_vars > 0, params0, targets,
+ * params_out, x_out, m_out, info_out).  batch == 0, n_param == 0 or n_meas == 0: EZPZ_OK, nothing written, after the checks that need
+ * no values.  The _device form takes device pointers for x0, params0, targets and every output (targets are then not checked), host
+ * pointers for the rest.  x0 may be x_out itself, nothing else may overlap.  Tables other than the last run's, or a workspace that
+ * has to grow, are uploaded behind the last run's launches first.  Runs on one EzpzSystem go one behind the other whatever their
+ * streams; stream capture, thread safety and ordering against other launches: those of the four entries.  cfg == NULL: the defaults. */
+#define EZPZ_SEEK_MAX_PARAMS 16u
+#define EZPZ_SEEK_MAX_TARGETS 64u
+#define EZPZ_SEEK_REACHED 0u
+#define EZPZ_SEEK_MINIMUM 1u
+#define EZPZ_SEEK_ITERATIONS 2u
+#define EZPZ_SEEK_STALLED 3u
+#define EZPZ_SEEK_START_FAILED 4u
+#define EZPZ_SEEK_STEP_TRIAL 0
+#define EZPZ_SEEK_STEP_MINIMUM 1
+#define EZPZ_SEEK_STEP_PIVOT 2
+typedef struct EzpzSeekConfig { /* 136 bytes */
+    const double* weight; /* [n_meas] */
+    const double* tol;    /* [n_meas] */
+    const double* lo;     /* [n_param] */
+    const double* hi;     /* [n_param] */
+    const double* scale;  /* [n_param] */
+    uint32_t max_iterations;
+    uint32_t chunk;
+    double mu0, mu_up, mu_down, mu_min, mu_max, step_tol, sens_lambda;
+    EzpzConfig inner;
+} EzpzSeekConfig;
+typedef struct EzpzSeekInfo { /* one per system; 48 bytes */
+    uint32_t status, iterations, accepted, rejected;
+    double cost0, cost, worst, mu;
+} EzpzSeekInfo;
+void ezpz_default_seek_config(EzpzSeekConfig* cfg);
+int ezpz_seek_step(size_t n_param, size_t n_meas, const double* p, const double* m, const double* D, const double* targets,
+                   const EzpzSeekConfig* cfg, double mu, double* p_trial_out, double* delta_out, uint32_t* held_out);
+int ezpz_system_seek_targets(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const double* params0,
+                             const EzpzConstraint* records, size_t n_meas, const double* targets, size_t batch,
+                             const EzpzSeekConfig* cfg, double* params_out, double* x_out, double* m_out, EzpzSeekInfo* info_out,
+                             double* cost_trace_out);
+int ezpz_system_seek_targets_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                    const double* params0_dev, const EzpzConstraint* records, size_t n_meas,
+                                    const double* targets_dev, size_t batch, const EzpzSeekConfig* cfg, double* params_out_dev,
+                                    double* x_out_dev, double* m_out_dev, EzpzSeekInfo* info_out_dev, double* cost_trace_out_dev,
+                                    void* stream);
+
 /* ---- ezpz::solve for a batch (new; SURVEY.md 8f #3: priority tiers + weights end-to-end on device batches) --------
  * `batch` systems share the request list and differ in their guesses (x0 AoS [batch][n_vars], id == index).  Per
  * system exactly the semantics of ezpz_solve: LineSide / CircleSide inferred from that system's own guesses
