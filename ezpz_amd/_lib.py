@@ -23,6 +23,10 @@ MC_STATS_DTYPE = np.dtype([("n_valid", "<u8"), ("n_in", "<u8"), ("argmin", "<u8"
                            ("sum_d", "<f8"), ("sum_d2", "<f8"), ("mean", "<f8"), ("var", "<f8"), ("min", "<f8"), ("max", "<f8")])  # EzpzMcStats
 MC_TOTALS_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_all_in", "<u8")])  # EzpzMcTotals
 assert MC_DIST_DTYPE.itemsize == 24 and MC_STATS_DTYPE.itemsize == 88 and MC_TOTALS_DTYPE.itemsize == 24
+BRANCH_INFO_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_branches", "<u8"), ("n_overflow", "<u8")])  # EzpzBranchInfo
+BRANCH_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("dist_inf", "<f8"), ("status", STATUS_DTYPE)])  # EzpzBranch
+assert BRANCH_INFO_DTYPE.itemsize == 32 and BRANCH_DTYPE.itemsize == 56
+BRANCH_MAX, BRANCH_NOT_OK, BRANCH_OVERFLOW = 256, -1, -2  # EZPZ_BRANCH_*
 
 
 class CConfig(C.Structure):
@@ -83,6 +87,10 @@ class CGuardConfig(C.Structure):
 
 class CMcConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("hist_bins", C.c_uint32)]
+
+
+class CBranchConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("max_branches", C.c_uint32), ("eps_abs", C.c_double), ("eps_rel", C.c_double)]
 
 
 class CSeekConfig(C.Structure):  # EzpzSeekConfig; the arrays are host pointers, NULL = the default for every entry
@@ -156,6 +164,8 @@ EXPORTS = [
     "ezpz_system_measure_response_device", "ezpz_system_measure_vjp", "ezpz_system_measure_vjp_device",
     "ezpz_default_mc_config", "ezpz_mc_sample", "ezpz_system_tolerance_mc", "ezpz_system_tolerance_mc_device",
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
+    "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
+    "ezpz_system_solve_branches_device",
 ]
 
 _lib = None
@@ -228,6 +238,16 @@ def lib():
     L.ezpz_system_seek_targets.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, sz, C.POINTER(CSeekConfig), vp, vp, vp, vp, vp]
     L.ezpz_system_seek_targets_device.restype = C.c_int
     L.ezpz_system_seek_targets_device.argtypes = L.ezpz_system_seek_targets.argtypes + [vp]
+    L.ezpz_default_branch_config.restype = None
+    L.ezpz_default_branch_config.argtypes = [C.POINTER(CBranchConfig)]
+    L.ezpz_branch_cluster.restype = C.c_int
+    L.ezpz_branch_cluster.argtypes = [vp, vp, vp, sz, C.c_uint64, sz, C.POINTER(CBranchConfig), vp, vp, vp, vp]
+    L.ezpz_branch_cluster_device.restype = C.c_int
+    L.ezpz_branch_cluster_device.argtypes = L.ezpz_branch_cluster.argtypes + [vp]
+    L.ezpz_system_solve_branches.restype = C.c_int
+    L.ezpz_system_solve_branches.argtypes = [vp, vp, vp, vp, sz, C.c_uint64, C.POINTER(CBranchConfig), C.POINTER(CConfig), vp, vp, vp, vp]
+    L.ezpz_system_solve_branches_device.restype = C.c_int
+    L.ezpz_system_solve_branches_device.argtypes = L.ezpz_system_solve_branches.argtypes + [vp]
     L.ezpz_current_device.restype = C.c_int
     L.ezpz_current_device.argtypes = []
     L.ezpz_host_register.restype = C.c_int

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, MC_DIST_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CConfig, CGuardConfig, CMcConfig, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1258,6 +1258,47 @@ class System:
         if rc != 0:
             raise NonLinearSystemError(rc)
 
+    # ---- solution branches (ezpz_system_solve_branches) --------------------------------------------------------------------------
+    def _branch_request(self, dists, compare, seed, branch):
+        d = mc_dists(dists)
+        if len(d) != self.n_vars:
+            raise ValueError(f"dists: one per variable ({self.n_vars}), got {len(d)}")
+        return d, _compare_mask(compare, self.n_vars), (branch or BranchConfig())._c(seed)
+
+    def solve_branches(self, x0, dists, samples: int, seed: int = 0, compare=None, config: Optional[Config] = None,
+                       branch: Optional["BranchConfig"] = None, keep: bool = False) -> "BranchResult":
+        """`ezpz_system_solve_branches`: every base x0[b] ([n_vars] or [batch, n_vars]) gets `samples` starts -- sample 0 the base
+        itself, the others drawn around it by dists (one `McDist` per variable; `mc_sample(seed, dists, x0[b], first, count)` gives
+        the same starts) -- every start is solved, and the answers are clustered on the device by the sequential leader rule.
+        compare: a mask [n_vars] of the compared variables (non-zero: compared), None for all; branch: eps, max_branches and
+        chunk; keep: also every sample's label.  The same bytes whatever the chunk."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1, max(self.n_vars, 1))
+        d, mask, bc = self._branch_request(dists, compare, seed, branch)
+        batch, samples = x0.shape[0], int(samples)
+        info, branches, x, labels = _branch_outputs(batch, samples, self.n_vars, bc.max_branches, keep)
+        cfg = (config or Config())._c()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_solve_branches(self._h, ptr(x0), ptr(d), ptr(mask), batch, samples, C.byref(bc), C.byref(cfg), ptr(info),
+                                              ptr(branches), ptr(x), ptr(labels))
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return BranchResult(info, branches, x, labels)
+
+    def solve_branches_device(self, x0_ptr: int, dists, batch: int, samples: int, info_ptr: int, branches_ptr: int, x_branch_ptr: int,
+                              keep_label_ptr: int = 0, seed: int = 0, compare=None, config: Optional[Config] = None,
+                              branch: Optional["BranchConfig"] = None, stream: int = 0) -> None:
+        """Device pointers for x0 [batch, n_vars] and every output (info: BRANCH_INFO_DTYPE [batch], branches: BRANCH_DTYPE
+        [batch, max_branches], x_branch: float64 [batch, max_branches, n_vars], keep_label: int32 [batch, samples]) and a hipStream_t
+        handle; dists, compare and the configs stay host values.  Enqueues only once the run's tables are the last run's."""
+        d, mask, bc = self._branch_request(dists, compare, seed, branch)
+        cfg = (config or Config())._c()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_solve_branches_device(self._h, x0_ptr or None, ptr(d), ptr(mask), int(batch), int(samples), C.byref(bc),
+                                                     C.byref(cfg), info_ptr or None, branches_ptr or None, x_branch_ptr or None,
+                                                     keep_label_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
     # ---- dimension targets (ezpz_system_seek_targets) ---------------------------------------------------------------------------
     def seek_targets(self, x0, positions, params0, records, targets, config: Optional["SeekConfig"] = None,
                      want_trace: bool = False) -> "SeekResult":
@@ -1451,6 +1492,67 @@ class McResult:
         self.samples, self.n_ok, self.n_all_in = (int(totals[f][0]) for f in MC_TOTALS_DTYPE.names)
         if kept is not None:
             self.params, self.m, self.flags, self.ok = kept
+
+
+class BranchConfig:
+    """EzpzBranchConfig but the seed: eps_abs, eps_rel (two answers are the same branch when every compared variable differs by at
+    most eps_abs + eps_rel * max(|a|, |b|)), max_branches (1 .. 256) and chunk (samples per base and round; 0: the library's choice)."""
+
+    def __init__(self, eps_abs: float = 1e-5, eps_rel: float = 1e-5, max_branches: int = 32, chunk: int = 0):
+        self.eps_abs, self.eps_rel, self.max_branches, self.chunk = float(eps_abs), float(eps_rel), int(max_branches), int(chunk)
+
+    def _c(self, seed: int = 0) -> CBranchConfig:
+        return CBranchConfig(int(seed), self.chunk, self.max_branches, self.eps_abs, self.eps_rel)
+
+
+class BranchResult:
+    """What `System.solve_branches` and `cluster_branches` return: info (BRANCH_INFO_DTYPE [batch]), branches (BRANCH_DTYPE
+    [batch, max_branches]; the slots at and beyond n_branches are zero), x [batch, max_branches, n_vars], the leaders' answers, and
+    labels [batch, samples] (the slot, -1 not ok, -2 overflow; None without keep)."""
+
+    def __init__(self, info, branches, x, labels):
+        self.info, self.branches, self.x, self.labels = info, branches, x, labels
+        self.n_branches = info["n_branches"].astype(np.int64)
+
+    def nearest(self, base: int = 0) -> np.ndarray:
+        """The slots of a base by dist_inf, the nearest first (equal distances: the lower slot)."""
+        n = int(self.n_branches[base])
+        return np.argsort(self.branches["dist_inf"][base, :n], kind="stable")
+
+
+def _compare_mask(compare, n_vars: int):
+    if compare is None:
+        return None
+    compare = np.asarray(compare)
+    if compare.shape != (n_vars,):
+        raise ValueError(f"compare: expected a mask of shape ({n_vars},), got {compare.shape}")
+    return np.ascontiguousarray(compare != 0, dtype=np.uint8)
+
+
+def _branch_outputs(batch: int, samples: int, n_vars: int, max_branches: int, keep: bool):
+    return (np.zeros(batch, dtype=BRANCH_INFO_DTYPE), np.zeros((batch, max_branches), dtype=BRANCH_DTYPE),
+            np.zeros((batch, max_branches, n_vars)), np.zeros((batch, samples), np.int32) if keep else None)
+
+
+def cluster_branches(x, ok=None, compare=None, branch: Optional[BranchConfig] = None, keep: bool = False) -> BranchResult:
+    """`ezpz_branch_cluster`: the clustering alone on x [batch, samples, n_vars] (or [samples, n_vars]: one base) with the flags ok
+    [batch, samples] (None: every one set) -- no system involved.  dist_inf is measured from sample 0 of the base."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError(f"x: expected [batch, samples, n_vars], got {x.shape}")
+    batch, samples, n_vars = x.shape
+    if ok is not None:
+        ok = np.ascontiguousarray(np.asarray(ok).reshape(batch, samples) != 0, dtype=np.uint8)
+    mask, bc = _compare_mask(compare, n_vars), (branch or BranchConfig())._c()
+    info, branches, xb, labels = _branch_outputs(batch, samples, n_vars, bc.max_branches, keep)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = lib().ezpz_branch_cluster(ptr(x), ptr(ok), ptr(mask), batch, samples, n_vars, C.byref(bc), ptr(info), ptr(branches), ptr(xb),
+                                   ptr(labels))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return BranchResult(info, branches, xb, labels)
 
 
 def constraint_measure(record, x):

@@ -45,6 +45,9 @@ enum CallStage : uint32_t {
     // ezpz_system_seek_targets_device (seek.hip), around the stamps of the entries its rounds are made of
     SEEK_TABLES_UPLOADED = 70,  // other tables than the last run's, or a workspace that had to grow: waited, copied
     SEEK_LAUNCHED = 71,         // every round of every chunk enqueued (the host form: run)
+    // ezpz_branch_cluster_device and ezpz_system_solve_branches_device (branches.hip), the latter around the stamps of the solve entry
+    BRANCH_TABLES_UPLOADED = 80,  // other compared variables or distributions than the last run's, or a workspace that had to grow: waited, copied
+    BRANCH_LAUNCHED = 81,         // every round of the run enqueued
 };
 
 struct CallTrace {

@@ -10,6 +10,7 @@
 //   measure.hip   reference dimensions: a record list measured at given values, its response to S, stack-up and vjp
 //   tolerance_mc.hip  Monte-Carlo tolerance analysis: sampled driven solves, measured, their statistics reduced on the device
 //   seek.hip      dimension targets: driving dimensions solved for measured targets, rounds of the driven entries kept on the device
+//   branches.hip  solution branches: sampled multi-start solves, their answers clustered on the device by the sequential leader rule
 //   driven.cpp    the entries that take a `positions` list of driven constraints: the list check, and the one call path behind
 //                 params.hip and sweep.hip (driven_params.hpp); sensitivity.hip and front_sens.hip keep their lists in a KeptList
 //   mixed.hip, multi.cpp, solve.cpp  on top of the C ABI (heterogeneous batches, several devices, solve / solve_inner)
@@ -413,6 +414,10 @@ struct EzpzSystem {
     // ezpz_system_seek_targets (seek.hip): its SeekPlan -- the rounds' workspace, the tables, the host form's buffers, and the mutex
     // and event of its runs (created under mu on first use)
     std::shared_ptr<void> seek;
+    // ezpz_system_solve_branches (branches.hip): its BranchPlan -- the round's starts, answers, labels and list of unmatched samples,
+    // the compared variables' and the sampler's tables, the host form's buffers, and the mutex and event of its runs (created under
+    // mu on first use)
+    std::shared_ptr<void> branches;
     ~EzpzSystem() {
         if (dev_program) (void)hipFree(dev_program);
         if (dev_grid_blob) (void)hipFree(dev_grid_blob);

@@ -881,6 +881,91 @@ int ezpz_system_seek_targets_device(EzpzSystem* sys, const double* x0_dev, const
                                     double* x_out_dev, double* m_out_dev, EzpzSeekInfo* info_out_dev, double* cost_trace_out_dev,
                                     void* stream);
 
+/* ---- Solution branches: sampled multi-start solves, their answers clustered on the device (a project extension).
+ * A sketch usually has several configurations -- a triangle's apex on either side of its base, k such choices, 2^k assemblies -- and
+ * a solve returns the one its start leads to.  These entries answer "which configurations exist, and which is nearest to my start":
+ * `samples` starts scattered around a base x0 are solved in one launch per round, and what comes back is the B distinct answers
+ * with the number of starts that reached each: small records, not samples x n_vars values.
+ * THE RULE.  SAME BRANCH: samples i and j lie in one branch when, for every compared variable v,
+ *   |x_i[v] - x_j[v]| <= eps_abs + eps_rel * max(|x_i[v]|, |x_j[v]|)
+ * with the right side evaluated as written -- the product rounded, then the sum; never contracted into a fused multiply-add.
+ * `compare` [n_vars] bytes choose the compared variables (non-zero: compared), NULL means all of them; the mask exists for
+ * under-constrained sketches, whose free variables form a continuum.  The rule is comparisons only: there is no floating sum, so
+ * nothing depends on an order of addition.  OK: a sample is ok when its flag is set -- its `ok` byte is non-zero (the clustering
+ * alone) or its EzpzStatus has converged != 0 and n_unsatisfied == 0 (the run; the Monte-Carlo entry's rule) -- and its compared
+ * values are finite.  BRANCHES are those of the SEQUENTIAL LEADER pass over the samples of a base in index order: an ok sample joins
+ * the first (lowest-slot) leader whose branch it is in; otherwise it becomes the next leader while fewer than max_branches exist;
+ * otherwise it is OVERFLOW.  Slots are in order of discovery, so a leader is the lowest sample index of its branch.  Membership is
+ * tested against the LEADER, never against other members: the relation is not transitive, and the pass does not pretend it is.
+ * tests/branch_ref.py restates the rule in a dozen lines.
+ * EzpzBranchConfig: seed; chunk, the samples per base and round (0: the library's choice, 65536 or fewer where batch x n_vars is
+ * large; rounded up to a multiple of 256 as the Monte-Carlo entry rounds its own); max_branches, 1 .. EZPZ_BRANCH_MAX (default 32);
+ * eps_abs, eps_rel (default 1e-5 each).  WHERE 1e-5 COMES FROM: on chains of 2, 3 and 5 triangles and on 2 and 3 independent
+ * triangle blocks, 256 and 1024 uniform starts each, the answers of one branch differed by at most 1.1e-7 in the max-norm under the
+ * default EzpzConfig (the LM loop stops at residual_tolerance 1e-8) and distinct branches by at least 3.87; labels at 1e-6 and 1e-4
+ * were identical.  The default is about 100 x that spread.  A looser residual_tolerance wants a looser eps.
+ * OUTPUTS.  info [batch]: samples; n_ok; n_branches; n_overflow.  branches [batch][max_branches], one EzpzBranch per slot: first, the
+ * leader's sample index; count, the samples in the branch (the leader included); dist_inf, the largest |x_leader[v] - origin[v]| over
+ * the compared variables -- a maximum from +0.0, not a sum; a NaN difference never wins -- where the origin is x0[b] for the run and
+ * sample 0 of the base for the clustering alone; status, the leader's EzpzStatus (all zero for the clustering alone).  x_branch
+ * [batch][max_branches][n_vars]: the leaders' full answers, uncompared variables included.  keep_label [batch][samples] int32
+ * (optional, NULL): the sample's slot, EZPZ_BRANCH_NOT_OK (-1) or EZPZ_BRANCH_OVERFLOW (-2).  Slots at and beyond n_branches are
+ * zero-filled.  n_ok = the sum of the counts + n_overflow.
+ * ezpz_branch_cluster[_device] is the clustering alone on the caller's data, x [batch][samples][n_vars] with ok [batch][samples]
+ * bytes (NULL: every flag set) -- no system involved; useful on the kept samples of a Monte-Carlo run.
+ * ezpz_system_solve_branches[_device] is THE RUN: every base x0[b] ([batch][n_vars]) gets `samples` starts.  Sample 0 is x0[b]
+ * itself, so slot 0 is what the plain solve finds whenever that assembles; sample s >= 1 starts at the draw of (seed, s, v) by dist[v]
+ * (EzpzMcDist, the sampler of the Monte-Carlo section) around the nominal x0[b][v]: ezpz_mc_sample(seed, dist, x0[b], n_vars, first,
+ * count) reproduces the starts on the host, bitwise for FIXED / UNIFORM / CORNER, and a FIXED variable keeps its value.  Rounds of
+ * `chunk` samples per base (round 0 is at most 1024: it meets no leaders) run on one stream: the start kernel,
+ * ezpz_system_solve_batch_device on batch x count systems -- that entry itself, whatever kernel serves the system, and an error it
+ * returns is returned here -- then the clustering of the round: branch_assign_kernel compares every sample with the leaders known
+ * when the round begins, branch_elect_kernel (one workgroup per base) runs the leader pass over what is left.  The leader table
+ * persists in `branches` and `x_branch` between rounds: every output has the same bytes for any chunk and any stream, given the same
+ * answers of the solve entry (see there for when those depend on a call's size).  Memory is bounded by batch x chunk, not by samples;
+ * the host form of the clustering alone holds the caller's x on the device whole.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: max_branches 0 or above EZPZ_BRANCH_MAX; a negative or
+ * non-finite eps; a `compare` that selects nothing (n_vars == 0 included); every error of ezpz_mc_sample for dist (the host form
+ * checks it with every x0 row as the nominal, the _device form, which cannot read x0, with zeros); sys NULL; x (or x0), info, branches
+ * or x_branch NULL with batch > 0 and samples > 0.  EZPZ_ERR_TOO_LARGE, likewise: samples >= 2^48, batch >= 2^32, or a round of
+ * more than 2^40 values (batch x chunk x n_vars; the index arithmetic's bounds).  samples == 0 or batch == 0: EZPZ_OK after those checks, nothing written.
+ * The _device forms take device pointers for x, ok, x0 and every output, host pointers for compare, dist and the configs, and only
+ * enqueue on `stream` once the tables are the last run's and the workspace is large enough (else those are first uploaded behind the
+ * last run's launches).  Runs on one EzpzSystem -- and clusterings on one device, whose workspace is the process's -- go one behind
+ * the other whatever their streams.  Stream capture, thread safety and the ordering against other launches on the system: those of
+ * the solve entry.  cfg / bcfg == NULL: ezpz_default_branch_config's values; cfg of the run as for the solve entry. */
+#define EZPZ_BRANCH_MAX 256u
+#define EZPZ_BRANCH_NOT_OK (-1)
+#define EZPZ_BRANCH_OVERFLOW (-2)
+typedef struct EzpzBranchConfig { /* 32 bytes */
+    uint64_t seed;
+    uint32_t chunk;        /* samples per base and round; 0 = the library's choice */
+    uint32_t max_branches; /* 1 .. EZPZ_BRANCH_MAX */
+    double eps_abs, eps_rel;
+} EzpzBranchConfig;
+typedef struct EzpzBranchInfo { /* one per base; 32 bytes */
+    uint64_t samples, n_ok, n_branches, n_overflow;
+} EzpzBranchInfo;
+typedef struct EzpzBranch { /* one per slot; 56 bytes */
+    uint64_t first, count;
+    double dist_inf;
+    EzpzStatus status;
+} EzpzBranch;
+void ezpz_default_branch_config(EzpzBranchConfig* bcfg);
+int ezpz_branch_cluster(const double* x, const uint8_t* ok, const uint8_t* compare, size_t batch, uint64_t samples, size_t n_vars,
+                        const EzpzBranchConfig* cfg, EzpzBranchInfo* info, EzpzBranch* branches, double* x_branch,
+                        int32_t* keep_label);
+int ezpz_branch_cluster_device(const double* x_dev, const uint8_t* ok_dev, const uint8_t* compare, size_t batch, uint64_t samples,
+                               size_t n_vars, const EzpzBranchConfig* cfg, EzpzBranchInfo* info_dev, EzpzBranch* branches_dev,
+                               double* x_branch_dev, int32_t* keep_label_dev, void* stream);
+int ezpz_system_solve_branches(EzpzSystem* sys, const double* x0, const EzpzMcDist* dist, const uint8_t* compare, size_t batch,
+                               uint64_t samples, const EzpzBranchConfig* bcfg, const EzpzConfig* cfg, EzpzBranchInfo* info,
+                               EzpzBranch* branches, double* x_branch, int32_t* keep_label);
+int ezpz_system_solve_branches_device(EzpzSystem* sys, const double* x0_dev, const EzpzMcDist* dist, const uint8_t* compare,
+                                      size_t batch, uint64_t samples, const EzpzBranchConfig* bcfg, const EzpzConfig* cfg,
+                                      EzpzBranchInfo* info_dev, EzpzBranch* branches_dev, double* x_branch_dev,
+                                      int32_t* keep_label_dev, void* stream);
+
 /* ---- ezpz::solve for a batch (new; SURVEY.md 8f #3: priority tiers + weights end-to-end on device batches) --------
  * `batch` systems share the request list and differ in their guesses (x0 AoS [batch][n_vars], id == index).  Per
  * system exactly the semantics of ezpz_solve: LineSide / CircleSide inferred from that system's own guesses
