@@ -23,6 +23,9 @@ MC_STATS_DTYPE = np.dtype([("n_valid", "<u8"), ("n_in", "<u8"), ("argmin", "<u8"
                            ("sum_d", "<f8"), ("sum_d2", "<f8"), ("mean", "<f8"), ("var", "<f8"), ("min", "<f8"), ("max", "<f8")])  # EzpzMcStats
 MC_TOTALS_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_all_in", "<u8")])  # EzpzMcTotals
 assert MC_DIST_DTYPE.itemsize == 24 and MC_STATS_DTYPE.itemsize == 88 and MC_TOTALS_DTYPE.itemsize == 24
+MC_MOMENTS_INFO_DTYPE = np.dtype([("samples", "<u8"), ("n_complete", "<u8")])  # EzpzMcMomentsInfo
+MC_MOMENT_MAX = 64  # EZPZ_MC_MOMENT_MAX
+assert MC_MOMENTS_INFO_DTYPE.itemsize == 16
 BRANCH_INFO_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_branches", "<u8"), ("n_overflow", "<u8")])  # EzpzBranchInfo
 BRANCH_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("dist_inf", "<f8"), ("status", STATUS_DTYPE)])  # EzpzBranch
 assert BRANCH_INFO_DTYPE.itemsize == 32 and BRANCH_DTYPE.itemsize == 56
@@ -87,6 +90,10 @@ class CGuardConfig(C.Structure):
 
 class CMcConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("hist_bins", C.c_uint32)]
+
+
+class CMcContribConfig(C.Structure):
+    _fields_ = [("pivot_rel", C.c_double), ("reserved", C.c_uint64)]
 
 
 class CBranchConfig(C.Structure):
@@ -163,6 +170,8 @@ EXPORTS = [
     "ezpz_constraint_measure", "ezpz_system_measure", "ezpz_system_measure_device", "ezpz_system_measure_response",
     "ezpz_system_measure_response_device", "ezpz_system_measure_vjp", "ezpz_system_measure_vjp_device",
     "ezpz_default_mc_config", "ezpz_mc_sample", "ezpz_system_tolerance_mc", "ezpz_system_tolerance_mc_device",
+    "ezpz_default_mc_contrib_config", "ezpz_mc_contributors", "ezpz_mc_moments", "ezpz_mc_moments_device",
+    "ezpz_system_tolerance_mc_contrib", "ezpz_system_tolerance_mc_contrib_device",
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
     "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
     "ezpz_system_solve_branches_device",
@@ -231,6 +240,18 @@ def lib():
                                            C.POINTER(CConfig), vp, vp, vp, vp, vp, vp, vp]
     L.ezpz_system_tolerance_mc_device.restype = C.c_int
     L.ezpz_system_tolerance_mc_device.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp]
+    L.ezpz_default_mc_contrib_config.restype = None
+    L.ezpz_default_mc_contrib_config.argtypes = [C.POINTER(CMcContribConfig)]
+    L.ezpz_mc_contributors.restype = C.c_int
+    L.ezpz_mc_contributors.argtypes = [vp, C.c_uint64, sz, sz, C.POINTER(CMcContribConfig), vp, vp, vp, vp, vp]
+    L.ezpz_mc_moments.restype = C.c_int
+    L.ezpz_mc_moments.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, sz, sz, u32, vp, vp]
+    L.ezpz_mc_moments_device.restype = C.c_int
+    L.ezpz_mc_moments_device.argtypes = L.ezpz_mc_moments.argtypes + [vp]
+    L.ezpz_system_tolerance_mc_contrib.restype = C.c_int
+    L.ezpz_system_tolerance_mc_contrib.argtypes = L.ezpz_system_tolerance_mc.argtypes + [C.POINTER(CMcContribConfig), vp, vp, vp, vp, vp, vp, vp]
+    L.ezpz_system_tolerance_mc_contrib_device.restype = C.c_int
+    L.ezpz_system_tolerance_mc_contrib_device.argtypes = L.ezpz_system_tolerance_mc_contrib.argtypes + [vp]
     L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
     L.ezpz_seek_step.restype = C.c_int
     L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]

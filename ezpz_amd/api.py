@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1212,13 +1212,16 @@ class System:
         return pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc
 
     def tolerance_mc(self, x0, positions, dists, records, samples: int, seed: int = 0, nominal=None, limits=None, hist=None,
-                     chunk: int = 0, keep: bool = False, config: Optional[Config] = None) -> "McResult":
+                     chunk: int = 0, keep: bool = False, config: Optional[Config] = None, contributors: bool = False,
+                     pivot_rel: Optional[float] = None) -> "McResult":
         """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
         solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
         statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
         limits = (lo, hi), each [n_meas] or a scalar: the yield's limits; hist = (lo, hi, bins): a histogram of `bins` <= 64 bins per
         record with an under and an over count; chunk: samples per round (0: the library's choice); keep: also every sample's
-        params, m, flags and ok.  The sums' order is fixed: the same bits whatever the chunk."""
+        params, m, flags and ok.  The sums' order is fixed: the same bits whatever the chunk.
+        contributors: the same run through `ezpz_system_tolerance_mc_contrib` -- the result also has moments, n_complete, cov, beta,
+        contrib, r2, dropped and corr (`McContributors`); pivot_rel: EzpzMcContribConfig's (None: the library's default)."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
         if x0.size != self.n_vars:
             raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
@@ -1232,29 +1235,44 @@ class System:
                 np.zeros(samples, np.uint8)) if keep else (None,) * 4
         cfg = (config or Config())._c()
         ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_tolerance_mc(self._h, ptr(x0), ptr(pos), n_param, ptr(d), ptr(nominal), ptr(recs), k, ptr(lim_lo), ptr(lim_hi),
-                                            ptr(hist_lo), ptr(hist_hi), samples, C.byref(mc), C.byref(cfg), stats.ctypes.data,
-                                            totals.ctypes.data, ptr(counts), *(ptr(a) for a in kept))
+        args = (self._h, ptr(x0), ptr(pos), n_param, ptr(d), ptr(nominal), ptr(recs), k, ptr(lim_lo), ptr(lim_hi), ptr(hist_lo), ptr(hist_hi),
+                samples, C.byref(mc), C.byref(cfg), stats.ctypes.data, totals.ctypes.data, ptr(counts), *(ptr(a) for a in kept))
+        if not contributors:
+            rc = lib().ezpz_system_tolerance_mc(*args)
+            if rc != 0:
+                raise NonLinearSystemError(rc)
+            return McResult(stats, totals, counts, kept if keep else None)
+        cc = _contrib_config(pivot_rel)
+        moments, info, out = _contrib_outputs(n_param, k)
+        rc = lib().ezpz_system_tolerance_mc_contrib(*args, C.byref(cc), moments.ctypes.data, info.ctypes.data, *(ptr(a) for a in out))
         if rc != 0:
             raise NonLinearSystemError(rc)
-        return McResult(stats, totals, counts, kept if keep else None)
+        n_complete = int(info["n_complete"][0]) if samples else 0
+        return McResult(stats, totals, counts, kept if keep else None, McContributors(moments, n_complete, n_param, k, *out))
 
     def tolerance_mc_device(self, x0_ptr: int, positions, dists, records, samples: int, stats_ptr: int, totals_ptr: int, hist_ptr: int = 0,
                             seed: int = 0, nominal=None, limits=None, hist=None, chunk: int = 0, keep_params_ptr: int = 0,
                             keep_m_ptr: int = 0, keep_flags_ptr: int = 0, keep_ok_ptr: int = 0, stream: int = 0,
-                            config: Optional[Config] = None) -> None:
+                            config: Optional[Config] = None, moments_ptr: int = 0, info_ptr: int = 0, cov_ptr: int = 0, beta_ptr: int = 0,
+                            contrib_ptr: int = 0, r2_ptr: int = 0, dropped_ptr: int = 0, pivot_rel: Optional[float] = None) -> None:
         """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], hist: uint64
         [n_meas, bins + 2]) and a hipStream_t handle; positions, dists, records, nominal, limits and hist = (lo, hi, bins) stay host
-        values.  Enqueues only once the run's tables are the last run's."""
+        values.  Enqueues only once the run's tables are the last run's.  With moments_ptr the run goes through
+        `ezpz_system_tolerance_mc_contrib_device` and fills moments [K + K (K + 1) / 2], info (MC_MOMENTS_INFO_DTYPE [1]), cov [K, K],
+        beta and contrib [n_meas, n_param], r2 [n_meas] and dropped (uint64 [1]) as well, K = n_param + n_meas."""
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
         ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_tolerance_mc_device(self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs),
-                                                   ptr(lim_lo), ptr(lim_hi), ptr(hist_lo), ptr(hist_hi), int(samples), C.byref(mc),
-                                                   C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
-                                                   keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None,
-                                                   stream or None)
+        args = (self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs), ptr(lim_lo), ptr(lim_hi), ptr(hist_lo),
+                ptr(hist_hi), int(samples), C.byref(mc), C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
+                keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None)
+        if moments_ptr:
+            cc = _contrib_config(pivot_rel)
+            rc = lib().ezpz_system_tolerance_mc_contrib_device(*args, C.byref(cc), moments_ptr, info_ptr or None, cov_ptr or None, beta_ptr or None,
+                                                               contrib_ptr or None, r2_ptr or None, dropped_ptr or None, stream or None)
+        else:
+            rc = lib().ezpz_system_tolerance_mc_device(*args, stream or None)
         if rc != 0:
             raise NonLinearSystemError(rc)
 
@@ -1482,16 +1500,98 @@ def mc_sample(seed: int, dists, nominal, first: int, count: int) -> np.ndarray:
 class McResult:
     """What `System.tolerance_mc` returns: numpy fields per measurement record -- n_valid, mean, std, var, min, max, argmin, argmax,
     n_in, nominal, sum_d, sum_d2 -- hist [n_meas, bins + 2] (under, the bins, over; None without a histogram), the totals samples,
-    n_ok and n_all_in, and with keep the samples: params, m, flags, ok.  `stats` and `totals` are the library's records."""
+    n_ok and n_all_in, and with keep the samples: params, m, flags, ok.  `stats` and `totals` are the library's records.  A run with
+    contributors also has moments, n_complete, cov, beta, contrib, r2, dropped (those of its `contributors`, a `McContributors`) and
+    `corr`."""
 
-    def __init__(self, stats, totals, hist, kept):
+    def __init__(self, stats, totals, hist, kept, contributors=None):
         self.stats, self.totals, self.hist = stats, totals, hist
+        if contributors is not None:
+            self.contributors = contributors
+            for f in ("moments", "n_complete", "cov", "beta", "contrib", "r2", "dropped"):
+                setattr(self, f, getattr(contributors, f))
         for f in MC_STATS_DTYPE.names:
             setattr(self, f, stats[f])
         self.std = np.sqrt(stats["var"])
         self.samples, self.n_ok, self.n_all_in = (int(totals[f][0]) for f in MC_TOTALS_DTYPE.names)
         if kept is not None:
             self.params, self.m, self.flags, self.ok = kept
+
+    @property
+    def corr(self) -> np.ndarray:
+        """cov / sqrt(outer(diag)) of a run with contributors."""
+        return self.contributors.corr
+
+
+class McContributors:
+    """What `mc_contributors` returns and a `tolerance_mc` run with contributors carries: moments and n_complete as given, cov
+    [K, K] over (driving | reference) dimensions, beta and contrib [n_meas, n_param], r2 [n_meas], dropped (the library's bit mask)
+    with dropped_mask [n_param], and corr."""
+
+    def __init__(self, moments, n_complete, n_param, n_meas, cov, beta, contrib, r2, dropped):
+        self.moments, self.n_complete, self.n_param, self.n_meas = moments, int(n_complete), n_param, n_meas
+        self.cov, self.beta, self.contrib, self.r2 = cov, beta, contrib, r2
+        self.dropped = int(dropped[0])
+        self.dropped_mask = np.array([(self.dropped >> j) & 1 for j in range(n_param)], dtype=bool)
+
+    @property
+    def corr(self) -> np.ndarray:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.cov / np.sqrt(np.outer(np.diag(self.cov), np.diag(self.cov)))
+
+
+def _contrib_config(pivot_rel) -> CMcContribConfig:
+    cc = CMcContribConfig()
+    lib().ezpz_default_mc_contrib_config(C.byref(cc))
+    if pivot_rel is not None:
+        cc.pivot_rel = float(pivot_rel)
+    return cc
+
+
+def _contrib_outputs(n_param: int, n_meas: int):
+    K = n_param + n_meas
+    return (np.zeros(K + K * (K + 1) // 2), np.zeros(1, dtype=MC_MOMENTS_INFO_DTYPE),
+            (np.zeros((K, K)), np.zeros((n_meas, n_param)), np.zeros((n_meas, n_param)), np.zeros(n_meas), np.zeros(1, np.uint64)))
+
+
+def mc_moments(params, m, flags, ok, nominal_p, nominal_m, chunk: int = 0):
+    """`ezpz_mc_moments`: (moments [K + K (K + 1) / 2], n_complete) of the samples params [samples, n_param], m [samples, n_meas],
+    flags [samples, n_meas] (None: clear) and ok [samples] (None: every one set) about nominal_p and nominal_m -- the reduction
+    alone, on the device, no system involved; useful on the kept samples of any run."""
+    params, m = np.ascontiguousarray(params, dtype=np.float64), np.ascontiguousarray(m, dtype=np.float64)
+    if params.ndim != 2 or m.ndim != 2 or len(params) != len(m):
+        raise ValueError(f"params [samples, n_param] and m [samples, n_meas]: got {params.shape} and {m.shape}")
+    samples, n_param, n_meas = len(params), params.shape[1], m.shape[1]
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(samples, n_meas)
+    if ok is not None:
+        ok = np.ascontiguousarray(np.asarray(ok).reshape(samples) != 0, dtype=np.uint8)
+    nominal_p, nominal_m = np.ascontiguousarray(nominal_p, dtype=np.float64), np.ascontiguousarray(nominal_m, dtype=np.float64)
+    if nominal_p.shape != (n_param,) or nominal_m.shape != (n_meas,):
+        raise ValueError(f"nominal_p ({n_param},) and nominal_m ({n_meas},): got {nominal_p.shape} and {nominal_m.shape}")
+    moments, info, _ = _contrib_outputs(n_param, n_meas)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = lib().ezpz_mc_moments(ptr(params), ptr(m), ptr(flags), ptr(ok), ptr(nominal_p), ptr(nominal_m), samples, n_param, n_meas, int(chunk),
+                               ptr(moments), info.ctypes.data)
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return moments, int(info["n_complete"][0])
+
+
+def mc_contributors(moments, n_complete: int, n_param: int, n_meas: int, pivot_rel: Optional[float] = None) -> McContributors:
+    """`ezpz_mc_contributors`: the closing step on moments [K + K (K + 1) / 2] of n_complete samples.  Host only."""
+    n_param, n_meas = int(n_param), int(n_meas)
+    K = n_param + n_meas
+    moments = np.ascontiguousarray(moments, dtype=np.float64)
+    if not 1 <= K <= MC_MOMENT_MAX or moments.shape != (K + K * (K + 1) // 2,):
+        raise ValueError(f"moments: expected K + K (K + 1) / 2 values with 1 <= K = {K} <= {MC_MOMENT_MAX}, got {moments.shape}")
+    cc = _contrib_config(pivot_rel)
+    _, _, out = _contrib_outputs(n_param, n_meas)
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    rc = lib().ezpz_mc_contributors(moments.ctypes.data, int(n_complete), n_param, n_meas, C.byref(cc), *(ptr(a) for a in out))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return McContributors(moments, n_complete, n_param, n_meas, *out)
 
 
 class BranchConfig:

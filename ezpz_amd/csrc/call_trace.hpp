@@ -48,6 +48,9 @@ enum CallStage : uint32_t {
     // ezpz_branch_cluster_device and ezpz_system_solve_branches_device (branches.hip), the latter around the stamps of the solve entry
     BRANCH_TABLES_UPLOADED = 80,  // other compared variables or distributions than the last run's, or a workspace that had to grow: waited, copied
     BRANCH_LAUNCHED = 81,         // every round of the run enqueued
+    // ezpz_mc_moments_device (mc_moments.hip)
+    MOMENTS_WORKSPACE_GROWN = 90,  // a workspace that had to grow: waited for the last call's launches, allocated
+    MOMENTS_LAUNCHED = 91,         // every round of the reduction enqueued
 };
 
 struct CallTrace {

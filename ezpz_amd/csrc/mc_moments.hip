@@ -1,0 +1,201 @@
+// Tolerance contributors (include/ezpz_amd.h: ezpz_mc_contributors, ezpz_mc_moments and its _device form): the host
+// side of mc_moments.hip.hpp -- the checks, the closing step's host entry, the reduction's workspace and launches (shared with the
+// run, ezpz_system_tolerance_mc_contrib in tolerance_mc.hip) and the reduction alone on a caller's samples, on a workspace the
+// process owns per device.
+#define EZPZ_MCM_KERNELS
+#include "mc_moments.hip.hpp"
+
+using namespace ezpz;
+
+namespace ezpz {
+namespace mcm {
+
+static_assert(sizeof(EzpzMcContribConfig) == 16 && sizeof(EzpzMcMomentsInfo) == 16, "the layouts include/ezpz_amd.h documents");
+
+int MomentWork::ensure(uint64_t blocks, uint32_t K) {
+    int rc;
+    if ((rc = part.ensure(blocks * entries_of(K))) != EZPZ_OK || (rc = part_n.ensure(blocks)) != EZPZ_OK) return rc;
+    if (!ticket.p) {
+        if ((rc = ticket.ensure(1)) != EZPZ_OK) return rc;
+        HIP_TRY(hipMemset(ticket.p, 0, ticket.cap * sizeof(unsigned int)));
+    }
+    return EZPZ_OK;
+}
+
+int enqueue_moments(MomentWork& work, MomentArgs a, hipStream_t stream) {
+    a.part = work.part.p;
+    a.part_n = work.part_n.p;
+    a.ticket = work.ticket.p;
+    const uint32_t blocks = (uint32_t)((a.count + 255) / 256), K = a.k + a.n_meas;
+    hipLaunchKernelGGL(mc_moments_kernel, dim3(blocks), dim3(256), (size_t)kTile * K * sizeof(double), stream, a);
+    HIP_TRY(hipGetLastError());
+    return EZPZ_OK;
+}
+
+int enqueue_contributors(const ContribArgs& a, hipStream_t stream) {
+    const size_t lds = ((size_t)a.k * a.k + a.k) * sizeof(double) + (a.k + 7) / 8 * 8;
+    hipLaunchKernelGGL(mc_contrib_kernel, dim3(1), dim3(256), lds, stream, a);
+    HIP_TRY(hipGetLastError());
+    return EZPZ_OK;
+}
+
+}  // namespace mcm
+}  // namespace ezpz
+
+namespace {
+
+using namespace ezpz::mcm;
+
+constexpr uint64_t kBlock = 256;
+constexpr uint64_t kDefaultChunk = 65536;
+
+// ezpz_mc_moments has no system: its workspace is the process's, one per device (never destroyed: the runtime may be gone first)
+struct MomentPlan {
+    std::mutex mu;  // a call holds it from its first allocation to its last enqueue
+    LaunchOrder order;  // the completion of the last call's launches
+    MomentWork work;
+    // the host form's buffers: a round of the samples, the nominals, the outputs
+    DevBuf<double> params, m, nominal, moments_out;
+    DevBuf<uint8_t> flags, ok;
+    DevBuf<EzpzMcMomentsInfo> info_out;
+};
+
+MomentPlan* plan_of_device(int device) {
+    static std::mutex mu;
+    static MomentPlan* plans[16] = {};
+    if (device < 0 || device >= 16) return nullptr;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!plans[device]) plans[device] = new MomentPlan;
+    return plans[device];
+}
+
+// Every argument error of the reduction alone, before anything is enqueued or written; the pointers are only compared with NULL.
+int check_moments(const void* params, const void* m, const void* nominal_p, const void* nominal_m, uint64_t samples, size_t n_param,
+                  size_t n_meas, uint32_t chunk_in, const void* moments, const void* info, uint64_t& chunk) {
+    if (int rc = check_shape(n_param, n_meas)) return rc;
+    if (samples && (!moments || !info || (n_param && (!params || !nominal_p)) || (n_meas && (!m || !nominal_m)))) return EZPZ_ERR_INVALID_ARGUMENT;
+    if (samples > 0xFFFFFFFFFFFFull) return EZPZ_ERR_TOO_LARGE;
+    chunk = chunk_in ? chunk_in : kDefaultChunk;
+    chunk = (std::min<uint64_t>(chunk, 1ull << 30) + kBlock - 1) / kBlock * kBlock;
+    chunk = std::min<uint64_t>(chunk, (std::max<uint64_t>(samples, 1) + kBlock - 1) / kBlock * kBlock);
+    return EZPZ_OK;
+}
+
+int grow(MomentPlan& P, uint64_t chunk, uint32_t K) {
+    if (!P.work.grows(chunk / kBlock, K)) return EZPZ_OK;
+    int rc;
+    if ((rc = P.order.before_overwrite()) != EZPZ_OK || (rc = P.work.ensure(chunk / kBlock, K)) != EZPZ_OK) return rc;
+    call_stamp(MOMENTS_WORKSPACE_GROWN);
+    return EZPZ_OK;
+}
+
+MomentArgs args_of(const double* nominal_p, const double* nominal_m, uint64_t samples, size_t n_param, size_t n_meas, double* moments,
+                   EzpzMcMomentsInfo* info) {
+    MomentArgs a{};
+    a.nominal_p = nominal_p;
+    a.nominal_m = nominal_m;
+    a.samples = samples;
+    a.k = (uint32_t)n_param;
+    a.n_meas = (uint32_t)n_meas;
+    a.moments = moments;
+    a.info = info;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ezpz_default_mc_contrib_config(EzpzMcContribConfig* cc) {
+    if (cc) default_config(cc);
+}
+
+int ezpz_mc_contributors(const double* moments, uint64_t n_complete, size_t n_param, size_t n_meas, const EzpzMcContribConfig* cc,
+                         double* cov, double* beta, double* contrib, double* r2, uint64_t* dropped) {
+    return contributors_host(moments, n_complete, n_param, n_meas, cc, cov, beta, contrib, r2, dropped);
+}
+
+int ezpz_mc_moments_device(const double* params_dev, const double* m_dev, const uint8_t* flags_dev, const uint8_t* ok_dev,
+                           const double* nominal_p_dev, const double* nominal_m_dev, uint64_t samples, size_t n_param, size_t n_meas,
+                           uint32_t chunk_in, double* moments_dev, EzpzMcMomentsInfo* info_dev, void* stream_) {
+    uint64_t chunk = 0;
+    if (int rc = check_moments(params_dev, m_dev, nominal_p_dev, nominal_m_dev, samples, n_param, n_meas, chunk_in, moments_dev, info_dev, chunk))
+        return rc;
+    if (samples == 0) return EZPZ_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    int device = -1;
+    if (hipGetDevice(&device) != hipSuccess) {
+        (void)hipGetLastError();
+        return EZPZ_ERR_NO_DEVICE;
+    }
+    MomentPlan* P = plan_of_device(device);
+    if (!P) return EZPZ_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lock(P->mu);
+    int rc;
+    if ((rc = grow(*P, chunk, (uint32_t)(n_param + n_meas))) != EZPZ_OK || (rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
+    MomentArgs a = args_of(nominal_p_dev, nominal_m_dev, samples, n_param, n_meas, moments_dev, info_dev);
+    for (uint64_t first = 0; first < samples; first += chunk) {
+        a.params = params_dev + first * n_param;
+        a.m = m_dev + first * n_meas;
+        a.flags = flags_dev ? flags_dev + first * n_meas : nullptr;
+        a.ok = ok_dev ? ok_dev + first : nullptr;
+        a.first = first;
+        a.count = std::min<uint64_t>(chunk, samples - first);
+        a.first_round = first == 0;
+        if ((rc = enqueue_moments(P->work, a, stream)) != EZPZ_OK) return rc;
+    }
+    call_stamp(MOMENTS_LAUNCHED);
+    return P->order.record(stream);
+}
+
+int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags, const uint8_t* ok, const double* nominal_p,
+                    const double* nominal_m, uint64_t samples, size_t n_param, size_t n_meas, uint32_t chunk_in, double* moments,
+                    EzpzMcMomentsInfo* info) {
+    uint64_t chunk = 0;
+    if (int rc = check_moments(params, m, nominal_p, nominal_m, samples, n_param, n_meas, chunk_in, moments, info, chunk)) return rc;
+    if (samples == 0) return EZPZ_OK;
+    int device = -1;
+    if (hipGetDevice(&device) != hipSuccess) {
+        (void)hipGetLastError();
+        return EZPZ_ERR_NO_DEVICE;
+    }
+    MomentPlan* P = plan_of_device(device);
+    if (!P) return EZPZ_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lock(P->mu);
+    const uint32_t K = (uint32_t)(n_param + n_meas);
+    const hipStream_t stream = hipStreamPerThread;
+    int rc;
+    // (the buffers of an earlier host call are idle: it waited for its launches)
+    if ((rc = grow(*P, chunk, K)) != EZPZ_OK || (rc = P->params.ensure(chunk * n_param)) != EZPZ_OK || (rc = P->m.ensure(chunk * n_meas)) != EZPZ_OK ||
+        (rc = P->flags.ensure(flags ? chunk * n_meas : 0)) != EZPZ_OK || (rc = P->ok.ensure(ok ? chunk : 0)) != EZPZ_OK ||
+        (rc = P->nominal.ensure(K)) != EZPZ_OK || (rc = P->moments_out.ensure(entries_of(K))) != EZPZ_OK || (rc = P->info_out.ensure(1)) != EZPZ_OK)
+        return rc;
+    if (n_param) HIP_TRY(hipMemcpy(P->nominal.p, nominal_p, n_param * sizeof(double), hipMemcpyHostToDevice));
+    if (n_meas) HIP_TRY(hipMemcpy(P->nominal.p + n_param, nominal_m, n_meas * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
+    MomentArgs a = args_of(P->nominal.p, P->nominal.p + n_param, samples, n_param, n_meas, P->moments_out.p, P->info_out.p);
+    a.params = P->params.p;
+    a.m = P->m.p;
+    a.flags = flags ? P->flags.p : nullptr;
+    a.ok = ok ? P->ok.p : nullptr;
+    for (uint64_t first = 0; first < samples; first += chunk) {
+        const uint64_t count = std::min<uint64_t>(chunk, samples - first);
+        if (first) HIP_TRY(hipStreamSynchronize(stream));  // (the last round has read the buffers)
+        if (n_param) HIP_TRY(hipMemcpy(P->params.p, params + first * n_param, count * n_param * sizeof(double), hipMemcpyHostToDevice));
+        if (n_meas) HIP_TRY(hipMemcpy(P->m.p, m + first * n_meas, count * n_meas * sizeof(double), hipMemcpyHostToDevice));
+        if (flags && n_meas) HIP_TRY(hipMemcpy(P->flags.p, flags + first * n_meas, count * n_meas, hipMemcpyHostToDevice));
+        if (ok) HIP_TRY(hipMemcpy(P->ok.p, ok + first, count, hipMemcpyHostToDevice));
+        a.first = first;
+        a.count = count;
+        a.first_round = first == 0;
+        if ((rc = enqueue_moments(P->work, a, stream)) != EZPZ_OK) return rc;
+    }
+    call_stamp(MOMENTS_LAUNCHED);
+    if ((rc = P->order.record(stream)) != EZPZ_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(moments, P->moments_out.p, entries_of(K) * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(info, P->info_out.p, sizeof(EzpzMcMomentsInfo), hipMemcpyDeviceToHost));
+    return EZPZ_OK;
+}
+
+}  // extern "C"

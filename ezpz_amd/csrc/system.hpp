@@ -9,6 +9,7 @@
 //   redundancy.hip  redundant / conflicting constraints and conflict groups (the row-space counterpart, on freedom.hip's components)
 //   measure.hip   reference dimensions: a record list measured at given values, its response to S, stack-up and vjp
 //   tolerance_mc.hip  Monte-Carlo tolerance analysis: sampled driven solves, measured, their statistics reduced on the device
+//   mc_moments.hip  tolerance contributors: the second moments of a Monte-Carlo run reduced on the device, and their closing step
 //   seek.hip      dimension targets: driving dimensions solved for measured targets, rounds of the driven entries kept on the device
 //   branches.hip  solution branches: sampled multi-start solves, their answers clustered on the device by the sequential leader rule
 //   driven.cpp    the entries that take a `positions` list of driven constraints: the list check, and the one call path behind

@@ -2,8 +2,11 @@
 // 3k): the host side of tolerance_mc.hip.hpp's kernels -- the check of a request, the plan a system keeps (the round's workspace,
 // the sampler's and the limits' tables, the host form's buffers) and the rounds.  A round is sampler -> copies of x0 ->
 // ezpz_system_solve_batch_params_device -> ezpz_system_measure_device -> reduction, all on the caller's stream: the driven solve
-// and the measurement are those entries themselves, with their routes, their locks and their ordering.
+// and the measurement are those entries themselves, with their routes, their locks and their ordering.  The run with contributors
+// (ezpz_system_tolerance_mc_contrib[_device]) is the same run on the same plan: one more enqueue per round behind the
+// reduction -- mc_moments.hip's, on the round's params, m, flags and ok -- and the closing kernel behind the last round.
 #include "driven_params.hpp"
+#include "mc_moments.hip.hpp"
 #include "measure_tables.hpp"
 #include "tolerance_mc.hip.hpp"
 
@@ -26,7 +29,7 @@ struct McPlan {
     LaunchOrder order;
     std::vector<unsigned char> tables_kept;  // what `dist` and `tab` hold
     DevBuf<mc::Dist> dist;
-    DevBuf<double> tab;  // lim_lo | lim_hi | hist_lo | hist_scale, [n_meas] each
+    DevBuf<double> tab;  // lim_lo | lim_hi | hist_lo | hist_scale, [n_meas] each, | the draw's nominal [n_param]
     DevBuf<double> x_in, x_out, params, m, nominal, part_f;
     DevBuf<uint64_t> part_arg;
     DevBuf<uint32_t> part_n;
@@ -38,6 +41,10 @@ struct McPlan {
     DevBuf<EzpzMcStats> stats_out;
     DevBuf<EzpzMcTotals> totals_out;
     DevBuf<uint64_t> hist_out;
+    // the run with contributors: the moments' workspace, and the host form's buffers
+    mcm::MomentWork moment_work;
+    DevBuf<double> contrib_out;  // moments | cov | beta | contrib | r2
+    DevBuf<uint64_t> contrib_words;  // EzpzMcMomentsInfo | dropped
 };
 
 McPlan& plan_of(EzpzSystem* sys) {
@@ -72,7 +79,7 @@ int check_dists(const EzpzMcDist* dist, const double* nominal, size_t n_param, s
 struct Request {
     std::vector<mc::Dist> dists;
     std::vector<uint32_t> words;  // the packed measurement records (compared by the measure entry against its kept list)
-    std::vector<double> tab;      // lim_lo | lim_hi | hist_lo | hist_scale
+    std::vector<double> tab;      // lim_lo | lim_hi | hist_lo | hist_scale | the draw's nominal
     bool limits = false;
     uint32_t hist_bins = 0;
     uint64_t seed = 0, chunk = 0;
@@ -117,6 +124,7 @@ int check_run(EzpzSystem* sys, const double* x0, const uint32_t* positions, size
         nominal = own.data();
     }
     if (int rc = check_dists(dist, nominal, n_param, r.dists)) return rc;
+    for (size_t j = 0; j < n_param; ++j) r.tab.push_back(nominal[j]);
     if (samples && (!stats || !totals || (c.hist_bins && n_meas && !hist) || (sys->counts.n_vars && !x0))) return EZPZ_ERR_INVALID_ARGUMENT;
     r.limits = lim_lo != nullptr;
     r.hist_bins = c.hist_bins;
@@ -143,6 +151,24 @@ struct Keep {
     bool host;  // the keep_* pointers are host memory: a round waits for its launches and copies out
 };
 
+// The outputs of a run with contributors (device pointers) and its checked configuration; moments == NULL: the plain run.
+struct Contrib {
+    double* moments = nullptr;
+    EzpzMcMomentsInfo* info = nullptr;
+    double *cov = nullptr, *beta = nullptr, *contrib = nullptr, *r2 = nullptr;
+    uint64_t* dropped = nullptr;
+    double pivot_rel = 0.0;
+};
+
+// The argument errors the contributors add to a run's; the pointers are only compared with NULL.
+int check_contrib(size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcContribConfig* cc, Contrib& c) {
+    if (int rc = mcm::check_shape(n_param, n_meas)) return rc;
+    if (int rc = mcm::check_config(cc, c.pivot_rel)) return rc;
+    if (samples && (!c.moments || !c.info || !c.cov || !c.dropped || (n_meas && !c.r2) || (n_meas && n_param && (!c.beta || !c.contrib))))
+        return EZPZ_ERR_INVALID_ARGUMENT;
+    return EZPZ_OK;
+}
+
 int copy_out(void* dst, const void* src, size_t bytes, bool host, hipStream_t stream) {
     if (!dst || !bytes) return EZPZ_OK;
     if (host)
@@ -156,7 +182,7 @@ int copy_out(void* dst, const void* src, size_t bytes, bool host, hipStream_t st
 // checked and samples > 0.
 int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint32_t* positions, const EzpzConstraint* records,
         uint64_t samples, const EzpzConfig* cfg, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev, const Keep& keep,
-        hipStream_t stream) {
+        const Contrib& contrib, hipStream_t stream) {
     release_thread_kernel(sys->device);
     const size_t n = sys->counts.n_vars, n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords;
     const uint64_t chunk = r.chunk, blocks = chunk / kBlock;
@@ -168,13 +194,13 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
     const bool new_tables = tables != P.tables_kept;
     const bool grows = chunk * n > P.x_in.cap || chunk * n_param > P.params.cap || chunk * n_meas > P.m.cap || chunk > P.status.cap ||
                        blocks * n_meas * 4 > P.part_f.cap || blocks * (2 * n_meas + 2) > P.part_n.cap || n_meas > P.nominal.cap ||
-                       !P.ticket.p;
+                       !P.ticket.p || (contrib.moments && P.moment_work.grows(blocks, (uint32_t)(n_param + n_meas)));
     if (new_tables || grows) {
         if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
         P.tables_kept.clear();
-        if ((rc = P.dist.ensure(n_param)) != EZPZ_OK || (rc = P.tab.ensure(4 * n_meas)) != EZPZ_OK) return rc;
+        if ((rc = P.dist.ensure(n_param)) != EZPZ_OK || (rc = P.tab.ensure(r.tab.size())) != EZPZ_OK) return rc;
         if (n_param) HIP_TRY(hipMemcpy(P.dist.p, r.dists.data(), n_param * sizeof(mc::Dist), hipMemcpyHostToDevice));
-        if (n_meas) HIP_TRY(hipMemcpy(P.tab.p, r.tab.data(), 4 * n_meas * sizeof(double), hipMemcpyHostToDevice));
+        if (!r.tab.empty()) HIP_TRY(hipMemcpy(P.tab.p, r.tab.data(), r.tab.size() * sizeof(double), hipMemcpyHostToDevice));
         if ((rc = P.x_in.ensure(chunk * n)) != EZPZ_OK || (rc = P.x_out.ensure(chunk * n)) != EZPZ_OK ||
             (rc = P.params.ensure(chunk * n_param)) != EZPZ_OK || (rc = P.m.ensure(chunk * n_meas)) != EZPZ_OK ||
             (rc = P.flags.ensure(chunk * n_meas)) != EZPZ_OK || (rc = P.status.ensure(chunk)) != EZPZ_OK ||
@@ -186,6 +212,7 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
             if ((rc = P.ticket.ensure(1)) != EZPZ_OK) return rc;
             HIP_TRY(hipMemset(P.ticket.p, 0, P.ticket.cap * sizeof(unsigned int)));
         }
+        if (contrib.moments && (rc = P.moment_work.ensure(blocks, (uint32_t)(n_param + n_meas))) != EZPZ_OK) return rc;
         P.tables_kept = std::move(tables);
         call_stamp(MC_TABLES_UPLOADED);
     }
@@ -220,6 +247,18 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
     a.stats = stats_dev;
     a.totals = totals_dev;
     a.hist = hist_dev;
+    mcm::MomentArgs mo{};
+    mo.params = P.params.p;
+    mo.m = P.m.p;
+    mo.flags = P.flags.p;
+    mo.ok = P.ok.p;
+    mo.nominal_p = P.tab.p + 4 * n_meas;
+    mo.nominal_m = P.nominal.p;
+    mo.samples = samples;
+    mo.k = (uint32_t)n_param;
+    mo.n_meas = (uint32_t)n_meas;
+    mo.moments = contrib.moments;
+    mo.info = contrib.info;
     for (uint64_t first = 0; first < samples; first += chunk) {
         const uint64_t count = std::min<uint64_t>(chunk, samples - first);
         if (n_param) hipLaunchKernelGGL(mc::mc_sample_kernel, dim3(stride_grid(count * n_param, sys)), dim3(256), 0, stream, P.dist.p, r.seed, first, count, (uint32_t)n_param, P.params.p);
@@ -235,6 +274,12 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
         a.first_round = first == 0;
         hipLaunchKernelGGL(mc::mc_reduce_kernel, dim3((uint32_t)((count + kBlock - 1) / kBlock)), dim3(256), 0, stream, a);
         HIP_TRY(hipGetLastError());
+        if (contrib.moments) {
+            mo.first = first;
+            mo.count = count;
+            mo.first_round = first == 0;
+            if ((rc = mcm::enqueue_moments(P.moment_work, mo, stream)) != EZPZ_OK) return rc;
+        }
         if (keep.params || keep.m || keep.flags || keep.ok) {
             if (keep.host) HIP_TRY(hipStreamSynchronize(stream));
             if ((rc = copy_out(keep.params ? keep.params + first * n_param : nullptr, P.params.p, count * n_param * sizeof(double), keep.host, stream)) != EZPZ_OK ||
@@ -244,8 +289,92 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
                 return rc;
         }
     }
+    if (contrib.moments) {
+        mcm::ContribArgs c{};
+        c.moments = contrib.moments;
+        c.info = contrib.info;
+        c.k = (uint32_t)n_param;
+        c.m = (uint32_t)n_meas;
+        c.pivot_rel = contrib.pivot_rel;
+        c.cov = contrib.cov, c.beta = contrib.beta, c.contrib = contrib.contrib, c.r2 = contrib.r2, c.dropped = contrib.dropped;
+        if ((rc = mcm::enqueue_contributors(c, stream)) != EZPZ_OK) return rc;
+    }
     call_stamp(MC_LAUNCHED);
     return P.order.record(stream);
+}
+
+// The device form of both runs: the request checked, then the rounds.
+int run_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist, const double* nominal,
+               const EzpzConstraint* records, size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
+               const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+               EzpzMcTotals* totals_dev, uint64_t* hist_dev, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib,
+               hipStream_t stream) {
+    Request r;
+    if (int rc = check_run(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg,
+                           stats_dev, totals_dev, hist_dev, stream, r))
+        return rc;
+    if (contrib)
+        if (int rc = check_contrib(n_param, n_meas, samples, cc, *contrib)) return rc;
+    if (samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(sys->device);
+    return run(sys, P, r, x0_dev, positions, records, samples, cfg, stats_dev, totals_dev, hist_dev, keep, contrib ? *contrib : Contrib{}, stream);
+}
+
+// The host form of both runs: the plan's buffers for x0 and the outputs, the rounds, the copies back once the stream has drained.
+// `contrib` holds host pointers here.
+int run_host(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist, const double* nominal,
+             const EzpzConstraint* records, size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+             uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals, uint64_t* hist,
+             const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib) {
+    Request r;
+    if (int rc = check_run(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, stats,
+                           totals, hist, hipStreamPerThread, r))
+        return rc;
+    if (contrib)
+        if (int rc = check_contrib(n_param, n_meas, samples, cc, *contrib)) return rc;
+    if (samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(sys->device);
+    const size_t n = sys->counts.n_vars, hist_words = n_meas * (r.hist_bins ? r.hist_bins + 2 : 0);
+    const size_t K = n_param + n_meas, E = contrib ? mcm::entries_of((uint32_t)K) : 0, km = n_param * n_meas;
+    int rc;
+    // (the buffers of an earlier host call are idle: it waited for its launches)
+    if ((rc = P.x0_in.ensure(n)) != EZPZ_OK || (rc = P.stats_out.ensure(n_meas)) != EZPZ_OK || (rc = P.totals_out.ensure(1)) != EZPZ_OK ||
+        (rc = P.hist_out.ensure(hist_words)) != EZPZ_OK)
+        return rc;
+    Contrib dev;
+    if (contrib) {
+        if ((rc = P.contrib_out.ensure(E + K * K + 2 * km + n_meas)) != EZPZ_OK || (rc = P.contrib_words.ensure(3)) != EZPZ_OK) return rc;
+        dev.moments = P.contrib_out.p;
+        dev.cov = dev.moments + E;
+        dev.beta = dev.cov + K * K;
+        dev.contrib = dev.beta + km;
+        dev.r2 = dev.contrib + km;
+        dev.info = reinterpret_cast<EzpzMcMomentsInfo*>(P.contrib_words.p);
+        dev.dropped = P.contrib_words.p + 2;
+        dev.pivot_rel = contrib->pivot_rel;
+    }
+    if (n) HIP_TRY(hipMemcpy(P.x0_in.p, x0, n * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = run(sys, P, r, P.x0_in.p, positions, records, samples, cfg, P.stats_out.p, P.totals_out.p, P.hist_out.p, keep, dev,
+                  hipStreamPerThread)) != EZPZ_OK)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
+    if (n_meas) HIP_TRY(hipMemcpy(stats, P.stats_out.p, n_meas * sizeof(EzpzMcStats), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(totals, P.totals_out.p, sizeof(EzpzMcTotals), hipMemcpyDeviceToHost));
+    if (hist_words) HIP_TRY(hipMemcpy(hist, P.hist_out.p, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (contrib) {
+        HIP_TRY(hipMemcpy(contrib->moments, dev.moments, E * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(contrib->cov, dev.cov, K * K * sizeof(double), hipMemcpyDeviceToHost));
+        if (km) HIP_TRY(hipMemcpy(contrib->beta, dev.beta, km * sizeof(double), hipMemcpyDeviceToHost));
+        if (km) HIP_TRY(hipMemcpy(contrib->contrib, dev.contrib, km * sizeof(double), hipMemcpyDeviceToHost));
+        if (n_meas) HIP_TRY(hipMemcpy(contrib->r2, dev.r2, n_meas * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(contrib->info, dev.info, sizeof(EzpzMcMomentsInfo), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(contrib->dropped, dev.dropped, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    return EZPZ_OK;
 }
 
 }  // namespace
@@ -275,16 +404,9 @@ int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const
                                     const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev,
                                     uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev, uint8_t* keep_flags_dev,
                                     uint8_t* keep_ok_dev, void* stream) {
-    Request r;
-    if (int rc = check_run(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg,
-                           stats_dev, totals_dev, hist_dev, (hipStream_t)stream, r))
-        return rc;
-    if (samples == 0) return EZPZ_OK;
-    McPlan& P = plan_of(sys);
-    std::lock_guard<std::mutex> lock(P.mu);
-    EZPZ_ON_DEVICE(sys->device);
-    return run(sys, P, r, x0_dev, positions, records, samples, cfg, stats_dev, totals_dev, hist_dev,
-               Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, (hipStream_t)stream);
+    return run_device(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                      stats_dev, totals_dev, hist_dev, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr,
+                      (hipStream_t)stream);
 }
 
 int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -292,29 +414,36 @@ int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* 
                              const double* hist_lo, const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg,
                              EzpzMcStats* stats, EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m,
                              uint8_t* keep_flags, uint8_t* keep_ok) {
-    Request r;
-    if (int rc = check_run(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, stats,
-                           totals, hist, hipStreamPerThread, r))
-        return rc;
-    if (samples == 0) return EZPZ_OK;
-    McPlan& P = plan_of(sys);
-    std::lock_guard<std::mutex> lock(P.mu);
-    EZPZ_ON_DEVICE(sys->device);
-    const size_t n = sys->counts.n_vars, hist_words = n_meas * (r.hist_bins ? r.hist_bins + 2 : 0);
-    int rc;
-    // (the buffers of an earlier host call are idle: it waited for its launches)
-    if ((rc = P.x0_in.ensure(n)) != EZPZ_OK || (rc = P.stats_out.ensure(n_meas)) != EZPZ_OK || (rc = P.totals_out.ensure(1)) != EZPZ_OK ||
-        (rc = P.hist_out.ensure(hist_words)) != EZPZ_OK)
-        return rc;
-    if (n) HIP_TRY(hipMemcpy(P.x0_in.p, x0, n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = run(sys, P, r, P.x0_in.p, positions, records, samples, cfg, P.stats_out.p, P.totals_out.p, P.hist_out.p,
-                  Keep{keep_params, keep_m, keep_flags, keep_ok, true}, hipStreamPerThread)) != EZPZ_OK)
-        return rc;
-    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
-    if (n_meas) HIP_TRY(hipMemcpy(stats, P.stats_out.p, n_meas * sizeof(EzpzMcStats), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(totals, P.totals_out.p, sizeof(EzpzMcTotals), hipMemcpyDeviceToHost));
-    if (hist_words) HIP_TRY(hipMemcpy(hist, P.hist_out.p, hist_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return EZPZ_OK;
+    return run_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg, stats,
+                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr);
+}
+
+int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                            const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                            const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                            uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                            EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                            uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, const EzpzMcContribConfig* cc, double* moments_dev,
+                                            EzpzMcMomentsInfo* info_dev, double* cov_dev, double* beta_dev, double* contrib_dev,
+                                            double* r2_dev, uint64_t* dropped_dev, void* stream) {
+    Contrib c;
+    c.moments = moments_dev, c.info = info_dev, c.cov = cov_dev, c.beta = beta_dev, c.contrib = contrib_dev, c.r2 = r2_dev, c.dropped = dropped_dev;
+    return run_device(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                      stats_dev, totals_dev, hist_dev, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, cc, &c,
+                      (hipStream_t)stream);
+}
+
+int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                     const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                     const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                     const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals,
+                                     uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok,
+                                     const EzpzMcContribConfig* cc, double* moments, EzpzMcMomentsInfo* info, double* cov, double* beta,
+                                     double* contrib, double* r2, uint64_t* dropped) {
+    Contrib c;
+    c.moments = moments, c.info = info, c.cov = cov, c.beta = beta, c.contrib = contrib, c.r2 = r2, c.dropped = dropped;
+    return run_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg, stats,
+                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, cc, &c);
 }
 
 }  // extern "C"

@@ -776,6 +776,99 @@ int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const
                                     EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
                                     uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, void* stream);
 
+/* ---- Tolerance contributors: which driving dimension causes the spread (a project extension) -- the Monte-Carlo
+ * counterpart of D of ezpz_system_measure_response.  The second-moment matrix between the sampled driving dimensions and the measured
+ * reference dimensions of a Monte-Carlo run is reduced on the device, with the fixed-order sums of the section above, and a closing
+ * step turns it into the covariance, the regression coefficients (effective sensitivities over the tolerance zone), each driving
+ * dimension's share of each reference dimension's variance, and the explained fraction r2: 1 - r2 is what non-linearity and
+ * interactions cause.  samples x (n_param + n_meas) values come back as K + K (K + 1) / 2 sums.
+ * THE SAMPLE VECTOR.  k = n_param, m = n_meas, K = k + m, 1 <= K <= EZPZ_MC_MOMENT_MAX.  For sample b, z [K]:
+ *   z[j] = p[b][j] - nominal_p[j], j < k;     z[k + i] = m[b][i] - nominal_m[i], i < m
+ * each one rounded subtraction: a FIXED dimension gives exactly +0.0.  In the run nominal_p is the nominal of the draw and nominal_m
+ * the statistics' nominal[i].
+ * Sample b is COMPLETE when it is ok (the run: the section above's rule; ezpz_mc_moments: ok[b] != 0, ok == NULL: every one) and,
+ * for EVERY record i, flag bit 0 of (b, i) is clear (flags == NULL: every one) and m[b][i] is finite.  One rule for the whole matrix
+ * (complete cases); per-record validity stays in EzpzMcStats.n_valid.  A caller whose record is always degenerate sees
+ * n_complete == 0 and drops that record.
+ * THE MOMENTS.  moments [K + K (K + 1) / 2]: first the K sums s[a] = sum of z[a]; then the upper triangle, row-major (a = 0: b = 0 ..
+ * K - 1; a = 1: b = 1 .. K - 1; ..): G[a][b] = sum of (z[a] * z[b]), a <= b, the product rounded, then added.  EzpzMcMomentsInfo:
+ * samples; n_complete, the complete samples.
+ * THE ORDER OF EVERY SUM is the section above's: block q is the samples [256 q, 256 q + 256); a leaf is the sample's z[a], or its
+ * rounded product, and +0.0 for a sample that is incomplete or past `samples`; inside a block the 256 leaves are summed by the
+ * adjacent-pair tree (for h = 1, 2, .. 128: v[t] += v[t + h] for every t that is a multiple of 2 h); the blocks' sums are added left
+ * to right from +0.0.  No floating-point atomics, no product contracted into a fused multiply-add: the same bits for any chunk, any
+ * stream and any device.
+ * THE CLOSING STEP, ezpz_mc_contributors (host only, no device; the run's kernel has the same body and gives the same bits): a pure
+ * function of moments, n_complete, k, m and pivot_rel, from + - * / and comparisons alone, every loop ascending.  n = n_complete as
+ * a double.
+ *   cov [K][K], full and symmetric: cov[a][b] = (G[a][b] - s[a] * s[b] / n) / (n - 1), evaluated as written for a <= b and mirrored.
+ *   n_complete < 2: cov, beta, contrib and r2 are all NaN, dropped is all ones (UINT64_MAX); nothing below applies.
+ *   LDL^T of the input block cov[0 .. k)[0 .. k), j ascending.  KEPT(l): dimension l was not dropped.
+ *     d_j = cov[j][j], then for every kept l < j, ascending:  t = L[j][l] * d_l;  d_j = d_j - L[j][l] * t
+ *     dimension j is kept when cov[j][j] > 0 and d_j > pivot_rel * cov[j][j] (false for NaN), else DROPPED: bit j of `dropped`
+ *     kept j, every i > j:  v = cov[i][j], then for every kept l < j, ascending:  t = L[j][l] * d_l;  v = v - L[i][l] * t;
+ *                           L[i][j] = v / d_j
+ *   A dropped dimension is left out of the factorisation: FIXED dimensions (variance 0), a dimension that repeats an earlier one,
+ *   CORNER dimensions aliased by too few samples.  pivot_rel (EzpzMcContribConfig; default 2^-26): below sqrt(epsilon) of its own
+ *   variance a dimension is a combination of earlier ones to half the digits, and its coefficient would have none left.
+ *   beta [m][k], per record i -- cov[0 .. k)[0 .. k) beta_i = cov[0 .. k)[k + i] over the kept dimensions, 0 for a dropped one:
+ *     y_j = cov[j][k + i], then for every kept l < j, ascending: y_j = y_j - L[j][l] * y_l          (j ascending, kept)
+ *     w_j = y_j / d_j
+ *     beta_j = w_j, then for every kept l > j, ascending: beta_j = beta_j - L[l][j] * beta_l       (j descending, kept)
+ *   r2 [m]:  explained_i = +0.0, then for every kept j, ascending: explained_i = explained_i + beta[i][j] * cov[j][k + i];
+ *            r2[i] = explained_i / cov[k + i][k + i]
+ *   contrib [m][k]:  contrib[i][j] = beta[i][j] * beta[i][j] * cov[j][j] / cov[k + i][k + i] (left to right), +0.0 for a dropped j
+ *   A reference dimension whose variance is not > 0 gives NaN for r2[i] and contrib[i][*] (its beta is what the formulas give).
+ * The sum of contrib[i][j] over j equals r2[i] only up to the sampled inputs' cross-covariances -- r2[i] - sum_j contrib[i][j] is
+ * sum over j != l of beta[i][j] * beta[i][l] * cov[j][l] / cov[k + i][k + i] -- which are O(1 / sqrt(n)) of the variances for the
+ * sampler's independent draws.  Correlations need a square root and are left to the caller (cov / sqrt(outer(diag))).
+ * ezpz_mc_moments[_device]: the reduction alone on the caller's samples -- params [samples][n_param], m [samples][n_meas], flags
+ * [samples][n_meas] bytes, ok [samples] bytes, nominal_p [n_param], nominal_m [n_meas] -- no system involved; useful on the kept
+ * samples of any run.  It works in rounds of `chunk` samples (rounded up to a multiple of 256; 0: 65536) on a workspace the library
+ * owns per device, as ezpz_branch_cluster's.  The _device form takes device pointers for every array and only enqueues on `stream`
+ * (a workspace that has to grow is first allocated behind the last call's launches); calls on one device go one behind the other
+ * whatever their streams.
+ * ezpz_system_tolerance_mc_contrib[_device]: ezpz_system_tolerance_mc[_device] -- the same arguments, the same run, stats, totals,
+ * hist and keep_* byte for byte -- with one more kernel per round, behind the round's reduction, that folds the round's params, m,
+ * flags and ok into `moments` and `info`, and one closing kernel behind the last round that fills cov, beta, contrib, r2 and dropped
+ * [1] from them.  The _device form takes device pointers for these outputs too.  cc == NULL: ezpz_default_mc_contrib_config's value.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: K == 0; K > EZPZ_MC_MOMENT_MAX; a negative or non-finite
+ * pivot_rel; moments NULL (ezpz_mc_contributors: or an output that has elements NULL); with samples > 0: an output NULL -- moments,
+ * info, and for the run cov, dropped, r2 (m > 0), beta and contrib (k m > 0) -- or an input that has elements NULL (flags and ok
+ * may be); for the run every argument error of ezpz_system_tolerance_mc.  samples == 0: EZPZ_OK after those checks, nothing written. */
+#define EZPZ_MC_MOMENT_MAX 64u
+typedef struct EzpzMcContribConfig { /* 16 bytes */
+    double pivot_rel; /* >= 0; default 2^-26 */
+    uint64_t reserved;
+} EzpzMcContribConfig;
+typedef struct EzpzMcMomentsInfo { /* 16 bytes */
+    uint64_t samples, n_complete;
+} EzpzMcMomentsInfo;
+void ezpz_default_mc_contrib_config(EzpzMcContribConfig* cc);
+int ezpz_mc_contributors(const double* moments, uint64_t n_complete, size_t n_param, size_t n_meas, const EzpzMcContribConfig* cc,
+                         double* cov, double* beta, double* contrib, double* r2, uint64_t* dropped);
+int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags, const uint8_t* ok, const double* nominal_p,
+                    const double* nominal_m, uint64_t samples, size_t n_param, size_t n_meas, uint32_t chunk, double* moments,
+                    EzpzMcMomentsInfo* info);
+int ezpz_mc_moments_device(const double* params_dev, const double* m_dev, const uint8_t* flags_dev, const uint8_t* ok_dev,
+                           const double* nominal_p_dev, const double* nominal_m_dev, uint64_t samples, size_t n_param, size_t n_meas,
+                           uint32_t chunk, double* moments_dev, EzpzMcMomentsInfo* info_dev, void* stream);
+int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                     const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                     const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                     const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals,
+                                     uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok,
+                                     const EzpzMcContribConfig* cc, double* moments, EzpzMcMomentsInfo* info, double* cov, double* beta,
+                                     double* contrib, double* r2, uint64_t* dropped);
+int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                            const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                            const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                            uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                            EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                            uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, const EzpzMcContribConfig* cc,
+                                            double* moments_dev, EzpzMcMomentsInfo* info_dev, double* cov_dev, double* beta_dev,
+                                            double* contrib_dev, double* r2_dev, uint64_t* dropped_dev, void* stream);
+
 /* ---- Dimension targets: solve driving dimensions for measured targets (a project extension) -- the inverse of the
  * entries above: which values of the driving dimensions (the constraints at `positions`, as ezpz_system_solve_batch_params takes
  * them) put the reference dimensions `records` (measurement records, as ezpz_system_measure takes them; host memory in both forms)
