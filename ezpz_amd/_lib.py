@@ -96,6 +96,14 @@ class CMcContribConfig(C.Structure):
     _fields_ = [("pivot_rel", C.c_double), ("reserved", C.c_uint64)]
 
 
+class CSobolConfig(C.Structure):
+    _fields_ = [("seed_b", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+SOBOL_MAX = 32  # EZPZ_SOBOL_MAX
+SOBOL_SEED_B = 0x9E3779B97F4A7C15  # ezpz_default_sobol_config's seed_b; the Python default is seed ^ this
+
+
 class CBranchConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("max_branches", C.c_uint32), ("eps_abs", C.c_double), ("eps_rel", C.c_double)]
 
@@ -172,6 +180,8 @@ EXPORTS = [
     "ezpz_default_mc_config", "ezpz_mc_sample", "ezpz_system_tolerance_mc", "ezpz_system_tolerance_mc_device",
     "ezpz_default_mc_contrib_config", "ezpz_mc_contributors", "ezpz_mc_moments", "ezpz_mc_moments_device",
     "ezpz_system_tolerance_mc_contrib", "ezpz_system_tolerance_mc_contrib_device",
+    "ezpz_default_sobol_config", "ezpz_mc_sobol_indices", "ezpz_mc_sobol_sums", "ezpz_mc_sobol_sums_device",
+    "ezpz_system_tolerance_sobol", "ezpz_system_tolerance_sobol_device",
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
     "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
     "ezpz_system_solve_branches_device",
@@ -252,6 +262,19 @@ def lib():
     L.ezpz_system_tolerance_mc_contrib.argtypes = L.ezpz_system_tolerance_mc.argtypes + [C.POINTER(CMcContribConfig), vp, vp, vp, vp, vp, vp, vp]
     L.ezpz_system_tolerance_mc_contrib_device.restype = C.c_int
     L.ezpz_system_tolerance_mc_contrib_device.argtypes = L.ezpz_system_tolerance_mc_contrib.argtypes + [vp]
+    L.ezpz_default_sobol_config.restype = None
+    L.ezpz_default_sobol_config.argtypes = [C.POINTER(CSobolConfig)]
+    L.ezpz_mc_sobol_indices.restype = C.c_int
+    L.ezpz_mc_sobol_indices.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.ezpz_mc_sobol_sums.restype = C.c_int
+    L.ezpz_mc_sobol_sums.argtypes = [vp, vp, vp, vp, u32, C.c_uint64, sz, sz, u32, vp, vp]
+    L.ezpz_mc_sobol_sums_device.restype = C.c_int
+    L.ezpz_mc_sobol_sums_device.argtypes = L.ezpz_mc_sobol_sums.argtypes + [vp]
+    L.ezpz_system_tolerance_sobol.restype = C.c_int
+    L.ezpz_system_tolerance_sobol.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, C.c_uint64, C.POINTER(CMcConfig), C.POINTER(CConfig),
+                                              C.POINTER(CSobolConfig)] + [vp] * 12
+    L.ezpz_system_tolerance_sobol_device.restype = C.c_int
+    L.ezpz_system_tolerance_sobol_device.argtypes = L.ezpz_system_tolerance_sobol.argtypes + [vp]
     L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
     L.ezpz_seek_step.restype = C.c_int
     L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1276,6 +1276,51 @@ class System:
         if rc != 0:
             raise NonLinearSystemError(rc)
 
+    # ---- Sobol tolerance indices (ezpz_system_tolerance_sobol) ------------------------------------------------------------------------
+    def tolerance_sobol(self, x0, positions, dists, records, samples: int, seed: int = 0, seed_b: Optional[int] = None, chunk: int = 0,
+                        keep: bool = False, nominal=None, config: Optional[Config] = None) -> "SobolResult":
+        """`ezpz_system_tolerance_sobol`: first-order and total-effect Sobol indices of every reference dimension (`records`) for
+        every driving dimension (`positions`, one `McDist` each; no CORNER ones) by pick-freeze sampling: (k' + 2) x samples
+        driven solves from x0 -- the nominal solution -- for k' dimensions that are not FIXED, reduced on the device.  seed: matrix
+        A's (the draws of `tolerance_mc` with this seed); seed_b: matrix B's (None: seed ^ 0x9E3779B97F4A7C15); chunk: samples per
+        round (0: the library's choice); keep: also every row's f [samples, k + 2, n_meas], flags and ok [samples, k + 2]."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if x0.size != self.n_vars:
+            raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
+        pos, d, recs, nominal, _, _, _, _, mc = self._mc_request(positions, dists, records, nominal, None, None, seed, chunk)
+        m, k, samples = len(recs), len(pos), int(samples)
+        sc = CSobolConfig((int(seed) ^ SOBOL_SEED_B if seed_b is None else int(seed_b)) & 0xFFFFFFFFFFFFFFFF, 0)
+        stats, totals = np.zeros(m, dtype=MC_STATS_DTYPE), np.zeros(1, dtype=MC_TOTALS_DTYPE)
+        sums, n_complete, out = _sobol_outputs(k, m)
+        kept = (np.zeros((samples, k + 2, m)), np.zeros((samples, k + 2, m), np.uint8), np.zeros((samples, k + 2), np.uint8)) if keep else (None,) * 3
+        cfg = (config or Config())._c()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_tolerance_sobol(self._h, ptr(x0), ptr(pos), k, ptr(d), ptr(nominal), ptr(recs), m, samples, C.byref(mc), C.byref(cfg),
+                                               C.byref(sc), ptr(stats), totals.ctypes.data, ptr(sums), ptr(n_complete), *(ptr(a) for a in out),
+                                               *(ptr(a) for a in kept))
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+        return SobolResult(stats, totals, sums, n_complete, *out, kept if keep else None, sc.seed_b)
+
+    def tolerance_sobol_device(self, x0_ptr: int, positions, dists, records, samples: int, stats_ptr: int, totals_ptr: int, sums_ptr: int,
+                               n_complete_ptr: int, var_ptr: int, first_ptr: int, total_ptr: int, first_var_ptr: int, total_var_ptr: int,
+                               seed: int = 0, seed_b: Optional[int] = None, chunk: int = 0, keep_f_ptr: int = 0, keep_flags_ptr: int = 0,
+                               keep_ok_ptr: int = 0, stream: int = 0, nominal=None, config: Optional[Config] = None) -> None:
+        """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], sums [n_meas, 4 + 4
+        n_param], n_complete uint64 [n_meas], var [n_meas], first, total, first_var, total_var [n_meas, n_param]) and a hipStream_t
+        handle; positions, dists, records and nominal stay host values.  Enqueues only once the run's tables are the last run's."""
+        pos, d, recs, nominal, _, _, _, _, mc = self._mc_request(positions, dists, records, nominal, None, None, seed, chunk)
+        sc = CSobolConfig((int(seed) ^ SOBOL_SEED_B if seed_b is None else int(seed_b)) & 0xFFFFFFFFFFFFFFFF, 0)
+        cfg = (config or Config())._c()
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = lib().ezpz_system_tolerance_sobol_device(self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs),
+                                                      int(samples), C.byref(mc), C.byref(cfg), C.byref(sc), stats_ptr or None, totals_ptr or None,
+                                                      sums_ptr or None, n_complete_ptr or None, var_ptr or None, first_ptr or None,
+                                                      total_ptr or None, first_var_ptr or None, total_var_ptr or None, keep_f_ptr or None,
+                                                      keep_flags_ptr or None, keep_ok_ptr or None, stream or None)
+        if rc != 0:
+            raise NonLinearSystemError(rc)
+
     # ---- solution branches (ezpz_system_solve_branches) --------------------------------------------------------------------------
     def _branch_request(self, dists, compare, seed, branch):
         d = mc_dists(dists)
@@ -1592,6 +1637,91 @@ def mc_contributors(moments, n_complete: int, n_param: int, n_meas: int, pivot_r
     if rc != 0:
         raise NonLinearSystemError(rc)
     return McContributors(moments, n_complete, n_param, n_meas, *out)
+
+
+class SobolIndices:
+    """What `mc_sobol_indices` returns and a `SobolResult` carries: sums [n_meas, 4 + 4 n_param] and n_complete [n_meas] as given,
+    var [n_meas] (the pooled variance of A's and B's deviations), first and total [n_meas, n_param] (the first-order and the
+    total-effect index) and first_var, total_var (the estimates' own variances: `first_se` and `total_se` are their square roots).
+    `interaction` is total - first."""
+
+    def __init__(self, sums, n_complete, var, first, total, first_var, total_var):
+        self.sums, self.n_complete, self.var = sums, n_complete, var
+        self.first, self.total, self.first_var, self.total_var = first, total, first_var, total_var
+
+    @property
+    def first_se(self) -> np.ndarray:
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self.first_var)
+
+    @property
+    def total_se(self) -> np.ndarray:
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(self.total_var)
+
+    @property
+    def interaction(self) -> np.ndarray:
+        return self.total - self.first
+
+
+class SobolResult(SobolIndices):
+    """What `System.tolerance_sobol` returns: the `SobolIndices`, matrix A's statistics as `tolerance_mc` gives them for the same
+    seed (`stats`, `totals` and their fields -- n_valid, mean, std, var_a (stats' var), nominal, .. -- samples, n_ok), seed_b, and
+    with keep the rows: f [samples, k + 2, n_meas], flags (the same shape) and ok [samples, k + 2]."""
+
+    def __init__(self, stats, totals, sums, n_complete, var, first, total, first_var, total_var, kept, seed_b):
+        super().__init__(sums, n_complete, var, first, total, first_var, total_var)
+        self.stats, self.totals, self.seed_b = stats, totals, int(seed_b)
+        for f in MC_STATS_DTYPE.names:
+            setattr(self, "var_a" if f == "var" else f, stats[f])
+        self.std = np.sqrt(stats["var"])
+        self.samples, self.n_ok, self.n_all_in = (int(totals[f][0]) for f in MC_TOTALS_DTYPE.names)
+        if kept is not None:
+            self.f, self.flags, self.ok = kept
+
+
+def _sobol_outputs(n_param: int, n_meas: int):
+    return (np.zeros((n_meas, 4 + 4 * n_param)), np.zeros(n_meas, np.uint64),
+            (np.zeros(n_meas), *(np.zeros((n_meas, n_param)) for _ in range(4))))
+
+
+def mc_sobol_sums(f, flags, ok, nominal_m, fixed_mask: int = 0, chunk: int = 0):
+    """`ezpz_mc_sobol_sums`: (sums [n_meas, 4 + 4 n_param], n_complete [n_meas]) of the pick-freeze rows f [samples, n_param + 2,
+    n_meas] (row 0: A, row 1: B, row 2 + j: A with column j from B), flags (the same shape; None: clear) and ok [samples, n_param + 2]
+    (None: every one set) about nominal_m; bit j of fixed_mask: dimension j is FIXED.  Computed on the host, in the device's order."""
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if f.ndim != 3 or f.shape[1] < 2:
+        raise ValueError(f"f [samples, n_param + 2, n_meas]: got {f.shape}")
+    samples, n_param, n_meas = f.shape[0], f.shape[1] - 2, f.shape[2]
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(f.shape)
+    if ok is not None:
+        ok = np.ascontiguousarray(np.asarray(ok).reshape(samples, n_param + 2) != 0, dtype=np.uint8)
+    nominal_m = np.ascontiguousarray(nominal_m, dtype=np.float64)
+    if nominal_m.shape != (n_meas,):
+        raise ValueError(f"nominal_m ({n_meas},): got {nominal_m.shape}")
+    sums, n_complete, _ = _sobol_outputs(min(n_param, SOBOL_MAX), min(n_meas, SOBOL_MAX))
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = lib().ezpz_mc_sobol_sums(ptr(f), ptr(flags), ptr(ok), ptr(nominal_m), int(fixed_mask), samples, n_param, n_meas, int(chunk), ptr(sums),
+                                  ptr(n_complete))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return sums, n_complete
+
+
+def mc_sobol_indices(sums, n_complete) -> SobolIndices:
+    """`ezpz_mc_sobol_indices`: the closing step on sums [n_meas, 4 + 4 n_param] and n_complete [n_meas].  Host only."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    n_complete = np.ascontiguousarray(n_complete, dtype=np.uint64)
+    if sums.ndim != 2 or sums.shape[1] < 4 or sums.shape[1] % 4 or n_complete.shape != (sums.shape[0],):
+        raise ValueError(f"sums [n_meas, 4 + 4 n_param] and n_complete [n_meas]: got {sums.shape} and {n_complete.shape}")
+    n_meas, n_param = sums.shape[0], sums.shape[1] // 4 - 1
+    _, _, out = _sobol_outputs(min(n_param, SOBOL_MAX), min(n_meas, SOBOL_MAX))
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    rc = lib().ezpz_mc_sobol_indices(ptr(sums), ptr(n_complete), n_param, n_meas, *(ptr(a) for a in out))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return SobolIndices(sums, n_complete, *out)
 
 
 class BranchConfig:

@@ -51,6 +51,9 @@ enum CallStage : uint32_t {
     // ezpz_mc_moments_device (mc_moments.hip)
     MOMENTS_WORKSPACE_GROWN = 90,  // a workspace that had to grow: waited for the last call's launches, allocated
     MOMENTS_LAUNCHED = 91,         // every round of the reduction enqueued
+    // ezpz_mc_sobol_sums_device (mc_sobol.hip)
+    SOBOL_WORKSPACE_GROWN = 100,  // a workspace that had to grow: waited for the last call's launches, allocated
+    SOBOL_LAUNCHED = 101,         // every round of the reduction enqueued
 };
 
 struct CallTrace {

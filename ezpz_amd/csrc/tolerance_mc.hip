@@ -4,9 +4,12 @@
 // ezpz_system_solve_batch_params_device -> ezpz_system_measure_device -> reduction, all on the caller's stream: the driven solve
 // and the measurement are those entries themselves, with their routes, their locks and their ordering.  The run with contributors
 // (ezpz_system_tolerance_mc_contrib[_device]) is the same run on the same plan: one more enqueue per round behind the
-// reduction -- mc_moments.hip's, on the round's params, m, flags and ok -- and the closing kernel behind the last round.
+// reduction -- mc_moments.hip's, on the round's params, m, flags and ok -- and the closing kernel behind the last round.  The run
+// with Sobol indices (ezpz_system_tolerance_sobol[_device]) is a second run on the same plan, run_sobol() below: k' + 2
+// sub-rounds a round, mc_sobol.hip's reduction behind the last one.
 #include "driven_params.hpp"
 #include "mc_moments.hip.hpp"
+#include "mc_sobol.hip.hpp"
 #include "measure_tables.hpp"
 #include "tolerance_mc.hip.hpp"
 
@@ -45,6 +48,13 @@ struct McPlan {
     mcm::MomentWork moment_work;
     DevBuf<double> contrib_out;  // moments | cov | beta | contrib | r2
     DevBuf<uint64_t> contrib_words;  // EzpzMcMomentsInfo | dropped
+    // the run with Sobol indices: the round's rows -- [k + 2][chunk][n_meas] values and flags, [k + 2][chunk] ok bytes
+    // -- the sums' workspace, and the host form's buffers
+    DevBuf<double> rows_f;
+    DevBuf<uint8_t> rows_flags, rows_ok;
+    sobol::SumWork sobol_work;
+    DevBuf<double> sobol_out;  // sums | var | first | total | first_var | total_var
+    DevBuf<uint64_t> sobol_words;  // n_complete
 };
 
 McPlan& plan_of(EzpzSystem* sys) {
@@ -377,6 +387,242 @@ int run_host(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_
     return EZPZ_OK;
 }
 
+// ---- the run with Sobol indices (ezpz_system_tolerance_sobol[_device]) -----------------------------------------------
+// The same plan, the same kernels and entries as run(), which stays what it is: a round is k' + 2 sub-rounds -- pick sampler, copies
+// of x0, the params entry, the measure entry into the round's rows -- with mc_reduce_kernel behind A's, mc_sobol_kernel behind the
+// last one and the closing kernel behind the last round.
+struct SobolOut {  // the outputs (device pointers in run_sobol) and the checked configuration
+    double* sums = nullptr;
+    uint64_t* n_complete = nullptr;
+    double *var = nullptr, *first = nullptr, *total = nullptr, *first_var = nullptr, *total_var = nullptr;
+    uint64_t seed_b = 0;
+    uint32_t fixed_mask = 0;
+};
+
+struct KeepRows {
+    double* f;
+    uint8_t *flags, *ok;
+    bool host;  // host memory: a round waits for its launches and copies out
+};
+
+// The argument errors the indices add to a run's, and the run's chunk; the pointers are only compared with NULL.
+int check_sobol(const EzpzSystem* sys, size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzSobolConfig* sc,
+                Request& r, SobolOut& o) {
+    if (int rc = sobol::check_shape(n_param, n_meas)) return rc;
+    EzpzSobolConfig c;
+    sobol::default_config(&c);
+    if (sc) c = *sc;
+    if (c.seed_b == r.seed) return EZPZ_ERR_INVALID_ARGUMENT;
+    o.seed_b = c.seed_b;
+    o.fixed_mask = 0;
+    for (size_t j = 0; j < n_param; ++j) {
+        if (r.dists[j].kind == EZPZ_MC_CORNER) return EZPZ_ERR_INVALID_ARGUMENT;
+        if (r.dists[j].kind == EZPZ_MC_FIXED) o.fixed_mask |= 1u << j;
+    }
+    if (samples && (!o.sums || !o.n_complete || !o.var || (n_param && (!o.first || !o.total || !o.first_var || !o.total_var))))
+        return EZPZ_ERR_INVALID_ARGUMENT;
+    if (!(mc_cfg && mc_cfg->chunk)) {  // the library's choice: the rows and the copies of x0 each below the round's bound
+        const uint64_t per_sample = std::max<uint64_t>({(uint64_t)sys->counts.n_vars, (uint64_t)(n_param + 2) * n_meas, 1}) * sizeof(double);
+        const uint64_t chunk = std::max<uint64_t>(std::min<uint64_t>(kChunkValueBytes / per_sample, kDefaultChunk) / kBlock * kBlock, kBlock);
+        r.chunk = std::min<uint64_t>(chunk, (std::max<uint64_t>(samples, 1) + kBlock - 1) / kBlock * kBlock);
+    }
+    return EZPZ_OK;
+}
+
+// rows of `width` bytes, `height` of them, between pitched arrays
+int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, bool host, hipStream_t stream) {
+    if (!dst || !width || !height) return EZPZ_OK;
+    if (host)
+        HIP_TRY(hipMemcpy2D(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToHost));
+    else
+        HIP_TRY(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, stream));
+    return EZPZ_OK;
+}
+
+// Device pointers throughout (but KeepRows', see there): the plan's mutex is held, the system's device current, the request checked
+// and samples > 0.
+int run_sobol(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint32_t* positions, const EzpzConstraint* records,
+              uint64_t samples, const EzpzConfig* cfg, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, const SobolOut& out,
+              const KeepRows& keep, hipStream_t stream) {
+    release_thread_kernel(sys->device);
+    const size_t n = sys->counts.n_vars, n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords, R = n_param + 2;
+    const uint64_t chunk = r.chunk, blocks = chunk / kBlock;
+    int rc;
+    // ---- what the host writes: behind the last run's launches ----
+    std::vector<unsigned char> tables(r.dists.size() * sizeof(mc::Dist) + r.tab.size() * sizeof(double));
+    if (!r.dists.empty()) std::memcpy(tables.data(), r.dists.data(), r.dists.size() * sizeof(mc::Dist));
+    if (!r.tab.empty()) std::memcpy(tables.data() + r.dists.size() * sizeof(mc::Dist), r.tab.data(), r.tab.size() * sizeof(double));
+    const bool new_tables = tables != P.tables_kept;
+    const bool grows = chunk * n > P.x_in.cap || chunk * n_param > P.params.cap || chunk > P.status.cap || blocks * n_meas * 4 > P.part_f.cap ||
+                       blocks * (2 * n_meas + 2) > P.part_n.cap || n_meas > P.nominal.cap || !P.ticket.p || R * chunk * n_meas > P.rows_f.cap ||
+                       R * chunk > P.rows_ok.cap || P.sobol_work.grows(blocks, (uint32_t)n_param, (uint32_t)n_meas);
+    if (new_tables || grows) {
+        if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
+        P.tables_kept.clear();
+        if ((rc = P.dist.ensure(n_param)) != EZPZ_OK || (rc = P.tab.ensure(r.tab.size())) != EZPZ_OK) return rc;
+        if (n_param) HIP_TRY(hipMemcpy(P.dist.p, r.dists.data(), n_param * sizeof(mc::Dist), hipMemcpyHostToDevice));
+        if (!r.tab.empty()) HIP_TRY(hipMemcpy(P.tab.p, r.tab.data(), r.tab.size() * sizeof(double), hipMemcpyHostToDevice));
+        if ((rc = P.x_in.ensure(chunk * n)) != EZPZ_OK || (rc = P.x_out.ensure(chunk * n)) != EZPZ_OK ||
+            (rc = P.params.ensure(chunk * n_param)) != EZPZ_OK || (rc = P.status.ensure(chunk)) != EZPZ_OK ||
+            (rc = P.nominal.ensure(n_meas)) != EZPZ_OK || (rc = P.part_f.ensure(blocks * n_meas * 4)) != EZPZ_OK ||
+            (rc = P.part_arg.ensure(blocks * n_meas * 2)) != EZPZ_OK || (rc = P.part_n.ensure(blocks * (2 * n_meas + 2))) != EZPZ_OK ||
+            (rc = P.rows_f.ensure(R * chunk * n_meas)) != EZPZ_OK || (rc = P.rows_flags.ensure(R * chunk * n_meas)) != EZPZ_OK ||
+            (rc = P.rows_ok.ensure(R * chunk)) != EZPZ_OK)
+            return rc;
+        if (!P.ticket.p) {
+            if ((rc = P.ticket.ensure(1)) != EZPZ_OK) return rc;
+            HIP_TRY(hipMemset(P.ticket.p, 0, P.ticket.cap * sizeof(unsigned int)));
+        }
+        if ((rc = P.sobol_work.ensure(blocks, (uint32_t)n_param, (uint32_t)n_meas)) != EZPZ_OK) return rc;
+        P.tables_kept = std::move(tables);
+        call_stamp(MC_TABLES_UPLOADED);
+    }
+    if ((rc = P.order.order_behind(stream)) != EZPZ_OK) return rc;
+    if ((rc = ezpz_system_measure_device(sys, records, n_meas, x0_dev, 1, P.nominal.p, nullptr, nullptr, stream)) != EZPZ_OK) return rc;
+    mc::ReduceArgs a{};  // A's rows through the plain run's reduction: no limits, no histogram
+    a.m = P.rows_f.p;
+    a.flags = P.rows_flags.p;
+    a.status = P.status.p;
+    a.nominal = P.nominal.p;
+    a.hist_lo = P.tab.p + 2 * n_meas;
+    a.hist_scale = P.tab.p + 3 * n_meas;
+    a.samples = samples;
+    a.n_meas = (uint32_t)n_meas;
+    a.part_d = P.part_f.p;
+    a.part_d2 = a.part_d + blocks * n_meas;
+    a.part_min = a.part_d2 + blocks * n_meas;
+    a.part_max = a.part_min + blocks * n_meas;
+    a.part_argmin = P.part_arg.p;
+    a.part_argmax = a.part_argmin + blocks * n_meas;
+    a.part_valid = P.part_n.p;
+    a.part_in = a.part_valid + blocks * n_meas;
+    a.part_ok = a.part_in + blocks * n_meas;
+    a.part_all_in = a.part_ok + blocks;
+    a.ticket = P.ticket.p;
+    a.ok = P.rows_ok.p;
+    a.stats = stats_dev;
+    a.totals = totals_dev;
+    sobol::SumArgs su{};
+    su.f = P.rows_f.p;
+    su.flags = P.rows_flags.p;
+    su.ok = P.rows_ok.p;
+    su.nominal_m = P.nominal.p;
+    su.stride_s = n_meas, su.stride_r = chunk * n_meas;
+    su.ok_stride_s = 1, su.ok_stride_r = chunk;
+    su.k = (uint32_t)n_param, su.m = (uint32_t)n_meas, su.fixed_mask = out.fixed_mask;
+    su.sums = out.sums;
+    su.n_complete = out.n_complete;
+    for (uint64_t first = 0; first < samples; first += chunk) {
+        const uint64_t count = std::min<uint64_t>(chunk, samples - first);
+        for (size_t row = 0; row < R; ++row) {
+            if (row >= 2 && ((out.fixed_mask >> (row - 2)) & 1u)) continue;  // AB_j == A: not solved
+            const uint32_t pick = row == 0 ? mc::kPickNone : row == 1 ? mc::kPickAll : (uint32_t)(row - 2);
+            if (n_param) hipLaunchKernelGGL(mc::mc_sample_pick_kernel, dim3(stride_grid(count * n_param, sys)), dim3(256), 0, stream, P.dist.p, r.seed, out.seed_b, pick, first, count, (uint32_t)n_param, P.params.p);
+            if (n) hipLaunchKernelGGL(mc::mc_broadcast_kernel, dim3(stride_grid(count * n, sys)), dim3(256), 0, stream, x0_dev, (uint32_t)n, count, P.x_in.p);
+            HIP_TRY(hipGetLastError());
+            if ((rc = ezpz_system_solve_batch_params_device(sys, P.x_in.p, positions, n_param, P.params.p, count, cfg, P.x_out.p, P.status.p,
+                                                            nullptr, nullptr, 0, stream)) != EZPZ_OK)
+                return rc;
+            if ((rc = ezpz_system_measure_device(sys, records, n_meas, P.x_out.p, count, P.rows_f.p + row * chunk * n_meas,
+                                                 P.rows_flags.p + row * chunk * n_meas, nullptr, stream)) != EZPZ_OK)
+                return rc;
+            if (row == 0) {
+                a.first = first;
+                a.count = count;
+                a.first_round = first == 0;
+                hipLaunchKernelGGL(mc::mc_reduce_kernel, dim3((uint32_t)((count + kBlock - 1) / kBlock)), dim3(256), 0, stream, a);
+                HIP_TRY(hipGetLastError());
+            } else if ((rc = sobol::enqueue_ok(P.status.p, count, P.rows_ok.p + row * chunk, stream)) != EZPZ_OK) {
+                return rc;
+            }
+        }
+        su.count = count;
+        su.first_round = first == 0;
+        if ((rc = sobol::enqueue_sums(P.sobol_work, su, stream)) != EZPZ_OK) return rc;
+        if (keep.f || keep.flags || keep.ok) {
+            if (keep.host) HIP_TRY(hipStreamSynchronize(stream));
+            for (size_t row = 0; row < R; ++row) {
+                const size_t src = row >= 2 && ((out.fixed_mask >> (row - 2)) & 1u) ? 0 : row;  // (a FIXED j: a copy of row 0)
+                if ((rc = copy_rows(keep.f ? keep.f + (first * R + row) * n_meas : nullptr, R * n_meas * sizeof(double), P.rows_f.p + src * chunk * n_meas,
+                                    n_meas * sizeof(double), n_meas * sizeof(double), count, keep.host, stream)) != EZPZ_OK ||
+                    (rc = copy_rows(keep.flags ? keep.flags + (first * R + row) * n_meas : nullptr, R * n_meas, P.rows_flags.p + src * chunk * n_meas,
+                                    n_meas, n_meas, count, keep.host, stream)) != EZPZ_OK ||
+                    (rc = copy_rows(keep.ok ? keep.ok + first * R + row : nullptr, R, P.rows_ok.p + src * chunk, 1, 1, count, keep.host, stream)) != EZPZ_OK)
+                    return rc;
+            }
+        }
+    }
+    sobol::CloseArgs c{};
+    c.sums = out.sums;
+    c.n_complete = out.n_complete;
+    c.k = (uint32_t)n_param, c.m = (uint32_t)n_meas;
+    c.var = out.var, c.first = out.first, c.total = out.total, c.first_var = out.first_var, c.total_var = out.total_var;
+    if ((rc = sobol::enqueue_close(c, stream)) != EZPZ_OK) return rc;
+    call_stamp(MC_LAUNCHED);
+    return P.order.record(stream);
+}
+
+int sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist, const double* nominal,
+                 const EzpzConstraint* records, size_t n_meas, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg,
+                 const EzpzSobolConfig* sc, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, SobolOut& out, const KeepRows& keep,
+                 hipStream_t stream) {
+    Request r;
+    if (int rc = check_run(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, nullptr, nullptr, nullptr, nullptr, samples, mc_cfg,
+                           stats_dev, totals_dev, nullptr, stream, r))
+        return rc;
+    if (int rc = check_sobol(sys, n_param, n_meas, samples, mc_cfg, sc, r, out)) return rc;
+    if (samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(sys->device);
+    return run_sobol(sys, P, r, x0_dev, positions, records, samples, cfg, stats_dev, totals_dev, out, keep, stream);
+}
+
+// `out` holds host pointers here.
+int sobol_host(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist, const double* nominal,
+               const EzpzConstraint* records, size_t n_meas, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg,
+               const EzpzSobolConfig* sc, EzpzMcStats* stats, EzpzMcTotals* totals, SobolOut& out, const KeepRows& keep) {
+    Request r;
+    if (int rc = check_run(sys, x0, positions, n_param, dist, nominal, records, n_meas, nullptr, nullptr, nullptr, nullptr, samples, mc_cfg, stats,
+                           totals, nullptr, hipStreamPerThread, r))
+        return rc;
+    if (int rc = check_sobol(sys, n_param, n_meas, samples, mc_cfg, sc, r, out)) return rc;
+    if (samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(sys->device);
+    const size_t n = sys->counts.n_vars, E = n_meas * sobol::width_of((uint32_t)n_param), km = n_param * n_meas;
+    int rc;
+    // (the buffers of an earlier host call are idle: it waited for its launches)
+    if ((rc = P.x0_in.ensure(n)) != EZPZ_OK || (rc = P.stats_out.ensure(n_meas)) != EZPZ_OK || (rc = P.totals_out.ensure(1)) != EZPZ_OK ||
+        (rc = P.sobol_out.ensure(E + n_meas + 4 * km)) != EZPZ_OK || (rc = P.sobol_words.ensure(n_meas)) != EZPZ_OK)
+        return rc;
+    SobolOut dev = out;
+    dev.sums = P.sobol_out.p;
+    dev.var = dev.sums + E;
+    dev.first = dev.var + n_meas;
+    dev.total = dev.first + km;
+    dev.first_var = dev.total + km;
+    dev.total_var = dev.first_var + km;
+    dev.n_complete = P.sobol_words.p;
+    if (n) HIP_TRY(hipMemcpy(P.x0_in.p, x0, n * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = run_sobol(sys, P, r, P.x0_in.p, positions, records, samples, cfg, P.stats_out.p, P.totals_out.p, dev, keep, hipStreamPerThread)) != EZPZ_OK)
+        return rc;
+    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
+    HIP_TRY(hipMemcpy(stats, P.stats_out.p, n_meas * sizeof(EzpzMcStats), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(totals, P.totals_out.p, sizeof(EzpzMcTotals), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out.sums, dev.sums, E * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out.n_complete, dev.n_complete, n_meas * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out.var, dev.var, n_meas * sizeof(double), hipMemcpyDeviceToHost));
+    if (km) {
+        HIP_TRY(hipMemcpy(out.first, dev.first, km * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out.total, dev.total, km * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out.first_var, dev.first_var, km * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out.total_var, dev.total_var, km * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return EZPZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -444,6 +690,30 @@ int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const ui
     c.moments = moments, c.info = info, c.cov = cov, c.beta = beta, c.contrib = contrib, c.r2 = r2, c.dropped = dropped;
     return run_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg, stats,
                     totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, cc, &c);
+}
+
+int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                       const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                       uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, const EzpzSobolConfig* sc,
+                                       EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, double* sums_dev, uint64_t* n_complete_dev,
+                                       double* var_dev, double* first_dev, double* total_dev, double* first_var_dev, double* total_var_dev,
+                                       double* keep_f_dev, uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, void* stream) {
+    SobolOut o;
+    o.sums = sums_dev, o.n_complete = n_complete_dev, o.var = var_dev, o.first = first_dev, o.total = total_dev;
+    o.first_var = first_var_dev, o.total_var = total_var_dev;
+    return sobol_device(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, samples, mc_cfg, cfg, sc, stats_dev, totals_dev, o,
+                        KeepRows{keep_f_dev, keep_flags_dev, keep_ok_dev, false}, (hipStream_t)stream);
+}
+
+int ezpz_system_tolerance_sobol(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                const double* nominal, const EzpzConstraint* records, size_t n_meas, uint64_t samples,
+                                const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, const EzpzSobolConfig* sc, EzpzMcStats* stats,
+                                EzpzMcTotals* totals, double* sums, uint64_t* n_complete, double* var, double* first, double* total,
+                                double* first_var, double* total_var, double* keep_f, uint8_t* keep_flags, uint8_t* keep_ok) {
+    SobolOut o;
+    o.sums = sums, o.n_complete = n_complete, o.var = var, o.first = first, o.total = total, o.first_var = first_var, o.total_var = total_var;
+    return sobol_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, samples, mc_cfg, cfg, sc, stats, totals, o,
+                      KeepRows{keep_f, keep_flags, keep_ok, true});
 }
 
 }  // extern "C"

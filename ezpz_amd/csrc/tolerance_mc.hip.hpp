@@ -1,6 +1,7 @@
 // Monte-Carlo tolerance analysis (include/ezpz_amd.h: ezpz_mc_sample, ezpz_system_tolerance_mc[_device]): the three
 // kernels of a round -- mc_sample_kernel (the round's driven values), mc_broadcast_kernel (its copies of x0) and mc_reduce_kernel
-// (the round's statistics, folded into the running results).  The sampler itself -- one __host__ __device__ body behind the host
+// (the round's statistics, folded into the running results) -- and mc_sample_pick_kernel, the sampler of the Sobol indices' pick-freeze
+// matrices.  The sampler itself -- one __host__ __device__ body behind the host
 // entry and the sampler kernel -- is in mc_sampler.hip.hpp; the host plan and the entries are in tolerance_mc.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +25,19 @@ __global__ __launch_bounds__(256) void mc_sample_kernel(const Dist* __restrict__
         const uint64_t s = idx / n_param;
         const uint32_t j = (uint32_t)(idx - s * n_param);
         params[idx] = draw(seed, first + s, j, dist[j]);
+    }
+}
+
+// ---- the same with the seed chosen per column (the pick-freeze matrices of the Sobol indices): column `pick` is
+// drawn with seed_b and every other one with seed_a -- kPickNone: all of them with seed_a (matrix A), kPickAll: all with seed_b (B)
+constexpr uint32_t kPickNone = 0xFFFFFFFFu, kPickAll = 0xFFFFFFFEu;
+__global__ __launch_bounds__(256) void mc_sample_pick_kernel(const Dist* __restrict__ dist, uint64_t seed_a, uint64_t seed_b, uint32_t pick,
+                                                             uint64_t first, uint64_t count, uint32_t n_param, double* __restrict__ params) {
+    const uint64_t total = count * n_param, stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
+        const uint64_t s = idx / n_param;
+        const uint32_t j = (uint32_t)(idx - s * n_param);
+        params[idx] = draw(pick == kPickAll || j == pick ? seed_b : seed_a, first + s, j, dist[j]);
     }
 }
 

@@ -869,6 +869,95 @@ int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_de
                                             double* moments_dev, EzpzMcMomentsInfo* info_dev, double* cov_dev, double* beta_dev,
                                             double* contrib_dev, double* r2_dev, uint64_t* dropped_dev, void* stream);
 
+/* ---- Sobol tolerance indices: which driving dimension causes the spread, curvature and interactions included (a
+ * project extension) -- the variance-based counterpart of the contributors above.  A regression is blind to a dimension that acts
+ * through curvature alone (beta and contrib are 0 by symmetry) and cannot say who is behind 1 - r2.  The first-order index first[i][j]
+ * is the share of reference dimension i's variance that driving dimension j causes on its own, the total-effect index total[i][j] the
+ * share it causes alone or together with others; total - first is what j's interactions cause.  Both are estimated by pick-freeze
+ * sampling: (k' + 2) x samples driven solves for k' sampled dimensions, reduced on the device with the fixed-order sums of the
+ * Monte-Carlo section to 4 + 4 k sums per record.
+ * THE MATRICES.  k = n_param <= EZPZ_SOBOL_MAX, m = n_meas, 1 <= m <= EZPZ_SOBOL_MAX.  Sample b of matrix A is row b of
+ * ezpz_mc_sample(seed, ..): the draws of ezpz_system_tolerance_mc with the same seed.  Matrix B is the same with seed_b
+ * (EzpzSobolConfig; ezpz_default_sobol_config: 0x9E3779B97F4A7C15); seed_b == seed is an argument error.  Matrix AB_j is A with
+ * column j taken from B.  A FIXED dimension has AB_j == A and is not solved.  A CORNER dimension is an argument error: its draw
+ * depends on the sample index alone, so A and B coincide.
+ * THE ROWS.  Per sample k + 2 rows of measurements, f [samples][k + 2][m]: row 0 of A, row 1 of B, row 2 + j of AB_j; for a FIXED j
+ * the kept row is a copy of row 0.  A row is SOLVED unless it is the row 2 + j of a FIXED j.
+ * Sample b is COMPLETE FOR record i when every solved row of b is ok (the run: the Monte-Carlo section's rule; ezpz_mc_sobol_sums:
+ * ok[b][r] != 0, ok == NULL: every one) and, in every solved row r, flag bit 0 of (b, r, i) is clear (flags == NULL: every one) and
+ * f[b][r][i] is finite.  Per record, not per sample as for the contributors: the records are independent here.
+ * THE LEAVES of sample b for record i, each operation rounded once, no product contracted into a fused multiply-add; every leaf is
+ * +0.0 for a sample that is incomplete for i or past `samples`:
+ *   dA = f[b][0][i] - nominal_m[i];   dB = f[b][1][i] - nominal_m[i];   dj = f[b][2 + j][i] - nominal_m[i];   t = dj - dA
+ *   p = dB * t  (first order: Saltelli et al. 2010);   q = t * t  (total effect: Jansen 1999);   p * p;   q * q;
+ *   dA;   dB;   dA * dA;   dB * dB
+ * THE SUMS.  sums [m][4 + 4 k], per record: sA, sB, sAA, sBB (the sums of dA, dB, dA * dA, dB * dB), then P [k], Q [k], P2 [k], Q2 [k]
+ * (the sums of p, q, p * p, q * q per dimension); n_complete [m] uint64: the samples complete for i.  The order of every sum is the
+ * Monte-Carlo section's: block q is the samples [256 q, 256 q + 256), the 256 leaves are summed by the adjacent-pair tree (for h =
+ * 1, 2, .. 128: v[t] += v[t + h] for every t that is a multiple of 2 h), the blocks' sums are added left to right from +0.0; no
+ * floating-point atomics: the same bits for any chunk, any stream and any device, and on the host.  For a FIXED j the four entries
+ * are WRITTEN as +0.0, not summed (dB * (+0.0) is -0.0 for a negative dB, and a block of those sums to -0.0).
+ * THE CLOSING STEP, ezpz_mc_sobol_indices (host only, no device; the run's kernel has the same body and gives the same bits): a
+ * pure function of sums, n_complete, k and m, from + - * / and comparisons alone, per record i, every loop ascending, each line
+ * evaluated as written, left to right.  n = n_complete[i] as a double.
+ *   n_complete[i] < 2: var[i], first[i][*], total[i][*], first_var[i][*], total_var[i][*] are all NaN; nothing below applies.
+ *   n2 = 2 * n;   s = sA + sB;   mean = s / n2;   var[i] = ((sAA + sBB) - s * mean) / (n2 - 1)
+ *   var[i] not > 0 (a constant record; NaN): first, total, first_var and total_var of the record are NaN.  Else, j ascending:
+ *   pm = P[j] / n;                first[i][j] = pm / var[i];   first_var[i][j] = ((P2[j] / n - pm * pm) / (n - 1)) / (var[i] * var[i])
+ *   qm = (Q[j] / 2) / n;          total[i][j] = (Q[j] / n2) / var[i]
+ *   total_var[i][j] = (((Q2[j] / 4) / n - qm * qm) / (n - 1)) / (var[i] * var[i])
+ * var is the variance of the 2 n values dA and dB pooled.  first_var and total_var are the variances of the two estimates -- the
+ * sample variance of the leaves over n, scaled -- and IGNORE the uncertainty of var itself; the standard error is their square root,
+ * which is the caller's, as for the correlations.  total - first, what interactions cause, is the caller's subtraction too.  A FIXED
+ * dimension's indices are +0.0.  An estimate can leave [0, 1] by its own error; nothing is clamped.
+ * ezpz_mc_sobol_sums[_device]: the reduction alone on the caller's rows -- f [samples][k + 2][m], flags (bytes, the same shape, may
+ * be NULL), ok [samples][k + 2] bytes (may be NULL), nominal_m [m], fixed_mask (bit j: dimension j is FIXED; bits >= k must be
+ * clear) -- no system involved; useful on the kept rows of any run.  The host form computes on the host, with no device, and gives
+ * the device form's bits.  The _device form takes device pointers for every array and only enqueues on `stream`, in rounds of `chunk`
+ * samples (rounded up to a multiple of 256; 0: 65536) on a workspace the library owns per device (a workspace that has to grow is
+ * first allocated behind the last call's launches); calls on one device go one behind the other whatever their streams.
+ * ezpz_system_tolerance_sobol[_device]: THE RUN -- the arguments of ezpz_system_tolerance_mc[_device] without limits and
+ * histogram (mc->hist_bins must be 0), plus EzpzSobolConfig.  A round of `chunk` samples (0: the largest multiple of 256, at most
+ * 65536, whose rows -- chunk x (k + 2) x m doubles -- and whose copies of x0 each stay below 256 MiB) is k' + 2 sub-rounds on the
+ * caller's stream, k' the dimensions that are not FIXED: the sampler with the seed chosen per column, the copies of x0,
+ * ezpz_system_solve_batch_params_device and ezpz_system_measure_device -- those entries themselves -- into the round's rows; the
+ * Monte-Carlo section's reduction follows A's sub-round, so stats [m] and totals are ezpz_system_tolerance_mc's with the same seed,
+ * byte for byte; one kernel behind the last sub-round folds the round's rows into sums and n_complete, and one closing kernel behind
+ * the last round fills var [m], first, total, first_var and total_var [m][k].  keep_f [samples][k + 2][m], keep_flags (bytes, the
+ * same shape), keep_ok [samples][k + 2] bytes (each optional, NULL): the rows themselves; the flags and ok of a FIXED j's row are
+ * copies of row 0's too.  The _device form takes device pointers for x0 and every output and enqueues as ezpz_system_tolerance_mc_device
+ * does; runs on one EzpzSystem, of either kind, go one behind the other.  sobol == NULL: ezpz_default_sobol_config's value.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: k > EZPZ_SOBOL_MAX; m == 0 or m > EZPZ_SOBOL_MAX; a CORNER
+ * dimension; seed_b == seed; a fixed_mask bit at or above k; with samples > 0 an output NULL -- sums, n_complete, and for the run
+ * stats, totals, var, and with k > 0 first, total, first_var, total_var (ezpz_mc_sobol_indices: whatever samples) -- or an input that
+ * has elements NULL (flags and ok may be); for the run every argument error of ezpz_system_tolerance_mc.  samples == 0: EZPZ_OK
+ * after those checks, nothing written. */
+#define EZPZ_SOBOL_MAX 32u
+typedef struct EzpzSobolConfig { /* 16 bytes */
+    uint64_t seed_b; /* matrix B's seed; default 0x9E3779B97F4A7C15 */
+    uint64_t reserved;
+} EzpzSobolConfig;
+void ezpz_default_sobol_config(EzpzSobolConfig* sobol);
+int ezpz_mc_sobol_indices(const double* sums, const uint64_t* n_complete, size_t n_param, size_t n_meas, double* var, double* first,
+                          double* total, double* first_var, double* total_var);
+int ezpz_mc_sobol_sums(const double* f, const uint8_t* flags, const uint8_t* ok, const double* nominal_m, uint32_t fixed_mask,
+                       uint64_t samples, size_t n_param, size_t n_meas, uint32_t chunk, double* sums, uint64_t* n_complete);
+int ezpz_mc_sobol_sums_device(const double* f_dev, const uint8_t* flags_dev, const uint8_t* ok_dev, const double* nominal_m_dev,
+                              uint32_t fixed_mask, uint64_t samples, size_t n_param, size_t n_meas, uint32_t chunk, double* sums_dev,
+                              uint64_t* n_complete_dev, void* stream);
+int ezpz_system_tolerance_sobol(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                const double* nominal, const EzpzConstraint* records, size_t n_meas, uint64_t samples,
+                                const EzpzMcConfig* mc, const EzpzConfig* cfg, const EzpzSobolConfig* sobol, EzpzMcStats* stats,
+                                EzpzMcTotals* totals, double* sums, uint64_t* n_complete, double* var, double* first, double* total,
+                                double* first_var, double* total_var, double* keep_f, uint8_t* keep_flags, uint8_t* keep_ok);
+int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                       const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                       uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, const EzpzSobolConfig* sobol,
+                                       EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, double* sums_dev, uint64_t* n_complete_dev,
+                                       double* var_dev, double* first_dev, double* total_dev, double* first_var_dev,
+                                       double* total_var_dev, double* keep_f_dev, uint8_t* keep_flags_dev, uint8_t* keep_ok_dev,
+                                       void* stream);
+
 /* ---- Dimension targets: solve driving dimensions for measured targets (a project extension) -- the inverse of the
  * entries above: which values of the driving dimensions (the constraints at `positions`, as ezpz_system_solve_batch_params takes
  * them) put the reference dimensions `records` (measurement records, as ezpz_system_measure takes them; host memory in both forms)
