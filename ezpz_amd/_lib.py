@@ -104,6 +104,16 @@ SOBOL_MAX = 32  # EZPZ_SOBOL_MAX
 SOBOL_SEED_B = 0x9E3779B97F4A7C15  # ezpz_default_sobol_config's seed_b; the Python default is seed ^ this
 
 
+class CMcQuantileConfig(C.Structure):
+    _fields_ = [("z", C.c_double), ("reserved", C.c_uint64)]
+
+
+MC_QUANTILE_MAX_PROBS, MC_QUANTILE_MAX_MEAS = 16, 64  # EZPZ_MC_QUANTILE_MAX_*
+MC_QUANTILE_DTYPE = np.dtype([("n_valid", "<u8"), ("rank", "<u8"), ("rank_lo", "<u8"), ("rank_hi", "<u8"), ("frac", "<f8"), ("lo", "<f8"),
+                              ("hi", "<f8"), ("value", "<f8"), ("band_lo", "<f8"), ("band_hi", "<f8")])  # EzpzMcQuantile
+assert C.sizeof(CMcQuantileConfig) == 16 and MC_QUANTILE_DTYPE.itemsize == 80
+
+
 class CBranchConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("max_branches", C.c_uint32), ("eps_abs", C.c_double), ("eps_rel", C.c_double)]
 
@@ -182,6 +192,8 @@ EXPORTS = [
     "ezpz_system_tolerance_mc_contrib", "ezpz_system_tolerance_mc_contrib_device",
     "ezpz_default_sobol_config", "ezpz_mc_sobol_indices", "ezpz_mc_sobol_sums", "ezpz_mc_sobol_sums_device",
     "ezpz_system_tolerance_sobol", "ezpz_system_tolerance_sobol_device",
+    "ezpz_default_mc_quantile_config", "ezpz_mc_quantiles", "ezpz_mc_quantiles_device", "ezpz_system_tolerance_mc_quantiles",
+    "ezpz_system_tolerance_mc_quantiles_device",
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
     "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
     "ezpz_system_solve_branches_device",
@@ -275,6 +287,16 @@ def lib():
                                               C.POINTER(CSobolConfig)] + [vp] * 12
     L.ezpz_system_tolerance_sobol_device.restype = C.c_int
     L.ezpz_system_tolerance_sobol_device.argtypes = L.ezpz_system_tolerance_sobol.argtypes + [vp]
+    L.ezpz_default_mc_quantile_config.restype = None
+    L.ezpz_default_mc_quantile_config.argtypes = [C.POINTER(CMcQuantileConfig)]
+    L.ezpz_mc_quantiles.restype = C.c_int
+    L.ezpz_mc_quantiles.argtypes = [vp, vp, vp, C.c_uint64, sz, vp, sz, C.POINTER(CMcQuantileConfig), vp]
+    L.ezpz_mc_quantiles_device.restype = C.c_int
+    L.ezpz_mc_quantiles_device.argtypes = L.ezpz_mc_quantiles.argtypes + [vp]
+    L.ezpz_system_tolerance_mc_quantiles.restype = C.c_int
+    L.ezpz_system_tolerance_mc_quantiles.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp, sz, C.POINTER(CMcQuantileConfig), vp]
+    L.ezpz_system_tolerance_mc_quantiles_device.restype = C.c_int
+    L.ezpz_system_tolerance_mc_quantiles_device.argtypes = L.ezpz_system_tolerance_mc_quantiles.argtypes + [vp]
     L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
     L.ezpz_seek_step.restype = C.c_int
     L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1213,7 +1213,7 @@ class System:
 
     def tolerance_mc(self, x0, positions, dists, records, samples: int, seed: int = 0, nominal=None, limits=None, hist=None,
                      chunk: int = 0, keep: bool = False, config: Optional[Config] = None, contributors: bool = False,
-                     pivot_rel: Optional[float] = None) -> "McResult":
+                     pivot_rel: Optional[float] = None, quantiles=None, quantile_z: float = 0.0) -> "McResult":
         """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
         solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
         statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
@@ -1221,7 +1221,13 @@ class System:
         record with an under and an over count; chunk: samples per round (0: the library's choice); keep: also every sample's
         params, m, flags and ok.  The sums' order is fixed: the same bits whatever the chunk.
         contributors: the same run through `ezpz_system_tolerance_mc_contrib` -- the result also has moments, n_complete, cov, beta,
-        contrib, r2, dropped and corr (`McContributors`); pivot_rel: EzpzMcContribConfig's (None: the library's default)."""
+        contrib, r2, dropped and corr (`McContributors`); pivot_rel: EzpzMcContribConfig's (None: the library's default).
+        quantiles: a list of probabilities in [0, 1] -- the same run through `ezpz_system_tolerance_mc_quantiles`: every sample's m,
+        flags and ok stay on the device (samples x n_meas x 9 + samples bytes) and the exact order statistics are selected there; the
+        result also has `quantiles` (MC_QUANTILE_DTYPE [n_meas, n_q]) and q_value, q_lo, q_hi, q_band_lo, q_band_hi [n_meas, n_q];
+        quantile_z: the band's half width in standard errors of the rank.  Not together with contributors."""
+        if quantiles is not None and contributors:
+            raise ValueError("quantiles together with contributors: run them one after the other")
         x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
         if x0.size != self.n_vars:
             raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
@@ -1237,6 +1243,14 @@ class System:
         ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
         args = (self._h, ptr(x0), ptr(pos), n_param, ptr(d), ptr(nominal), ptr(recs), k, ptr(lim_lo), ptr(lim_hi), ptr(hist_lo), ptr(hist_hi),
                 samples, C.byref(mc), C.byref(cfg), stats.ctypes.data, totals.ctypes.data, ptr(counts), *(ptr(a) for a in kept))
+        if quantiles is not None:
+            probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+            out = np.zeros((k, len(probs)), dtype=MC_QUANTILE_DTYPE)
+            qc = CMcQuantileConfig(float(quantile_z), 0)
+            rc = lib().ezpz_system_tolerance_mc_quantiles(*args, ptr(probs), len(probs), C.byref(qc), ptr(out))
+            if rc != 0:
+                raise NonLinearSystemError(rc)
+            return McResult(stats, totals, counts, kept if keep else None, quantiles=out)
         if not contributors:
             rc = lib().ezpz_system_tolerance_mc(*args)
             if rc != 0:
@@ -1254,12 +1268,17 @@ class System:
                             seed: int = 0, nominal=None, limits=None, hist=None, chunk: int = 0, keep_params_ptr: int = 0,
                             keep_m_ptr: int = 0, keep_flags_ptr: int = 0, keep_ok_ptr: int = 0, stream: int = 0,
                             config: Optional[Config] = None, moments_ptr: int = 0, info_ptr: int = 0, cov_ptr: int = 0, beta_ptr: int = 0,
-                            contrib_ptr: int = 0, r2_ptr: int = 0, dropped_ptr: int = 0, pivot_rel: Optional[float] = None) -> None:
+                            contrib_ptr: int = 0, r2_ptr: int = 0, dropped_ptr: int = 0, pivot_rel: Optional[float] = None,
+                            quantiles=None, quantile_z: float = 0.0, quantiles_ptr: int = 0) -> None:
         """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], hist: uint64
         [n_meas, bins + 2]) and a hipStream_t handle; positions, dists, records, nominal, limits and hist = (lo, hi, bins) stay host
         values.  Enqueues only once the run's tables are the last run's.  With moments_ptr the run goes through
         `ezpz_system_tolerance_mc_contrib_device` and fills moments [K + K (K + 1) / 2], info (MC_MOMENTS_INFO_DTYPE [1]), cov [K, K],
-        beta and contrib [n_meas, n_param], r2 [n_meas] and dropped (uint64 [1]) as well, K = n_param + n_meas."""
+        beta and contrib [n_meas, n_param], r2 [n_meas] and dropped (uint64 [1]) as well, K = n_param + n_meas.  With quantiles (host
+        probabilities) the run goes through `ezpz_system_tolerance_mc_quantiles_device` and fills quantiles_ptr (MC_QUANTILE_DTYPE
+        [n_meas, n_q]); it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given."""
+        if quantiles is not None and moments_ptr:
+            raise ValueError("quantiles together with contributors: run them one after the other")
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
@@ -1267,7 +1286,11 @@ class System:
         args = (self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs), ptr(lim_lo), ptr(lim_hi), ptr(hist_lo),
                 ptr(hist_hi), int(samples), C.byref(mc), C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
                 keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None)
-        if moments_ptr:
+        if quantiles is not None:
+            probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+            qc = CMcQuantileConfig(float(quantile_z), 0)
+            rc = lib().ezpz_system_tolerance_mc_quantiles_device(*args, ptr(probs), len(probs), C.byref(qc), quantiles_ptr or None, stream or None)
+        elif moments_ptr:
             cc = _contrib_config(pivot_rel)
             rc = lib().ezpz_system_tolerance_mc_contrib_device(*args, C.byref(cc), moments_ptr, info_ptr or None, cov_ptr or None, beta_ptr or None,
                                                                contrib_ptr or None, r2_ptr or None, dropped_ptr or None, stream or None)
@@ -1547,10 +1570,15 @@ class McResult:
     n_in, nominal, sum_d, sum_d2 -- hist [n_meas, bins + 2] (under, the bins, over; None without a histogram), the totals samples,
     n_ok and n_all_in, and with keep the samples: params, m, flags, ok.  `stats` and `totals` are the library's records.  A run with
     contributors also has moments, n_complete, cov, beta, contrib, r2, dropped (those of its `contributors`, a `McContributors`) and
-    `corr`."""
+    `corr`.  A run with quantiles also has `quantiles` (MC_QUANTILE_DTYPE [n_meas, n_q]) and its fields as q_value, q_lo, q_hi,
+    q_band_lo, q_band_hi."""
 
-    def __init__(self, stats, totals, hist, kept, contributors=None):
+    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None):
         self.stats, self.totals, self.hist = stats, totals, hist
+        if quantiles is not None:
+            self.quantiles = quantiles
+            for f in ("value", "lo", "hi", "band_lo", "band_hi"):
+                setattr(self, "q_" + f, quantiles[f])
         if contributors is not None:
             self.contributors = contributors
             for f in ("moments", "n_complete", "cov", "beta", "contrib", "r2", "dropped"):
@@ -1637,6 +1665,28 @@ def mc_contributors(moments, n_complete: int, n_param: int, n_meas: int, pivot_r
     if rc != 0:
         raise NonLinearSystemError(rc)
     return McContributors(moments, n_complete, n_param, n_meas, *out)
+
+
+def mc_quantiles(m, flags, ok, probs, z: float = 0.0) -> np.ndarray:
+    """`ezpz_mc_quantiles`: MC_QUANTILE_DTYPE [n_meas, n_q], the exact order statistics of the kept rows m [samples, n_meas], flags
+    (the same shape; None: clear) and ok [samples] (None: every one set) at the probabilities `probs`, with the distribution-free
+    band of z standard errors of the rank.  Computed on the host; the device form gives the same bytes."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.ndim != 2:
+        raise ValueError(f"m [samples, n_meas]: got {m.shape}")
+    samples, n_meas = m.shape
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(m.shape)
+    if ok is not None:
+        ok = np.ascontiguousarray(np.asarray(ok).reshape(samples) != 0, dtype=np.uint8)
+    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    out = np.zeros((min(n_meas, MC_QUANTILE_MAX_MEAS), min(len(probs), MC_QUANTILE_MAX_PROBS)), dtype=MC_QUANTILE_DTYPE)
+    qc = CMcQuantileConfig(float(z), 0)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    rc = lib().ezpz_mc_quantiles(ptr(m), ptr(flags), ptr(ok), samples, n_meas, ptr(probs), len(probs), C.byref(qc), ptr(out))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return out
 
 
 class SobolIndices:

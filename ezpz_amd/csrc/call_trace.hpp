@@ -54,6 +54,9 @@ enum CallStage : uint32_t {
     // ezpz_mc_sobol_sums_device (mc_sobol.hip)
     SOBOL_WORKSPACE_GROWN = 100,  // a workspace that had to grow: waited for the last call's launches, allocated
     SOBOL_LAUNCHED = 101,         // every round of the reduction enqueued
+    // ezpz_mc_quantiles_device (mc_quantiles.hip)
+    QUANTILES_WORKSPACE_GROWN = 110,  // a workspace that had to grow: waited for the last call's launches, allocated
+    QUANTILES_LAUNCHED = 111,         // every digit pass of the selection enqueued
 };
 
 struct CallTrace {

@@ -6,9 +6,11 @@
 // (ezpz_system_tolerance_mc_contrib[_device]) is the same run on the same plan: one more enqueue per round behind the
 // reduction -- mc_moments.hip's, on the round's params, m, flags and ok -- and the closing kernel behind the last round.  The run
 // with Sobol indices (ezpz_system_tolerance_sobol[_device]) is a second run on the same plan, run_sobol() below: k' + 2
-// sub-rounds a round, mc_sobol.hip's reduction behind the last one.
+// sub-rounds a round, mc_sobol.hip's reduction behind the last one.  The run with quantiles (ezpz_system_tolerance_mc_quantiles[_device];
+// DESIGN.md 3p) is run() again: every round's m, flags and ok kept on the device, mc_quantiles.hip's selection behind the last round.
 #include "driven_params.hpp"
 #include "mc_moments.hip.hpp"
+#include "mc_quantiles.hip.hpp"
 #include "mc_sobol.hip.hpp"
 #include "measure_tables.hpp"
 #include "tolerance_mc.hip.hpp"
@@ -55,6 +57,12 @@ struct McPlan {
     sobol::SumWork sobol_work;
     DevBuf<double> sobol_out;  // sums | var | first | total | first_var | total_var
     DevBuf<uint64_t> sobol_words;  // n_complete
+    // the run with quantiles: every sample's m, flags and ok -- samples x n_meas x 9 + samples bytes, the one
+    // workspace here that grows with samples -- the selection's workspace, and the host form's buffer
+    DevBuf<double> all_m;
+    DevBuf<uint8_t> all_flags, all_ok;
+    mcq::SelectWork select_work;
+    DevBuf<EzpzMcQuantile> quant_out;
 };
 
 McPlan& plan_of(EzpzSystem* sys) {
@@ -179,6 +187,14 @@ int check_contrib(size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcC
     return EZPZ_OK;
 }
 
+// The quantiles of a run (probs: host memory; out: a device pointer in run()) and the checked z; n_q == 0: the plain run.
+struct Quant {
+    const double* probs = nullptr;
+    size_t n_q = 0;
+    EzpzMcQuantile* out = nullptr;
+    double z = 0.0;
+};
+
 int copy_out(void* dst, const void* src, size_t bytes, bool host, hipStream_t stream) {
     if (!dst || !bytes) return EZPZ_OK;
     if (host)
@@ -192,7 +208,7 @@ int copy_out(void* dst, const void* src, size_t bytes, bool host, hipStream_t st
 // checked and samples > 0.
 int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint32_t* positions, const EzpzConstraint* records,
         uint64_t samples, const EzpzConfig* cfg, EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev, const Keep& keep,
-        const Contrib& contrib, hipStream_t stream) {
+        const Contrib& contrib, const Quant& quant, hipStream_t stream) {
     release_thread_kernel(sys->device);
     const size_t n = sys->counts.n_vars, n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords;
     const uint64_t chunk = r.chunk, blocks = chunk / kBlock;
@@ -205,7 +221,14 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
     const bool grows = chunk * n > P.x_in.cap || chunk * n_param > P.params.cap || chunk * n_meas > P.m.cap || chunk > P.status.cap ||
                        blocks * n_meas * 4 > P.part_f.cap || blocks * (2 * n_meas + 2) > P.part_n.cap || n_meas > P.nominal.cap ||
                        !P.ticket.p || (contrib.moments && P.moment_work.grows(blocks, (uint32_t)(n_param + n_meas)));
-    if (new_tables || grows) {
+    // the rows the selection reads: the caller's device buffers where given, else the plan's
+    const bool select = quant.n_q != 0;
+    double* all_m = !keep.host && keep.m ? keep.m : nullptr;
+    uint8_t* all_flags = !keep.host && keep.flags ? keep.flags : nullptr;
+    uint8_t* all_ok = !keep.host && keep.ok ? keep.ok : nullptr;
+    const bool select_grows = select && ((!all_m && samples * n_meas > P.all_m.cap) || (!all_flags && samples * n_meas > P.all_flags.cap) ||
+                                         (!all_ok && samples > P.all_ok.cap) || P.select_work.grows((uint32_t)n_meas, (uint32_t)quant.n_q));
+    if (new_tables || grows || select_grows) {
         if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
         P.tables_kept.clear();
         if ((rc = P.dist.ensure(n_param)) != EZPZ_OK || (rc = P.tab.ensure(r.tab.size())) != EZPZ_OK) return rc;
@@ -223,6 +246,11 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
             HIP_TRY(hipMemset(P.ticket.p, 0, P.ticket.cap * sizeof(unsigned int)));
         }
         if (contrib.moments && (rc = P.moment_work.ensure(blocks, (uint32_t)(n_param + n_meas))) != EZPZ_OK) return rc;
+        if (select && ((!all_m && (rc = P.all_m.ensure(samples * n_meas)) != EZPZ_OK) ||
+                       (!all_flags && (rc = P.all_flags.ensure(samples * n_meas)) != EZPZ_OK) ||
+                       (!all_ok && (rc = P.all_ok.ensure(samples)) != EZPZ_OK) ||
+                       (rc = P.select_work.ensure((uint32_t)n_meas, (uint32_t)quant.n_q)) != EZPZ_OK))
+            return rc;
         P.tables_kept = std::move(tables);
         call_stamp(MC_TABLES_UPLOADED);
     }
@@ -290,6 +318,12 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
             mo.first_round = first == 0;
             if ((rc = mcm::enqueue_moments(P.moment_work, mo, stream)) != EZPZ_OK) return rc;
         }
+        if (select) {  // (a caller's device buffer is filled by the copies below)
+            if ((rc = copy_out(all_m ? nullptr : P.all_m.p + first * n_meas, P.m.p, count * n_meas * sizeof(double), false, stream)) != EZPZ_OK ||
+                (rc = copy_out(all_flags ? nullptr : P.all_flags.p + first * n_meas, P.flags.p, count * n_meas, false, stream)) != EZPZ_OK ||
+                (rc = copy_out(all_ok ? nullptr : P.all_ok.p + first, P.ok.p, count, false, stream)) != EZPZ_OK)
+                return rc;
+        }
         if (keep.params || keep.m || keep.flags || keep.ok) {
             if (keep.host) HIP_TRY(hipStreamSynchronize(stream));
             if ((rc = copy_out(keep.params ? keep.params + first * n_param : nullptr, P.params.p, count * n_param * sizeof(double), keep.host, stream)) != EZPZ_OK ||
@@ -309,6 +343,10 @@ int run(EzpzSystem* sys, McPlan& P, Request& r, const double* x0_dev, const uint
         c.cov = contrib.cov, c.beta = contrib.beta, c.contrib = contrib.contrib, c.r2 = contrib.r2, c.dropped = contrib.dropped;
         if ((rc = mcm::enqueue_contributors(c, stream)) != EZPZ_OK) return rc;
     }
+    if (select && (rc = mcq::enqueue_select(P.select_work, all_m ? all_m : P.all_m.p, all_flags ? all_flags : P.all_flags.p,
+                                            all_ok ? all_ok : P.all_ok.p, samples, (uint32_t)n_meas, quant.probs, (uint32_t)quant.n_q, quant.z,
+                                            quant.out, sys->lim.cus, stream)) != EZPZ_OK)
+        return rc;
     call_stamp(MC_LAUNCHED);
     return P.order.record(stream);
 }
@@ -318,18 +356,21 @@ int run_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions,
                const EzpzConstraint* records, size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
                const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
                EzpzMcTotals* totals_dev, uint64_t* hist_dev, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib,
-               hipStream_t stream) {
+               const EzpzMcQuantileConfig* qc, Quant* quant, hipStream_t stream) {
     Request r;
     if (int rc = check_run(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg,
                            stats_dev, totals_dev, hist_dev, stream, r))
         return rc;
     if (contrib)
         if (int rc = check_contrib(n_param, n_meas, samples, cc, *contrib)) return rc;
+    if (quant)
+        if (int rc = mcq::check(samples, n_meas, quant->probs, quant->n_q, qc, sys, quant->out, quant->z)) return rc;  // (the rows are the run's own)
     if (samples == 0) return EZPZ_OK;
     McPlan& P = plan_of(sys);
     std::lock_guard<std::mutex> lock(P.mu);
     EZPZ_ON_DEVICE(sys->device);
-    return run(sys, P, r, x0_dev, positions, records, samples, cfg, stats_dev, totals_dev, hist_dev, keep, contrib ? *contrib : Contrib{}, stream);
+    return run(sys, P, r, x0_dev, positions, records, samples, cfg, stats_dev, totals_dev, hist_dev, keep, contrib ? *contrib : Contrib{},
+               quant ? *quant : Quant{}, stream);
 }
 
 // The host form of both runs: the plan's buffers for x0 and the outputs, the rounds, the copies back once the stream has drained.
@@ -337,13 +378,15 @@ int run_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions,
 int run_host(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist, const double* nominal,
              const EzpzConstraint* records, size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
              uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals, uint64_t* hist,
-             const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib) {
+             const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant) {
     Request r;
     if (int rc = check_run(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, stats,
                            totals, hist, hipStreamPerThread, r))
         return rc;
     if (contrib)
         if (int rc = check_contrib(n_param, n_meas, samples, cc, *contrib)) return rc;
+    if (quant)
+        if (int rc = mcq::check(samples, n_meas, quant->probs, quant->n_q, qc, sys, quant->out, quant->z)) return rc;  // (the rows are the run's own)
     if (samples == 0) return EZPZ_OK;
     McPlan& P = plan_of(sys);
     std::lock_guard<std::mutex> lock(P.mu);
@@ -367,8 +410,14 @@ int run_host(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_
         dev.dropped = P.contrib_words.p + 2;
         dev.pivot_rel = contrib->pivot_rel;
     }
+    Quant qdev;
+    if (quant && quant->n_q) {
+        if ((rc = P.quant_out.ensure(n_meas * quant->n_q)) != EZPZ_OK) return rc;
+        qdev = *quant;
+        qdev.out = P.quant_out.p;
+    }
     if (n) HIP_TRY(hipMemcpy(P.x0_in.p, x0, n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = run(sys, P, r, P.x0_in.p, positions, records, samples, cfg, P.stats_out.p, P.totals_out.p, P.hist_out.p, keep, dev,
+    if ((rc = run(sys, P, r, P.x0_in.p, positions, records, samples, cfg, P.stats_out.p, P.totals_out.p, P.hist_out.p, keep, dev, qdev,
                   hipStreamPerThread)) != EZPZ_OK)
         return rc;
     HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
@@ -384,6 +433,7 @@ int run_host(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_
         HIP_TRY(hipMemcpy(contrib->info, dev.info, sizeof(EzpzMcMomentsInfo), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(contrib->dropped, dev.dropped, sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
+    if (qdev.n_q) HIP_TRY(hipMemcpy(quant->out, qdev.out, n_meas * qdev.n_q * sizeof(EzpzMcQuantile), hipMemcpyDeviceToHost));
     return EZPZ_OK;
 }
 
@@ -652,7 +702,7 @@ int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const
                                     uint8_t* keep_ok_dev, void* stream) {
     return run_device(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                       stats_dev, totals_dev, hist_dev, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr,
-                      (hipStream_t)stream);
+                      nullptr, nullptr, (hipStream_t)stream);
 }
 
 int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -661,7 +711,7 @@ int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* 
                              EzpzMcStats* stats, EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m,
                              uint8_t* keep_flags, uint8_t* keep_ok) {
     return run_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg, stats,
-                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr);
+                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, nullptr, nullptr);
 }
 
 int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
@@ -676,7 +726,7 @@ int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_de
     c.moments = moments_dev, c.info = info_dev, c.cov = cov_dev, c.beta = beta_dev, c.contrib = contrib_dev, c.r2 = r2_dev, c.dropped = dropped_dev;
     return run_device(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                       stats_dev, totals_dev, hist_dev, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, cc, &c,
-                      (hipStream_t)stream);
+                      nullptr, nullptr, (hipStream_t)stream);
 }
 
 int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -689,7 +739,35 @@ int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const ui
     Contrib c;
     c.moments = moments, c.info = info, c.cov = cov, c.beta = beta, c.contrib = contrib, c.r2 = r2, c.dropped = dropped;
     return run_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg, stats,
-                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, cc, &c);
+                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, cc, &c, nullptr, nullptr);
+}
+
+int ezpz_system_tolerance_mc_quantiles_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                              const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records,
+                                              size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
+                                              const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg,
+                                              EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev,
+                                              double* keep_params_dev, double* keep_m_dev, uint8_t* keep_flags_dev,
+                                              uint8_t* keep_ok_dev, const double* probs, size_t n_q, const EzpzMcQuantileConfig* qc,
+                                              EzpzMcQuantile* out_dev, void* stream) {
+    Quant q;
+    q.probs = probs, q.n_q = n_q, q.out = out_dev;
+    return run_device(sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                      stats_dev, totals_dev, hist_dev, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr,
+                      qc, &q, (hipStream_t)stream);
+}
+
+int ezpz_system_tolerance_mc_quantiles(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
+                                       const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                       const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                       uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats,
+                                       EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags,
+                                       uint8_t* keep_ok, const double* probs, size_t n_q, const EzpzMcQuantileConfig* qc,
+                                       EzpzMcQuantile* out) {
+    Quant q;
+    q.probs = probs, q.n_q = n_q, q.out = out;
+    return run_host(sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg, stats,
+                    totals, hist, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, qc, &q);
 }
 
 int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,

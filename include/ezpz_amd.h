@@ -958,6 +958,76 @@ int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, co
                                        double* total_var_dev, double* keep_f_dev, uint8_t* keep_flags_dev, uint8_t* keep_ok_dev,
                                        void* stream);
 
+/* ---- Monte-Carlo quantiles: exact order statistics of a reference dimension, selected on the device (a project
+ * extension).  mean and std describe a spread that is symmetric; a tolerance report asks where the 0.135 % and 99.865 % points and the
+ * median are, and how sure those figures are at this sample count.  A selection is comparisons and integer counts: it has no floating
+ * sum, so its output is the same bytes for any round size, any stream and any device, and on the host, with no order to prescribe.
+ * VALIDITY.  Sample b is VALID FOR record i exactly as in the Monte-Carlo section: it is ok (the run: that section's rule;
+ * ezpz_mc_quantiles: ok[b] != 0, ok == NULL: every one), flag bit 0 of (b, i) is clear (flags == NULL: every one) and m[b][i] is finite.
+ * THE ORDER.  Values are ordered by key(m) = bits(m) ^ (bits(m) >> 63 ? ~0ull : 1ull << 63), compared as uint64: the total order on
+ * finite doubles, with -0.0 before +0.0.  Equal keys are indistinguishable, so ties need no rule.  Sorted by key, the valid values of
+ * record i are x_0 <= .. <= x_{n-1}, n = n_valid.
+ * THE RANKS, for a probability p in [0, 1], each operation rounded once:
+ *   h = p * (double)(n - 1);   k = (uint64)floor(h);   g = h - (double)k;   lo = x_k;   hi = x_{min(k + 1, n - 1)}
+ *   value = g == 0 ? lo : lo + g * (hi - lo)      the product rounded, then added; no contraction on the host or on the device
+ * THE BAND, distribution-free, for a call-wide z >= 0 (EzpzMcQuantileConfig; ezpz_default_mc_quantile_config: 0):
+ *   s = sqrt(((double)n * p) * (1 - p));   a = h - z * s;   b = h + z * s
+ *   k_lo = a <= 0 ? 0 : (uint64)floor(a);   k_hi = b >= (double)(n - 1) ? n - 1 : (uint64)ceil(b)
+ *   band_lo = x_{k_lo};   band_hi = x_{k_hi}
+ * THE OUTPUT.  out [n_meas][n_q], one EzpzMcQuantile per (record, probability): n_valid, rank = k, rank_lo = k_lo, rank_hi = k_hi,
+ * frac = g, lo, hi, value, band_lo, band_hi.  With n == 0 the ranks are UINT64_MAX and the doubles NaN.
+ * LIMITS.  n_q <= EZPZ_MC_QUANTILE_MAX_PROBS, n_meas <= EZPZ_MC_QUANTILE_MAX_MEAS, samples < 2^32.
+ * ezpz_mc_quantiles[_device]: the selection alone on any kept rows -- m [samples][n_meas], flags [samples][n_meas] bytes, ok
+ * [samples] bytes -- no system involved.  probs [n_q] and the config are host pointers in both forms.  The host form computes on the
+ * host, with no device (a sort of the keys).  The _device form takes device pointers for m, flags, ok and out; it only enqueues on
+ * `stream` and does not synchronise: a most-significant-digit radix select over the keys, eight digits of eight bits.  Digit pass 0
+ * counts every valid key by its top byte, which gives n_valid; a closing kernel per record turns (n, probs, z) into at most four
+ * target ranks per probability -- k, k + 1 clamped, k_lo, k_hi -- sorted and made distinct: at most 64 selections a record.  Every
+ * digit pass is two launches: a count of the keys that carry a selection's prefix, by their next digit -- in LDS first, then global
+ * integer atomics -- and the narrowing of every selection's prefix and rank by that digit.  After the last digit a prefix is the key
+ * itself, and the same body as the host form's writes the records.  Nothing floating-point happens before that.  The workspace is
+ * the library's, per device (a workspace that has to grow is first allocated behind the last call's launches); calls on one device
+ * go one behind the other whatever their streams.
+ * ezpz_system_tolerance_mc_quantiles[_device]: ezpz_system_tolerance_mc[_device] -- the same arguments, the same run, stats, totals,
+ * hist and keep_* byte for byte -- plus probs, n_q, the config and out.  The run keeps m, flags and ok of EVERY sample on the device,
+ * in the caller's keep_* buffers where the _device form is given them and else in the plan's workspace, and the selection follows
+ * the last round on the same stream.  THE WORKSPACE COSTS samples x n_meas x 9 + samples BYTES: this is the one entry of the family
+ * whose memory grows with `samples`, not with chunk.  The _device form takes a device pointer for out too.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: a limit exceeded, or n_meas == 0; a p outside [0, 1] or not
+ * finite; z negative or not finite; probs or out NULL with n_q > 0; m NULL with samples > 0; for the run every argument error of
+ * ezpz_system_tolerance_mc.  samples == 0 or n_q == 0: EZPZ_OK after those checks, nothing written (the run with n_q == 0 is the
+ * plain run). */
+#define EZPZ_MC_QUANTILE_MAX_PROBS 16u
+#define EZPZ_MC_QUANTILE_MAX_MEAS 64u
+typedef struct EzpzMcQuantileConfig { /* 16 bytes */
+    double z; /* >= 0: the band's half width in standard errors of the rank; default 0 */
+    uint64_t reserved;
+} EzpzMcQuantileConfig;
+typedef struct EzpzMcQuantile { /* one per (record, probability); 80 bytes */
+    uint64_t n_valid, rank, rank_lo, rank_hi;
+    double frac, lo, hi, value, band_lo, band_hi;
+} EzpzMcQuantile;
+void ezpz_default_mc_quantile_config(EzpzMcQuantileConfig* qc);
+int ezpz_mc_quantiles(const double* m, const uint8_t* flags, const uint8_t* ok, uint64_t samples, size_t n_meas, const double* probs,
+                      size_t n_q, const EzpzMcQuantileConfig* qc, EzpzMcQuantile* out);
+int ezpz_mc_quantiles_device(const double* m_dev, const uint8_t* flags_dev, const uint8_t* ok_dev, uint64_t samples, size_t n_meas,
+                             const double* probs, size_t n_q, const EzpzMcQuantileConfig* qc, EzpzMcQuantile* out_dev, void* stream);
+int ezpz_system_tolerance_mc_quantiles(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
+                                       const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                       const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                       uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats,
+                                       EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags,
+                                       uint8_t* keep_ok, const double* probs, size_t n_q, const EzpzMcQuantileConfig* qc,
+                                       EzpzMcQuantile* out);
+int ezpz_system_tolerance_mc_quantiles_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                              const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records,
+                                              size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
+                                              const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg,
+                                              EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev,
+                                              double* keep_params_dev, double* keep_m_dev, uint8_t* keep_flags_dev,
+                                              uint8_t* keep_ok_dev, const double* probs, size_t n_q, const EzpzMcQuantileConfig* qc,
+                                              EzpzMcQuantile* out_dev, void* stream);
+
 /* ---- Dimension targets: solve driving dimensions for measured targets (a project extension) -- the inverse of the
  * entries above: which values of the driving dimensions (the constraints at `positions`, as ezpz_system_solve_batch_params takes
  * them) put the reference dimensions `records` (measurement records, as ezpz_system_measure takes them; host memory in both forms)
