@@ -513,6 +513,11 @@ class SolveOutcome:
         return bool(self._raw.unsatisfied)
 
 
+def _ptr(a):
+    """The address ctypes takes for an optional array: None for None and for an empty one."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
 def stack_records(records) -> np.ndarray:
     if isinstance(records, np.ndarray) and records.dtype == CONSTRAINT_DTYPE:
         return np.ascontiguousarray(records).reshape(-1)
@@ -1186,6 +1191,12 @@ class System:
             raise NonLinearSystemError(rc)
 
     # ---- Monte-Carlo tolerance analysis (ezpz_system_tolerance_mc) ---------------------------------------------------------------
+    def _mc_x0(self, x0):
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if x0.size != self.n_vars:
+            raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
+        return x0
+
     def _mc_request(self, positions, dists, records, nominal, limits, hist, seed, chunk):
         pos = self._positions(positions)
         d = mc_dists(dists)
@@ -1228,9 +1239,7 @@ class System:
         quantile_z: the band's half width in standard errors of the rank.  Not together with contributors."""
         if quantiles is not None and contributors:
             raise ValueError("quantiles together with contributors: run them one after the other")
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
-        if x0.size != self.n_vars:
-            raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
+        x0 = self._mc_x0(x0)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         k, n_param, samples = len(recs), len(pos), int(samples)
@@ -1240,14 +1249,13 @@ class System:
         kept = (np.zeros((samples, n_param)), np.zeros((samples, k)), np.zeros((samples, k), np.uint8),
                 np.zeros(samples, np.uint8)) if keep else (None,) * 4
         cfg = (config or Config())._c()
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        args = (self._h, ptr(x0), ptr(pos), n_param, ptr(d), ptr(nominal), ptr(recs), k, ptr(lim_lo), ptr(lim_hi), ptr(hist_lo), ptr(hist_hi),
-                samples, C.byref(mc), C.byref(cfg), stats.ctypes.data, totals.ctypes.data, ptr(counts), *(ptr(a) for a in kept))
+        args = (self._h, _ptr(x0), _ptr(pos), n_param, _ptr(d), _ptr(nominal), _ptr(recs), k, _ptr(lim_lo), _ptr(lim_hi), _ptr(hist_lo), _ptr(hist_hi),
+                samples, C.byref(mc), C.byref(cfg), stats.ctypes.data, totals.ctypes.data, _ptr(counts), *(_ptr(a) for a in kept))
         if quantiles is not None:
             probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
             out = np.zeros((k, len(probs)), dtype=MC_QUANTILE_DTYPE)
             qc = CMcQuantileConfig(float(quantile_z), 0)
-            rc = lib().ezpz_system_tolerance_mc_quantiles(*args, ptr(probs), len(probs), C.byref(qc), ptr(out))
+            rc = lib().ezpz_system_tolerance_mc_quantiles(*args, _ptr(probs), len(probs), C.byref(qc), _ptr(out))
             if rc != 0:
                 raise NonLinearSystemError(rc)
             return McResult(stats, totals, counts, kept if keep else None, quantiles=out)
@@ -1258,7 +1266,7 @@ class System:
             return McResult(stats, totals, counts, kept if keep else None)
         cc = _contrib_config(pivot_rel)
         moments, info, out = _contrib_outputs(n_param, k)
-        rc = lib().ezpz_system_tolerance_mc_contrib(*args, C.byref(cc), moments.ctypes.data, info.ctypes.data, *(ptr(a) for a in out))
+        rc = lib().ezpz_system_tolerance_mc_contrib(*args, C.byref(cc), moments.ctypes.data, info.ctypes.data, *(_ptr(a) for a in out))
         if rc != 0:
             raise NonLinearSystemError(rc)
         n_complete = int(info["n_complete"][0]) if samples else 0
@@ -1282,14 +1290,13 @@ class System:
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        args = (self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs), ptr(lim_lo), ptr(lim_hi), ptr(hist_lo),
-                ptr(hist_hi), int(samples), C.byref(mc), C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
+        args = (self._h, x0_ptr or None, _ptr(pos), len(pos), _ptr(d), _ptr(nominal), _ptr(recs), len(recs), _ptr(lim_lo), _ptr(lim_hi), _ptr(hist_lo),
+                _ptr(hist_hi), int(samples), C.byref(mc), C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
                 keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None)
         if quantiles is not None:
             probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
             qc = CMcQuantileConfig(float(quantile_z), 0)
-            rc = lib().ezpz_system_tolerance_mc_quantiles_device(*args, ptr(probs), len(probs), C.byref(qc), quantiles_ptr or None, stream or None)
+            rc = lib().ezpz_system_tolerance_mc_quantiles_device(*args, _ptr(probs), len(probs), C.byref(qc), quantiles_ptr or None, stream or None)
         elif moments_ptr:
             cc = _contrib_config(pivot_rel)
             rc = lib().ezpz_system_tolerance_mc_contrib_device(*args, C.byref(cc), moments_ptr, info_ptr or None, cov_ptr or None, beta_ptr or None,
@@ -1307,20 +1314,17 @@ class System:
         driven solves from x0 -- the nominal solution -- for k' dimensions that are not FIXED, reduced on the device.  seed: matrix
         A's (the draws of `tolerance_mc` with this seed); seed_b: matrix B's (None: seed ^ 0x9E3779B97F4A7C15); chunk: samples per
         round (0: the library's choice); keep: also every row's f [samples, k + 2, n_meas], flags and ok [samples, k + 2]."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
-        if x0.size != self.n_vars:
-            raise ValueError(f"x0: expected {self.n_vars} values, got {x0.size}")
+        x0 = self._mc_x0(x0)
         pos, d, recs, nominal, _, _, _, _, mc = self._mc_request(positions, dists, records, nominal, None, None, seed, chunk)
         m, k, samples = len(recs), len(pos), int(samples)
-        sc = CSobolConfig((int(seed) ^ SOBOL_SEED_B if seed_b is None else int(seed_b)) & 0xFFFFFFFFFFFFFFFF, 0)
+        sc = _sobol_config(seed, seed_b)
         stats, totals = np.zeros(m, dtype=MC_STATS_DTYPE), np.zeros(1, dtype=MC_TOTALS_DTYPE)
         sums, n_complete, out = _sobol_outputs(k, m)
         kept = (np.zeros((samples, k + 2, m)), np.zeros((samples, k + 2, m), np.uint8), np.zeros((samples, k + 2), np.uint8)) if keep else (None,) * 3
         cfg = (config or Config())._c()
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_tolerance_sobol(self._h, ptr(x0), ptr(pos), k, ptr(d), ptr(nominal), ptr(recs), m, samples, C.byref(mc), C.byref(cfg),
-                                               C.byref(sc), ptr(stats), totals.ctypes.data, ptr(sums), ptr(n_complete), *(ptr(a) for a in out),
-                                               *(ptr(a) for a in kept))
+        rc = lib().ezpz_system_tolerance_sobol(self._h, _ptr(x0), _ptr(pos), k, _ptr(d), _ptr(nominal), _ptr(recs), m, samples, C.byref(mc), C.byref(cfg),
+                                               C.byref(sc), _ptr(stats), totals.ctypes.data, _ptr(sums), _ptr(n_complete), *(_ptr(a) for a in out),
+                                               *(_ptr(a) for a in kept))
         if rc != 0:
             raise NonLinearSystemError(rc)
         return SobolResult(stats, totals, sums, n_complete, *out, kept if keep else None, sc.seed_b)
@@ -1333,10 +1337,9 @@ class System:
         n_param], n_complete uint64 [n_meas], var [n_meas], first, total, first_var, total_var [n_meas, n_param]) and a hipStream_t
         handle; positions, dists, records and nominal stay host values.  Enqueues only once the run's tables are the last run's."""
         pos, d, recs, nominal, _, _, _, _, mc = self._mc_request(positions, dists, records, nominal, None, None, seed, chunk)
-        sc = CSobolConfig((int(seed) ^ SOBOL_SEED_B if seed_b is None else int(seed_b)) & 0xFFFFFFFFFFFFFFFF, 0)
+        sc = _sobol_config(seed, seed_b)
         cfg = (config or Config())._c()
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_tolerance_sobol_device(self._h, x0_ptr or None, ptr(pos), len(pos), ptr(d), ptr(nominal), ptr(recs), len(recs),
+        rc = lib().ezpz_system_tolerance_sobol_device(self._h, x0_ptr or None, _ptr(pos), len(pos), _ptr(d), _ptr(nominal), _ptr(recs), len(recs),
                                                       int(samples), C.byref(mc), C.byref(cfg), C.byref(sc), stats_ptr or None, totals_ptr or None,
                                                       sums_ptr or None, n_complete_ptr or None, var_ptr or None, first_ptr or None,
                                                       total_ptr or None, first_var_ptr or None, total_var_ptr or None, keep_f_ptr or None,
@@ -1363,9 +1366,8 @@ class System:
         batch, samples = x0.shape[0], int(samples)
         info, branches, x, labels = _branch_outputs(batch, samples, self.n_vars, bc.max_branches, keep)
         cfg = (config or Config())._c()
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_solve_branches(self._h, ptr(x0), ptr(d), ptr(mask), batch, samples, C.byref(bc), C.byref(cfg), ptr(info),
-                                              ptr(branches), ptr(x), ptr(labels))
+        rc = lib().ezpz_system_solve_branches(self._h, _ptr(x0), _ptr(d), _ptr(mask), batch, samples, C.byref(bc), C.byref(cfg), _ptr(info),
+                                              _ptr(branches), _ptr(x), _ptr(labels))
         if rc != 0:
             raise NonLinearSystemError(rc)
         return BranchResult(info, branches, x, labels)
@@ -1378,8 +1380,7 @@ class System:
         handle; dists, compare and the configs stay host values.  Enqueues only once the run's tables are the last run's."""
         d, mask, bc = self._branch_request(dists, compare, seed, branch)
         cfg = (config or Config())._c()
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_solve_branches_device(self._h, x0_ptr or None, ptr(d), ptr(mask), int(batch), int(samples), C.byref(bc),
+        rc = lib().ezpz_system_solve_branches_device(self._h, x0_ptr or None, _ptr(d), _ptr(mask), int(batch), int(samples), C.byref(bc),
                                                      C.byref(cfg), info_ptr or None, branches_ptr or None, x_branch_ptr or None,
                                                      keep_label_ptr or None, stream or None)
         if rc != 0:
@@ -1407,9 +1408,8 @@ class System:
         params, x, m = np.zeros((batch, n_param)), np.zeros((batch, self.n_vars)), np.zeros((batch, k))
         info = np.zeros(batch, dtype=SEEK_INFO_DTYPE)
         trace = np.zeros((batch, c.max_iterations + 1)) if want_trace else None
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        rc = lib().ezpz_system_seek_targets(self._h, ptr(x0), ptr(pos), n_param, ptr(params0), ptr(recs), k, ptr(targets), batch,
-                                            C.byref(c), ptr(params), ptr(x), ptr(m), ptr(info), ptr(trace))
+        rc = lib().ezpz_system_seek_targets(self._h, _ptr(x0), _ptr(pos), n_param, _ptr(params0), _ptr(recs), k, _ptr(targets), batch,
+                                            C.byref(c), _ptr(params), _ptr(x), _ptr(m), _ptr(info), _ptr(trace))
         del keep
         if rc != 0:
             raise NonLinearSystemError(rc)
@@ -1501,8 +1501,7 @@ def seek_step(p, m, D, targets, mu: float, config: Optional[SeekConfig] = None):
         raise ValueError(f"D, targets: expected ({len(m)}, {len(p)}) and ({len(m)},), got {D.shape} and {targets.shape}")
     c, keep = (config or SeekConfig())._c(len(p), len(m))
     p_trial, delta, held = np.zeros(len(p)), np.zeros(len(p)), C.c_uint32(0)
-    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-    rc = lib().ezpz_seek_step(len(p), len(m), ptr(p), ptr(m), ptr(D), ptr(targets), C.byref(c), float(mu), ptr(p_trial), ptr(delta),
+    rc = lib().ezpz_seek_step(len(p), len(m), _ptr(p), _ptr(m), _ptr(D), _ptr(targets), C.byref(c), float(mu), _ptr(p_trial), _ptr(delta),
                               C.byref(held))
     del keep
     if rc < 0:
@@ -1613,6 +1612,11 @@ class McContributors:
             return self.cov / np.sqrt(np.outer(np.diag(self.cov), np.diag(self.cov)))
 
 
+def _sobol_config(seed, seed_b) -> CSobolConfig:
+    """seed_b None: matrix B's seed follows from matrix A's."""
+    return CSobolConfig((int(seed) ^ SOBOL_SEED_B if seed_b is None else int(seed_b)) & 0xFFFFFFFFFFFFFFFF, 0)
+
+
 def _contrib_config(pivot_rel) -> CMcContribConfig:
     cc = CMcContribConfig()
     lib().ezpz_default_mc_contrib_config(C.byref(cc))
@@ -1643,9 +1647,8 @@ def mc_moments(params, m, flags, ok, nominal_p, nominal_m, chunk: int = 0):
     if nominal_p.shape != (n_param,) or nominal_m.shape != (n_meas,):
         raise ValueError(f"nominal_p ({n_param},) and nominal_m ({n_meas},): got {nominal_p.shape} and {nominal_m.shape}")
     moments, info, _ = _contrib_outputs(n_param, n_meas)
-    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-    rc = lib().ezpz_mc_moments(ptr(params), ptr(m), ptr(flags), ptr(ok), ptr(nominal_p), ptr(nominal_m), samples, n_param, n_meas, int(chunk),
-                               ptr(moments), info.ctypes.data)
+    rc = lib().ezpz_mc_moments(_ptr(params), _ptr(m), _ptr(flags), _ptr(ok), _ptr(nominal_p), _ptr(nominal_m), samples, n_param, n_meas, int(chunk),
+                               _ptr(moments), info.ctypes.data)
     if rc != 0:
         raise NonLinearSystemError(rc)
     return moments, int(info["n_complete"][0])
@@ -1660,8 +1663,7 @@ def mc_contributors(moments, n_complete: int, n_param: int, n_meas: int, pivot_r
         raise ValueError(f"moments: expected K + K (K + 1) / 2 values with 1 <= K = {K} <= {MC_MOMENT_MAX}, got {moments.shape}")
     cc = _contrib_config(pivot_rel)
     _, _, out = _contrib_outputs(n_param, n_meas)
-    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-    rc = lib().ezpz_mc_contributors(moments.ctypes.data, int(n_complete), n_param, n_meas, C.byref(cc), *(ptr(a) for a in out))
+    rc = lib().ezpz_mc_contributors(moments.ctypes.data, int(n_complete), n_param, n_meas, C.byref(cc), *(_ptr(a) for a in out))
     if rc != 0:
         raise NonLinearSystemError(rc)
     return McContributors(moments, n_complete, n_param, n_meas, *out)
@@ -1682,8 +1684,7 @@ def mc_quantiles(m, flags, ok, probs, z: float = 0.0) -> np.ndarray:
     probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
     out = np.zeros((min(n_meas, MC_QUANTILE_MAX_MEAS), min(len(probs), MC_QUANTILE_MAX_PROBS)), dtype=MC_QUANTILE_DTYPE)
     qc = CMcQuantileConfig(float(z), 0)
-    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-    rc = lib().ezpz_mc_quantiles(ptr(m), ptr(flags), ptr(ok), samples, n_meas, ptr(probs), len(probs), C.byref(qc), ptr(out))
+    rc = lib().ezpz_mc_quantiles(_ptr(m), _ptr(flags), _ptr(ok), samples, n_meas, _ptr(probs), len(probs), C.byref(qc), _ptr(out))
     if rc != 0:
         raise NonLinearSystemError(rc)
     return out
@@ -1751,9 +1752,8 @@ def mc_sobol_sums(f, flags, ok, nominal_m, fixed_mask: int = 0, chunk: int = 0):
     if nominal_m.shape != (n_meas,):
         raise ValueError(f"nominal_m ({n_meas},): got {nominal_m.shape}")
     sums, n_complete, _ = _sobol_outputs(min(n_param, SOBOL_MAX), min(n_meas, SOBOL_MAX))
-    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-    rc = lib().ezpz_mc_sobol_sums(ptr(f), ptr(flags), ptr(ok), ptr(nominal_m), int(fixed_mask), samples, n_param, n_meas, int(chunk), ptr(sums),
-                                  ptr(n_complete))
+    rc = lib().ezpz_mc_sobol_sums(_ptr(f), _ptr(flags), _ptr(ok), _ptr(nominal_m), int(fixed_mask), samples, n_param, n_meas, int(chunk), _ptr(sums),
+                                  _ptr(n_complete))
     if rc != 0:
         raise NonLinearSystemError(rc)
     return sums, n_complete
@@ -1767,8 +1767,7 @@ def mc_sobol_indices(sums, n_complete) -> SobolIndices:
         raise ValueError(f"sums [n_meas, 4 + 4 n_param] and n_complete [n_meas]: got {sums.shape} and {n_complete.shape}")
     n_meas, n_param = sums.shape[0], sums.shape[1] // 4 - 1
     _, _, out = _sobol_outputs(min(n_param, SOBOL_MAX), min(n_meas, SOBOL_MAX))
-    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-    rc = lib().ezpz_mc_sobol_indices(ptr(sums), ptr(n_complete), n_param, n_meas, *(ptr(a) for a in out))
+    rc = lib().ezpz_mc_sobol_indices(_ptr(sums), _ptr(n_complete), n_param, n_meas, *(_ptr(a) for a in out))
     if rc != 0:
         raise NonLinearSystemError(rc)
     return SobolIndices(sums, n_complete, *out)
@@ -1827,9 +1826,8 @@ def cluster_branches(x, ok=None, compare=None, branch: Optional[BranchConfig] = 
         ok = np.ascontiguousarray(np.asarray(ok).reshape(batch, samples) != 0, dtype=np.uint8)
     mask, bc = _compare_mask(compare, n_vars), (branch or BranchConfig())._c()
     info, branches, xb, labels = _branch_outputs(batch, samples, n_vars, bc.max_branches, keep)
-    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-    rc = lib().ezpz_branch_cluster(ptr(x), ptr(ok), ptr(mask), batch, samples, n_vars, C.byref(bc), ptr(info), ptr(branches), ptr(xb),
-                                   ptr(labels))
+    rc = lib().ezpz_branch_cluster(_ptr(x), _ptr(ok), _ptr(mask), batch, samples, n_vars, C.byref(bc), _ptr(info), _ptr(branches), _ptr(xb),
+                                   _ptr(labels))
     if rc != 0:
         raise NonLinearSystemError(rc)
     return BranchResult(info, branches, xb, labels)

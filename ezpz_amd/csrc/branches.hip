@@ -44,16 +44,6 @@ BranchPlan& plan_of(EzpzSystem* sys) {
     return *static_cast<BranchPlan*>(sys->branches.get());
 }
 
-// ezpz_branch_cluster has no system: its workspace is the process's, one per device (never destroyed: the runtime may be gone first)
-BranchPlan* plan_of_device(int device) {
-    static std::mutex mu;
-    static BranchPlan* plans[16] = {};
-    if (device < 0 || device >= 16) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!plans[device]) plans[device] = new BranchPlan;
-    return plans[device];
-}
-
 struct Request {
     std::vector<uint32_t> cmp;    // the compared variables, ascending
     std::vector<mc::Dist> dists;  // the run's sampler table (nominal unused: the start kernel takes it per base)
@@ -87,8 +77,7 @@ int check_rule(const uint8_t* compare, size_t n_vars, uint64_t batch, uint64_t s
         chunk = kDefaultChunk;
         while (chunk > kBlock && chunk > kChunkValueBytes / sizeof(double) / per_sample) chunk /= 2;
     }
-    chunk = (std::min<uint64_t>(chunk, 1ull << 30) + kBlock - 1) / kBlock * kBlock;  // (a round's sample index is 32 bits)
-    r.chunk = std::min<uint64_t>(chunk, (std::max<uint64_t>(samples, 1) + kBlock - 1) / kBlock * kBlock);
+    r.chunk = round_chunk(chunk, samples, kBlock);
     // a round's workspace is batch x chunk x n_vars values: no product below may wrap
     if (r.chunk > kMaxRoundValues / per_sample) return EZPZ_ERR_TOO_LARGE;
     return EZPZ_OK;
@@ -313,10 +302,9 @@ int ezpz_branch_cluster_device(const double* x_dev, const uint8_t* ok_dev, const
     Request r;
     if (int rc = check_cluster(x_dev, batch, samples, n_vars, compare, bcfg, info_dev, branches_dev, x_branch_dev, r)) return rc;
     if (samples == 0 || batch == 0) return EZPZ_OK;
+    BranchPlan* P = nullptr;
     int device = -1;
-    HIP_TRY(hipGetDevice(&device));
-    BranchPlan* P = plan_of_device(device);
-    if (!P) return EZPZ_ERR_NO_DEVICE;
+    if (int rc = plan_of_device(P, device)) return device < 0 ? EZPZ_ERR_HIP : rc;  // (a failing hipGetDevice is the runtime's error here, as ever)
     std::lock_guard<std::mutex> lock(P->mu);
     return cluster(*P, r, device_limits(device).cus, x_dev, ok_dev, batch, samples, n_vars, info_dev, branches_dev, x_branch_dev, keep_label_dev,
                    (hipStream_t)stream);
@@ -327,13 +315,10 @@ int ezpz_branch_cluster(const double* x, const uint8_t* ok, const uint8_t* compa
     Request r;
     if (int rc = check_cluster(x, batch, samples, n_vars, compare, bcfg, info, branches, x_branch, r)) return rc;
     if (samples == 0 || batch == 0) return EZPZ_OK;
+    // ezpz_branch_cluster has no system: its workspace is the process's, one per device (system.hpp: plan_of_device)
+    BranchPlan* P = nullptr;
     int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) {
-        (void)hipGetLastError();
-        return EZPZ_ERR_NO_DEVICE;
-    }
-    BranchPlan* P = plan_of_device(device);
-    if (!P) return EZPZ_ERR_NO_DEVICE;
+    if (int rc = plan_of_device(P, device)) return rc;
     std::lock_guard<std::mutex> lock(P->mu);
     int rc;
     // (the buffers of an earlier host call are idle: it waited for its launches)

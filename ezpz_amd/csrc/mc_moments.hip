@@ -47,9 +47,8 @@ namespace {
 using namespace ezpz::mcm;
 
 constexpr uint64_t kBlock = 256;
-constexpr uint64_t kDefaultChunk = 65536;
 
-// ezpz_mc_moments has no system: its workspace is the process's, one per device (never destroyed: the runtime may be gone first)
+// ezpz_mc_moments has no system: its workspace is the process's, one per device (system.hpp: plan_of_device)
 struct MomentPlan {
     std::mutex mu;  // a call holds it from its first allocation to its last enqueue
     LaunchOrder order;  // the completion of the last call's launches
@@ -60,24 +59,13 @@ struct MomentPlan {
     DevBuf<EzpzMcMomentsInfo> info_out;
 };
 
-MomentPlan* plan_of_device(int device) {
-    static std::mutex mu;
-    static MomentPlan* plans[16] = {};
-    if (device < 0 || device >= 16) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!plans[device]) plans[device] = new MomentPlan;
-    return plans[device];
-}
-
 // Every argument error of the reduction alone, before anything is enqueued or written; the pointers are only compared with NULL.
 int check_moments(const void* params, const void* m, const void* nominal_p, const void* nominal_m, uint64_t samples, size_t n_param,
                   size_t n_meas, uint32_t chunk_in, const void* moments, const void* info, uint64_t& chunk) {
     if (int rc = check_shape(n_param, n_meas)) return rc;
     if (samples && (!moments || !info || (n_param && (!params || !nominal_p)) || (n_meas && (!m || !nominal_m)))) return EZPZ_ERR_INVALID_ARGUMENT;
     if (samples > 0xFFFFFFFFFFFFull) return EZPZ_ERR_TOO_LARGE;
-    chunk = chunk_in ? chunk_in : kDefaultChunk;
-    chunk = (std::min<uint64_t>(chunk, 1ull << 30) + kBlock - 1) / kBlock * kBlock;
-    chunk = std::min<uint64_t>(chunk, (std::max<uint64_t>(samples, 1) + kBlock - 1) / kBlock * kBlock);
+    chunk = round_chunk(chunk_in ? chunk_in : kDefaultSampleChunk, samples, kBlock);
     return EZPZ_OK;
 }
 
@@ -123,13 +111,9 @@ int ezpz_mc_moments_device(const double* params_dev, const double* m_dev, const 
         return rc;
     if (samples == 0) return EZPZ_OK;
     hipStream_t stream = (hipStream_t)stream_;
+    MomentPlan* P = nullptr;
     int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) {
-        (void)hipGetLastError();
-        return EZPZ_ERR_NO_DEVICE;
-    }
-    MomentPlan* P = plan_of_device(device);
-    if (!P) return EZPZ_ERR_NO_DEVICE;
+    if (int rc = plan_of_device(P, device)) return rc;
     std::lock_guard<std::mutex> lock(P->mu);
     int rc;
     if ((rc = grow(*P, chunk, (uint32_t)(n_param + n_meas))) != EZPZ_OK || (rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
@@ -154,13 +138,9 @@ int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags,
     uint64_t chunk = 0;
     if (int rc = check_moments(params, m, nominal_p, nominal_m, samples, n_param, n_meas, chunk_in, moments, info, chunk)) return rc;
     if (samples == 0) return EZPZ_OK;
+    MomentPlan* P = nullptr;
     int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) {
-        (void)hipGetLastError();
-        return EZPZ_ERR_NO_DEVICE;
-    }
-    MomentPlan* P = plan_of_device(device);
-    if (!P) return EZPZ_ERR_NO_DEVICE;
+    if (int rc = plan_of_device(P, device)) return rc;
     std::lock_guard<std::mutex> lock(P->mu);
     const uint32_t K = (uint32_t)(n_param + n_meas);
     const hipStream_t stream = hipStreamPerThread;

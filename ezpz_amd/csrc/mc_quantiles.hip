@@ -54,23 +54,14 @@ namespace {
 
 using namespace ezpz::mcq;
 
-// ezpz_mc_quantiles_device has no system: its workspace is the process's, one per device (never destroyed: the runtime may be gone
-// first) -- a sibling of ezpz_mc_sobol_sums_device's plan
+// ezpz_mc_quantiles_device has no system: its workspace is the process's, one per device (system.hpp: plan_of_device)
+// -- a sibling of ezpz_mc_sobol_sums_device's plan
 struct SelectPlan {
     std::mutex mu;      // a call holds it from its first allocation to its last enqueue
     LaunchOrder order;  // the completion of the last call's launches
     SelectWork work;
     uint32_t cus = 0;
 };
-
-SelectPlan* plan_of_device(int device) {
-    static std::mutex mu;
-    static SelectPlan* plans[16] = {};
-    if (device < 0 || device >= 16) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!plans[device]) plans[device] = new SelectPlan;
-    return plans[device];
-}
 
 }  // namespace
 
@@ -91,13 +82,9 @@ int ezpz_mc_quantiles_device(const double* m_dev, const uint8_t* flags_dev, cons
     if (int rc = check(samples, n_meas, probs, n_q, qc, m_dev, out_dev, z)) return rc;
     if (samples == 0 || n_q == 0) return EZPZ_OK;
     hipStream_t stream = (hipStream_t)stream_;
+    SelectPlan* P = nullptr;
     int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) {
-        (void)hipGetLastError();
-        return EZPZ_ERR_NO_DEVICE;
-    }
-    SelectPlan* P = plan_of_device(device);
-    if (!P) return EZPZ_ERR_NO_DEVICE;
+    if (int rc = plan_of_device(P, device)) return rc;
     std::lock_guard<std::mutex> lock(P->mu);
     int rc;
     if (!P->cus) {

@@ -51,24 +51,13 @@ namespace {
 
 using namespace ezpz::sobol;
 
-constexpr uint64_t kDefaultChunk = 65536;
-
-// ezpz_mc_sobol_sums_device has no system: its workspace is the process's, one per device (never destroyed: the runtime may be
-// gone first) -- a sibling of ezpz_mc_moments' plan
+// ezpz_mc_sobol_sums_device has no system: its workspace is the process's, one per device (system.hpp:
+// plan_of_device) -- a sibling of ezpz_mc_moments' plan
 struct SumPlan {
     std::mutex mu;      // a call holds it from its first allocation to its last enqueue
     LaunchOrder order;  // the completion of the last call's launches
     SumWork work;
 };
-
-SumPlan* plan_of_device(int device) {
-    static std::mutex mu;
-    static SumPlan* plans[16] = {};
-    if (device < 0 || device >= 16) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!plans[device]) plans[device] = new SumPlan;
-    return plans[device];
-}
 
 }  // namespace
 
@@ -97,17 +86,11 @@ int ezpz_mc_sobol_sums_device(const double* f_dev, const uint8_t* flags_dev, con
     if (samples && (!sums_dev || !n_complete_dev || !f_dev || !nominal_m_dev)) return EZPZ_ERR_INVALID_ARGUMENT;
     if (samples > 0xFFFFFFFFFFFFull) return EZPZ_ERR_TOO_LARGE;
     if (samples == 0) return EZPZ_OK;
-    uint64_t chunk = chunk_in ? chunk_in : kDefaultChunk;
-    chunk = (std::min<uint64_t>(chunk, 1ull << 30) + kBlock - 1) / kBlock * kBlock;
-    chunk = std::min<uint64_t>(chunk, (samples + kBlock - 1) / kBlock * kBlock);
+    const uint64_t chunk = round_chunk(chunk_in ? chunk_in : kDefaultSampleChunk, samples, kBlock);
     hipStream_t stream = (hipStream_t)stream_;
+    SumPlan* P = nullptr;
     int device = -1;
-    if (hipGetDevice(&device) != hipSuccess) {
-        (void)hipGetLastError();
-        return EZPZ_ERR_NO_DEVICE;
-    }
-    SumPlan* P = plan_of_device(device);
-    if (!P) return EZPZ_ERR_NO_DEVICE;
+    if (int rc = plan_of_device(P, device)) return rc;
     std::lock_guard<std::mutex> lock(P->mu);
     const uint32_t k = (uint32_t)n_param, m = (uint32_t)n_meas;
     int rc;

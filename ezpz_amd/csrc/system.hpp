@@ -167,6 +167,34 @@ struct LaunchOrder {
     }
 };
 
+// The plan an entry without a system works on: the process's own, one per type and per device, made under a mutex where the
+// calling thread's current device first asks for it and never destroyed (the runtime may be gone first).  EZPZ_ERR_NO_DEVICE
+// without a current device (`device` stays -1) or with one past the 16 a process keeps plans for.
+template <class Plan>
+int plan_of_device(Plan*& plan, int& device) {
+    static std::mutex mu;
+    static Plan* plans[16] = {};
+    device = -1;
+    if (hipGetDevice(&device) != hipSuccess) {
+        (void)hipGetLastError();
+        device = -1;
+        return EZPZ_ERR_NO_DEVICE;
+    }
+    if (device < 0 || device >= 16) return EZPZ_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!plans[device]) plans[device] = new Plan;
+    plan = plans[device];
+    return EZPZ_OK;
+}
+
+// The samples of a round in the reductions over a caller's samples and in the branch runs: whole blocks of `block`, at most 2^30 (a
+// round's sample index is 32 bits) and no more than `samples` take.
+constexpr uint64_t kDefaultSampleChunk = 65536;  // samples per round where the caller leaves the choice
+inline uint64_t round_chunk(uint64_t chunk, uint64_t samples, uint64_t block) {
+    chunk = (std::min<uint64_t>(chunk, 1ull << 30) + block - 1) / block * block;
+    return std::min<uint64_t>(chunk, (std::max<uint64_t>(samples, 1) + block - 1) / block * block);
+}
+
 // A `positions` list of driven constraints whose device tables a system keeps for a caller that repeats it (touched under the
 // system's launch_mu), and the completion of the last launch that read the tables: one event is what a call with another list waits
 // for before it overwrites them.
