@@ -114,6 +114,14 @@ MC_QUANTILE_DTYPE = np.dtype([("n_valid", "<u8"), ("rank", "<u8"), ("rank_lo", "
 assert C.sizeof(CMcQuantileConfig) == 16 and MC_QUANTILE_DTYPE.itemsize == 80
 
 
+class CMcEffectConfig(C.Structure):
+    _fields_ = [("bins", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+MC_EFFECT_MAX_DIM, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS = 32, 64, 4096  # the section's limits; EZPZ_MC_EFFECT_MAX_*
+assert C.sizeof(CMcEffectConfig) == 8
+
+
 class CBranchConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("max_branches", C.c_uint32), ("eps_abs", C.c_double), ("eps_rel", C.c_double)]
 
@@ -194,6 +202,8 @@ EXPORTS = [
     "ezpz_system_tolerance_sobol", "ezpz_system_tolerance_sobol_device",
     "ezpz_default_mc_quantile_config", "ezpz_mc_quantiles", "ezpz_mc_quantiles_device", "ezpz_system_tolerance_mc_quantiles",
     "ezpz_system_tolerance_mc_quantiles_device",
+    "ezpz_default_mc_effect_config", "ezpz_mc_effect_indices", "ezpz_mc_effects", "ezpz_mc_effects_device",
+    "ezpz_system_tolerance_mc_effects", "ezpz_system_tolerance_mc_effects_device",
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
     "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
     "ezpz_system_solve_branches_device",
@@ -297,6 +307,18 @@ def lib():
     L.ezpz_system_tolerance_mc_quantiles.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp, sz, C.POINTER(CMcQuantileConfig), vp]
     L.ezpz_system_tolerance_mc_quantiles_device.restype = C.c_int
     L.ezpz_system_tolerance_mc_quantiles_device.argtypes = L.ezpz_system_tolerance_mc_quantiles.argtypes + [vp]
+    L.ezpz_default_mc_effect_config.restype = None
+    L.ezpz_default_mc_effect_config.argtypes = [C.POINTER(CMcEffectConfig)]
+    L.ezpz_mc_effect_indices.restype = C.c_int
+    L.ezpz_mc_effect_indices.argtypes = [vp, vp, vp, sz, sz, u32, vp, vp, vp, vp, vp]
+    L.ezpz_mc_effects.restype = C.c_int
+    L.ezpz_mc_effects.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, sz, sz, u32, u32, vp, vp]
+    L.ezpz_mc_effects_device.restype = C.c_int
+    L.ezpz_mc_effects_device.argtypes = L.ezpz_mc_effects.argtypes + [vp]
+    L.ezpz_system_tolerance_mc_effects.restype = C.c_int
+    L.ezpz_system_tolerance_mc_effects.argtypes = L.ezpz_system_tolerance_mc.argtypes + [C.POINTER(CMcEffectConfig)] + [vp] * 8
+    L.ezpz_system_tolerance_mc_effects_device.restype = C.c_int
+    L.ezpz_system_tolerance_mc_effects_device.argtypes = L.ezpz_system_tolerance_mc_effects.argtypes + [vp]
     L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
     L.ezpz_seek_step.restype = C.c_int
     L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1224,7 +1224,8 @@ class System:
 
     def tolerance_mc(self, x0, positions, dists, records, samples: int, seed: int = 0, nominal=None, limits=None, hist=None,
                      chunk: int = 0, keep: bool = False, config: Optional[Config] = None, contributors: bool = False,
-                     pivot_rel: Optional[float] = None, quantiles=None, quantile_z: float = 0.0) -> "McResult":
+                     pivot_rel: Optional[float] = None, quantiles=None, quantile_z: float = 0.0,
+                     effects: Optional["EffectsConfig"] = None) -> "McResult":
         """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
         solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
         statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
@@ -1236,9 +1237,14 @@ class System:
         quantiles: a list of probabilities in [0, 1] -- the same run through `ezpz_system_tolerance_mc_quantiles`: every sample's m,
         flags and ok stay on the device (samples x n_meas x 9 + samples bytes) and the exact order statistics are selected there; the
         result also has `quantiles` (MC_QUANTILE_DTYPE [n_meas, n_q]) and q_value, q_lo, q_hi, q_band_lo, q_band_hi [n_meas, n_q];
-        quantile_z: the band's half width in standard errors of the rank.  Not together with contributors."""
+        quantile_z: the band's half width in standard errors of the rank.  Not together with contributors.
+        effects: an `EffectsConfig` -- the same run through `ezpz_system_tolerance_mc_effects`: every reference dimension's sums and
+        counts per bin of every driving dimension, reduced on the device, and from them the main-effect curves and the first-order
+        indices; the result also has `effects` (an `McEffects`, with the edges used).  Not together with contributors or quantiles."""
         if quantiles is not None and contributors:
             raise ValueError("quantiles together with contributors: run them one after the other")
+        if effects is not None and (contributors or quantiles is not None):
+            raise ValueError("effects together with contributors or quantiles: run them one after the other")
         x0 = self._mc_x0(x0)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
@@ -1259,6 +1265,14 @@ class System:
             if rc != 0:
                 raise NonLinearSystemError(rc)
             return McResult(stats, totals, counts, kept if keep else None, quantiles=out)
+        if effects is not None:
+            ec, edges, bounds = _effects_request(effects, d, pos, nominal, self)
+            sums, cnt, out = _effect_outputs(n_param, k, ec.bins)
+            rc = lib().ezpz_system_tolerance_mc_effects(*args, C.byref(ec), _ptr(edges), _ptr(sums), _ptr(cnt), *(_ptr(a) for a in out))
+            if rc != 0:
+                raise NonLinearSystemError(rc)
+            return McResult(stats, totals, counts, kept if keep else None,
+                            effects=McEffects(sums, cnt, stats["nominal"].copy(), edges, *out, bounds=bounds))
         if not contributors:
             rc = lib().ezpz_system_tolerance_mc(*args)
             if rc != 0:
@@ -1277,16 +1291,24 @@ class System:
                             keep_m_ptr: int = 0, keep_flags_ptr: int = 0, keep_ok_ptr: int = 0, stream: int = 0,
                             config: Optional[Config] = None, moments_ptr: int = 0, info_ptr: int = 0, cov_ptr: int = 0, beta_ptr: int = 0,
                             contrib_ptr: int = 0, r2_ptr: int = 0, dropped_ptr: int = 0, pivot_rel: Optional[float] = None,
-                            quantiles=None, quantile_z: float = 0.0, quantiles_ptr: int = 0) -> None:
+                            quantiles=None, quantile_z: float = 0.0, quantiles_ptr: int = 0, effects: Optional["EffectsConfig"] = None,
+                            effect_sums_ptr: int = 0, effect_counts_ptr: int = 0, cond_mean_ptr: int = 0, cond_var_ptr: int = 0,
+                            eta2_ptr: int = 0, first_ptr: int = 0, bins_used_ptr: int = 0):
         """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], hist: uint64
         [n_meas, bins + 2]) and a hipStream_t handle; positions, dists, records, nominal, limits and hist = (lo, hi, bins) stay host
         values.  Enqueues only once the run's tables are the last run's.  With moments_ptr the run goes through
         `ezpz_system_tolerance_mc_contrib_device` and fills moments [K + K (K + 1) / 2], info (MC_MOMENTS_INFO_DTYPE [1]), cov [K, K],
         beta and contrib [n_meas, n_param], r2 [n_meas] and dropped (uint64 [1]) as well, K = n_param + n_meas.  With quantiles (host
         probabilities) the run goes through `ezpz_system_tolerance_mc_quantiles_device` and fills quantiles_ptr (MC_QUANTILE_DTYPE
-        [n_meas, n_q]); it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given."""
+        [n_meas, n_q]); it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given.  With effects (an
+        `EffectsConfig`, host values) the run goes through `ezpz_system_tolerance_mc_effects_device` and fills effect_sums_ptr [n_param,
+        bins, n_meas, 2], effect_counts_ptr (uint64 [n_param, bins, n_meas]), cond_mean_ptr and cond_var_ptr [n_param, bins, n_meas],
+        eta2_ptr and first_ptr [n_meas, n_param] and bins_used_ptr (uint32 [n_meas, n_param]); the edges used [n_param, bins - 1] are
+        returned (None without effects)."""
         if quantiles is not None and moments_ptr:
             raise ValueError("quantiles together with contributors: run them one after the other")
+        if effects is not None and (quantiles is not None or moments_ptr):
+            raise ValueError("effects together with contributors or quantiles: run them one after the other")
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
@@ -1297,6 +1319,14 @@ class System:
             probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
             qc = CMcQuantileConfig(float(quantile_z), 0)
             rc = lib().ezpz_system_tolerance_mc_quantiles_device(*args, _ptr(probs), len(probs), C.byref(qc), quantiles_ptr or None, stream or None)
+        elif effects is not None:
+            ec, edges, _ = _effects_request(effects, d, pos, nominal, self)
+            rc = lib().ezpz_system_tolerance_mc_effects_device(*args, C.byref(ec), _ptr(edges), effect_sums_ptr or None, effect_counts_ptr or None,
+                                                               cond_mean_ptr or None, cond_var_ptr or None, eta2_ptr or None, first_ptr or None,
+                                                               bins_used_ptr or None, stream or None)
+            if rc != 0:
+                raise NonLinearSystemError(rc)
+            return edges
         elif moments_ptr:
             cc = _contrib_config(pivot_rel)
             rc = lib().ezpz_system_tolerance_mc_contrib_device(*args, C.byref(cc), moments_ptr, info_ptr or None, cov_ptr or None, beta_ptr or None,
@@ -1570,10 +1600,12 @@ class McResult:
     n_ok and n_all_in, and with keep the samples: params, m, flags, ok.  `stats` and `totals` are the library's records.  A run with
     contributors also has moments, n_complete, cov, beta, contrib, r2, dropped (those of its `contributors`, a `McContributors`) and
     `corr`.  A run with quantiles also has `quantiles` (MC_QUANTILE_DTYPE [n_meas, n_q]) and its fields as q_value, q_lo, q_hi,
-    q_band_lo, q_band_hi."""
+    q_band_lo, q_band_hi.  A run with effects also has `effects` (an `McEffects`)."""
 
-    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None):
+    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None, effects=None):
         self.stats, self.totals, self.hist = stats, totals, hist
+        if effects is not None:
+            self.effects = effects
         if quantiles is not None:
             self.quantiles = quantiles
             for f in ("value", "lo", "hi", "band_lo", "band_hi"):
@@ -1688,6 +1720,142 @@ def mc_quantiles(m, flags, ok, probs, z: float = 0.0) -> np.ndarray:
     if rc != 0:
         raise NonLinearSystemError(rc)
     return out
+
+
+class EffectsConfig:
+    """The main effects of a `tolerance_mc` run: `bins` per driving dimension (2 .. 64; n_param x bins x n_meas <= 4096 cells) and
+    their edges [n_param, bins - 1], absolute values, non-decreasing per dimension (+inf edges leave the upper bins empty).
+    edges None: equiprobable edges from the run's distributions (`mc_effect_edges`)."""
+
+    def __init__(self, bins: int = 8, edges=None):
+        self.bins, self.edges = int(bins), edges
+
+
+def mc_effect_edges(dists, nominal, bins: int) -> np.ndarray:
+    """Equiprobable bin edges [n_param, bins - 1] for the distributions `dists` about `nominal`: UNIFORM nominal + a + (b - a) c /
+    bins; NORMAL nominal + sigma z_c, z_c the equiprobable points of the (truncated) normal; CORNER one edge half way between its two
+    values, the rest +inf; a dimension that does not vary (FIXED, sigma == 0, a == b): all +inf, one bin."""
+    from statistics import NormalDist
+
+    d = mc_dists(dists)
+    nominal = np.ascontiguousarray(nominal, dtype=np.float64).reshape(-1)
+    bins = int(bins)
+    if len(nominal) != len(d):
+        raise ValueError(f"nominal: one per distribution ({len(d)}), got {len(nominal)}")
+    if bins < 2:
+        raise ValueError(f"bins: at least 2, got {bins}")
+    edges = np.full((len(d), bins - 1), np.inf)
+    for j in range(len(d)):
+        kind, a, b, nom = int(d["kind"][j]), float(d["a"][j]), float(d["b"][j]), float(nominal[j])
+        if kind == McDist.UNIFORM and a != b:
+            edges[j] = [nom + a + (b - a) * c / bins for c in range(1, bins)]
+        elif kind == McDist.NORMAL and a != 0.0:
+            nd = NormalDist()
+            lo, hi = (nd.cdf(-b), nd.cdf(b)) if b > 0.0 else (0.0, 1.0)
+            edges[j] = [nom + a * nd.inv_cdf(lo + (hi - lo) * c / bins) for c in range(1, bins)]
+        elif kind == McDist.CORNER and a != b:
+            edges[j, 0] = nom + (a + b) / 2.0
+    return edges
+
+
+def _effect_bounds(d, nominal) -> np.ndarray:
+    """[n_param, 2]: the ends of every dimension's tolerance zone, infinite where it has none (an untruncated NORMAL)."""
+    out = np.empty((len(d), 2))
+    for j in range(len(d)):
+        kind, a, b, nom = int(d["kind"][j]), float(d["a"][j]), float(d["b"][j]), float(nominal[j])
+        if kind in (McDist.UNIFORM, McDist.CORNER):
+            out[j] = (nom + min(a, b), nom + max(a, b))
+        elif kind == McDist.NORMAL and b > 0.0:
+            out[j] = (nom - a * b, nom + a * b)
+        elif kind == McDist.NORMAL and a != 0.0:
+            out[j] = (-np.inf, np.inf)
+        else:
+            out[j] = (nom, nom)
+    return out
+
+
+def _effects_request(effects: EffectsConfig, d, pos, nominal, system):
+    """(EzpzMcEffectConfig, the edges used [n_param, bins - 1], the zones' ends [n_param, 2]) of a run with effects."""
+    nom = np.array([system.records["param"][p] for p in pos], dtype=np.float64) if nominal is None else nominal
+    bins = effects.bins
+    if effects.edges is None:
+        edges = mc_effect_edges(d, nom, min(max(bins, 2), MC_EFFECT_MAX_BINS))
+    else:
+        edges = np.ascontiguousarray(effects.edges, dtype=np.float64)
+        if edges.shape != (len(pos), bins - 1):
+            raise ValueError(f"edges: expected shape ({len(pos)}, {bins - 1}), got {edges.shape}")
+    return CMcEffectConfig(bins, 0), edges, _effect_bounds(d, nom)
+
+
+def _effect_outputs(n_param: int, n_meas: int, bins: int):
+    k, m, B = min(n_param, MC_EFFECT_MAX_DIM), min(n_meas, MC_EFFECT_MAX_DIM), min(max(bins, 0), MC_EFFECT_MAX_BINS)
+    return (np.zeros((k, B, m, 2)), np.zeros((k, B, m), np.uint64),
+            (np.zeros((k, B, m)), np.zeros((k, B, m)), np.zeros((m, k)), np.zeros((m, k)), np.zeros((m, k), np.uint32)))
+
+
+class McEffects:
+    """What `mc_effect_indices` returns and a `tolerance_mc` run with effects carries: sums [k, B, m, 2] (sum_d, sum_d2) and counts
+    [k, B, m] per (driving dimension, bin, reference dimension) as given, nominal_m [m], edges [k, B - 1] (None where unknown),
+    cond_mean and cond_var [k, B, m] (the curve and the spread about it; NaN for an empty bin), eta2 and first [m, k] (the
+    correlation ratio and its bias-corrected form, an estimate of the first-order Sobol index) and bins_used [m, k]."""
+
+    def __init__(self, sums, counts, nominal_m, edges, cond_mean, cond_var, eta2, first, bins_used, bounds=None):
+        self.sums, self.counts, self.nominal_m, self.edges = sums, counts, nominal_m, edges
+        self.cond_mean, self.cond_var, self.eta2, self.first, self.bins_used = cond_mean, cond_var, eta2, first, bins_used
+        self.bounds = bounds
+
+    def curve(self, i: int, j: int):
+        """(centres, means, counts) of reference dimension i along driving dimension j: the bins both of whose ends are finite --
+        the edges, and at the two ends the tolerance zone's where the run knew them -- with their centre, conditional mean and
+        count."""
+        if self.edges is None:
+            raise ValueError("curve: the edges are not known here")
+        lo, hi = (-np.inf, np.inf) if self.bounds is None else self.bounds[j]
+        ends = np.concatenate([[lo], self.edges[j], [hi]])
+        with np.errstate(invalid="ignore"):
+            live = np.isfinite(ends[:-1]) & np.isfinite(ends[1:])
+        return ((ends[:-1][live] + ends[1:][live]) / 2.0, self.cond_mean[j, live, i], self.counts[j, live, i])
+
+
+def mc_effects(params, m, flags, ok, nominal_m, edges, chunk: int = 0):
+    """`ezpz_mc_effects`: (sums [n_param, bins, n_meas, 2], counts [n_param, bins, n_meas]) of the samples params [samples, n_param],
+    m [samples, n_meas], flags (the same shape; None: clear) and ok [samples] (None: every one set) about nominal_m, binned by edges
+    [n_param, bins - 1] -- the reduction alone, no system involved.  Computed on the host, in the device's order."""
+    params, m = np.ascontiguousarray(params, dtype=np.float64), np.ascontiguousarray(m, dtype=np.float64)
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    if params.ndim != 2 or m.ndim != 2 or len(params) != len(m) or edges.ndim != 2 or len(edges) != params.shape[1]:
+        raise ValueError(f"params [samples, n_param], m [samples, n_meas] and edges [n_param, bins - 1]: got {params.shape}, {m.shape} and {edges.shape}")
+    samples, n_param, n_meas, bins = len(params), params.shape[1], m.shape[1], edges.shape[1] + 1
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(samples, n_meas)
+    if ok is not None:
+        ok = np.ascontiguousarray(np.asarray(ok).reshape(samples) != 0, dtype=np.uint8)
+    nominal_m = np.ascontiguousarray(nominal_m, dtype=np.float64)
+    if nominal_m.shape != (n_meas,):
+        raise ValueError(f"nominal_m ({n_meas},): got {nominal_m.shape}")
+    sums, counts, _ = _effect_outputs(n_param, n_meas, bins)
+    rc = lib().ezpz_mc_effects(_ptr(params), _ptr(m), _ptr(flags), _ptr(ok), _ptr(nominal_m), _ptr(edges), samples, n_param, n_meas, bins, int(chunk),
+                               _ptr(sums), _ptr(counts))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return sums, counts
+
+
+def mc_effect_indices(sums, counts, nominal_m, edges=None, bounds=None) -> McEffects:
+    """`ezpz_mc_effect_indices`: the closing step on sums [n_param, bins, n_meas, 2], counts [n_param, bins, n_meas] and nominal_m
+    [n_meas].  Host only.  edges [n_param, bins - 1] and bounds [n_param, 2] only travel into the result, for `curve`."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    nominal_m = np.ascontiguousarray(nominal_m, dtype=np.float64)
+    if sums.ndim != 4 or sums.shape[3] != 2 or counts.shape != sums.shape[:3] or nominal_m.shape != (sums.shape[2],):
+        raise ValueError(f"sums [n_param, bins, n_meas, 2], counts [n_param, bins, n_meas] and nominal_m [n_meas]: got {sums.shape}, "
+                         f"{counts.shape} and {nominal_m.shape}")
+    n_param, bins, n_meas = counts.shape
+    _, _, out = _effect_outputs(n_param, n_meas, bins)
+    rc = lib().ezpz_mc_effect_indices(_ptr(sums), _ptr(counts), _ptr(nominal_m), n_param, n_meas, bins, *(_ptr(a) for a in out))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return McEffects(sums, counts, nominal_m, None if edges is None else np.asarray(edges, dtype=np.float64), *out, bounds=bounds)
 
 
 class SobolIndices:

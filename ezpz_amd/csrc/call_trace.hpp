@@ -57,6 +57,9 @@ enum CallStage : uint32_t {
     // ezpz_mc_quantiles_device (mc_quantiles.hip)
     QUANTILES_WORKSPACE_GROWN = 110,  // a workspace that had to grow: waited for the last call's launches, allocated
     QUANTILES_LAUNCHED = 111,         // every digit pass of the selection enqueued
+    // ezpz_mc_effects_device (mc_effects.hip)
+    EFFECTS_WORKSPACE_GROWN = 120,  // a workspace that had to grow: waited for the last call's launches, allocated
+    EFFECTS_LAUNCHED = 121,         // every round of the reduction enqueued
 };
 
 struct CallTrace {

@@ -9,11 +9,15 @@
 //   run()        one sub-round a round and the reduction behind it; with contributors (ezpz_system_tolerance_mc_contrib[_device];
 //                DESIGN.md 3n) one more enqueue per round behind the reduction -- mc_moments.hip's, on the round's params, m, flags
 //                and ok -- and the closing kernel behind the last round; with quantiles (ezpz_system_tolerance_mc_quantiles[_device];
-//                DESIGN.md 3p) every round's m, flags and ok kept on the device, mc_quantiles.hip's selection behind the last round
+//                DESIGN.md 3p) every round's m, flags and ok kept on the device, mc_quantiles.hip's selection behind the last round;
+//                with effects (ezpz_system_tolerance_mc_effects[_device]) one more enqueue per round behind the
+//                reduction -- mc_effects.hip's, on the same four arrays and the run's edges -- and its closing kernel behind the last
+//                round
 //   run_sobol()  (ezpz_system_tolerance_sobol[_device]) k' + 2 sub-rounds a round into the round's rows, the reduction
 //                behind A's, mc_sobol.hip's sums behind the last one and its closing kernel behind the last round
 // A host form is its run between the upload of x0 and the copies back of its Staged outputs.
 #include "driven_params.hpp"
+#include "mc_effects.hip.hpp"
 #include "mc_moments.hip.hpp"
 #include "mc_quantiles.hip.hpp"
 #include "mc_sobol.hip.hpp"
@@ -61,6 +65,10 @@ struct McPlan {
     DevBuf<double> all_m;
     DevBuf<uint8_t> all_flags, all_ok;
     mcq::SelectWork select_work;
+    // the run with effects: the cells' workspace, and the edges [k][bins - 1] with what the buffer holds
+    mce::EffectWork effect_work;
+    DevBuf<double> effect_edges;
+    std::vector<double> effect_edges_kept;
 };
 
 McPlan& plan_of(EzpzSystem* sys) {
@@ -210,6 +218,30 @@ int check_contrib(size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcC
     return EZPZ_OK;
 }
 
+// The outputs of a run with effects (device pointers in run(); edges: host memory) and its checked bins; sums == NULL: the plain run.
+struct Effects {
+    const double* edges = nullptr;
+    double* sums = nullptr;
+    uint64_t* counts = nullptr;
+    double *cond_mean = nullptr, *cond_var = nullptr, *eta2 = nullptr, *first = nullptr;
+    uint32_t* bins_used = nullptr;
+    uint32_t bins = 0;
+};
+
+// The argument errors the effects add to a run's; the outputs are only compared with NULL, the edges are read.
+int check_effects(size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcEffectConfig* ec, Effects& e) {
+    EzpzMcEffectConfig conf;
+    mce::default_config(&conf);
+    if (ec) conf = *ec;
+    if (int rc = mce::check_shape(n_param, n_meas, conf.bins)) return rc;
+    if (samples && (!e.edges || !e.sums || !e.counts || !e.cond_mean || !e.cond_var || !e.eta2 || !e.first || !e.bins_used))
+        return EZPZ_ERR_INVALID_ARGUMENT;
+    if (e.edges)
+        if (int rc = mce::check_edges(e.edges, n_param, conf.bins)) return rc;
+    e.bins = conf.bins;
+    return EZPZ_OK;
+}
+
 // The quantiles of a run (probs: host memory; out: a device pointer in run()) and the checked z; n_q == 0: the plain run.
 struct Quant {
     const double* probs = nullptr;
@@ -274,6 +306,7 @@ struct Needs {
     bool contrib;  // the moments' workspace
     size_t n_q;    // != 0: the selection's workspace, and of every sample's m, flags and ok the stores the plan has to hold itself
     bool own_m, own_flags, own_ok;  // (false: a caller's device keep-buffer stands in)
+    uint32_t effect_bins = 0;       // != 0: the cells' workspace
 
     // Every buffer with the count it has to hold.  grow == false: does any of them have to grow (1) or none (0); grow == true:
     // grow them (EZPZ_OK or the error).  A buffer cannot be in one answer and missing from the other.
@@ -303,6 +336,7 @@ struct Needs {
             if (own_ok) buf(P.all_ok, samples);
             work(P.select_work, m, (uint32_t)n_q);
         }
+        if (effect_bins) work(P.effect_work, blocks, k * effect_bins * m);
         return rc;
     }
 };
@@ -422,9 +456,26 @@ int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t w
     return EZPZ_OK;
 }
 
-// The plain run, with contributors or with quantiles.  Device pointers throughout (but Keep's, see there): the plan's mutex is
+// The edges of a run with effects where its kernels read them: others than the buffer holds wait for the last run's launches first.
+int upload_effect_edges(McPlan& P, const Call& c, const Effects& eff) {
+    const size_t count = c.n_param * (eff.bins - 1);
+    if (P.effect_edges.p && P.effect_edges_kept.size() == count && std::equal(eff.edges, eff.edges + count, P.effect_edges_kept.begin(),
+                                                                               [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }))
+        return EZPZ_OK;
+    release_thread_kernel(c.sys->device);
+    int rc;
+    if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
+    P.effect_edges_kept.clear();
+    if ((rc = P.effect_edges.ensure(count)) != EZPZ_OK) return rc;
+    HIP_TRY(hipMemcpy(P.effect_edges.p, eff.edges, count * sizeof(double), hipMemcpyHostToDevice));
+    P.effect_edges_kept.assign(eff.edges, eff.edges + count);
+    call_stamp(MC_TABLES_UPLOADED);
+    return EZPZ_OK;
+}
+
+// The plain run, with contributors, with quantiles or with effects.  Device pointers throughout (but Keep's, see there): the plan's mutex is
 // held, the system's device current, the request checked and samples > 0.
-int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Contrib& contrib, const Quant& quant) {
+int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Contrib& contrib, const Quant& quant, const Effects& eff) {
     const size_t n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords;
     const uint64_t samples = c.samples, chunk = r.chunk;
     const hipStream_t stream = c.stream;
@@ -434,7 +485,9 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
     double* all_m = !keep.host && keep.m ? keep.m : nullptr;
     uint8_t* all_flags = !keep.host && keep.flags ? keep.flags : nullptr;
     uint8_t* all_ok = !keep.host && keep.ok ? keep.ok : nullptr;
-    const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, 1, contrib.moments != nullptr, quant.n_q, !all_m, !all_flags, !all_ok};
+    const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, 1, contrib.moments != nullptr, quant.n_q, !all_m, !all_flags, !all_ok,
+                     eff.sums ? eff.bins : 0u};
+    if (eff.sums && (rc = upload_effect_edges(P, c, eff)) != EZPZ_OK) return rc;
     if ((rc = prepare(P, r, c, need)) != EZPZ_OK) return rc;
     if (r.hist_bins && n_meas) HIP_TRY(hipMemsetAsync(c.hist, 0, n_meas * (r.hist_bins + 2) * sizeof(uint64_t), stream));
     mc::ReduceArgs a = reduce_args(P, need, P.m.p, P.flags.p, P.ok.p, r.limits, r.hist_bins, c.stats, c.totals, c.hist);
@@ -450,6 +503,16 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
     mo.n_meas = (uint32_t)n_meas;
     mo.moments = contrib.moments;
     mo.info = contrib.info;
+    mce::EffectArgs ef{};
+    ef.params = P.params.p;
+    ef.m = P.m.p;
+    ef.flags = P.flags.p;
+    ef.ok = P.ok.p;
+    ef.nominal_m = P.nominal.p;
+    ef.edges = P.effect_edges.p;
+    ef.k = (uint32_t)n_param, ef.n_meas = (uint32_t)n_meas, ef.bins = eff.bins;
+    ef.sums = eff.sums;
+    ef.counts = eff.counts;
     for (uint64_t first = 0; first < samples; first += chunk) {
         const uint64_t count = std::min<uint64_t>(chunk, samples - first);
         if ((rc = sub_round(P, r, c, nullptr, first, count, P.m.p, P.flags.p)) != EZPZ_OK || (rc = enqueue_reduce(a, first, count, stream)) != EZPZ_OK)
@@ -459,6 +522,11 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
             mo.count = count;
             mo.first_round = first == 0;
             if ((rc = mcm::enqueue_moments(P.moment_work, mo, stream)) != EZPZ_OK) return rc;
+        }
+        if (eff.sums) {
+            ef.count = count;
+            ef.first_round = first == 0;
+            if ((rc = mce::enqueue_effects(P.effect_work, ef, stream)) != EZPZ_OK) return rc;
         }
         if (select) {  // (a caller's device buffer is filled by the copies below)
             if ((rc = copy_out(all_m ? nullptr : P.all_m.p + first * n_meas, P.m.p, count * n_meas * sizeof(double), false, stream)) != EZPZ_OK ||
@@ -484,6 +552,15 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
         ca.pivot_rel = contrib.pivot_rel;
         ca.cov = contrib.cov, ca.beta = contrib.beta, ca.contrib = contrib.contrib, ca.r2 = contrib.r2, ca.dropped = contrib.dropped;
         if ((rc = mcm::enqueue_contributors(ca, stream)) != EZPZ_OK) return rc;
+    }
+    if (eff.sums) {
+        mce::CloseArgs cl{};
+        cl.sums = eff.sums;
+        cl.counts = eff.counts;
+        cl.nominal_m = P.nominal.p;
+        cl.k = (uint32_t)n_param, cl.m = (uint32_t)n_meas, cl.bins = eff.bins;
+        cl.cond_mean = eff.cond_mean, cl.cond_var = eff.cond_var, cl.eta2 = eff.eta2, cl.first = eff.first, cl.bins_used = eff.bins_used;
+        if ((rc = mce::enqueue_close(cl, stream)) != EZPZ_OK) return rc;
     }
     if (select && (rc = mcq::enqueue_select(P.select_work, all_m ? all_m : P.all_m.p, all_flags ? all_flags : P.all_flags.p,
                                             all_ok ? all_ok : P.all_ok.p, samples, (uint32_t)n_meas, quant.probs, (uint32_t)quant.n_q, quant.z,
@@ -603,8 +680,11 @@ int host_form(McPlan& P, const Call& c, Staged& out, Run&& run_on) {
     return out.copy_back(P.host_out);
 }
 
-// ---- the entries: plain, with contributors, with quantiles ----------------------------------------------------------------------
-int check_kinds(const Call& c, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant) {
+// ---- the entries: plain, with contributors, with quantiles, with effects ----------------------------------------------------------
+int check_kinds(const Call& c, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant,
+                const EzpzMcEffectConfig* ec = nullptr, Effects* effects = nullptr) {
+    if (effects)
+        if (int rc = check_effects(c.n_param, c.n_meas, c.samples, ec, *effects)) return rc;
     if (contrib)
         if (int rc = check_contrib(c.n_param, c.n_meas, c.samples, cc, *contrib)) return rc;
     if (quant)
@@ -612,14 +692,17 @@ int check_kinds(const Call& c, const EzpzMcContribConfig* cc, Contrib* contrib, 
     return EZPZ_OK;
 }
 
-int run_device(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant) {
-    return enter(c, [&](Request&) { return check_kinds(c, cc, contrib, qc, quant); },
-                 [&](McPlan& P, Request& r) { return run(P, r, c, keep, contrib ? *contrib : Contrib{}, quant ? *quant : Quant{}); });
+int run_device(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant,
+               const EzpzMcEffectConfig* ec = nullptr, Effects* effects = nullptr) {
+    return enter(c, [&](Request&) { return check_kinds(c, cc, contrib, qc, quant, ec, effects); }, [&](McPlan& P, Request& r) {
+        return run(P, r, c, keep, contrib ? *contrib : Contrib{}, quant ? *quant : Quant{}, effects ? *effects : Effects{});
+    });
 }
 
-// `contrib` and `quant` hold host pointers here.
-int run_host(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant) {
-    return enter(c, [&](Request&) { return check_kinds(c, cc, contrib, qc, quant); }, [&](McPlan& P, Request& r) {
+// `contrib`, `quant` and `effects` hold host pointers here.
+int run_host(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant,
+             const EzpzMcEffectConfig* ec = nullptr, Effects* effects = nullptr) {
+    return enter(c, [&](Request&) { return check_kinds(c, cc, contrib, qc, quant, ec, effects); }, [&](McPlan& P, Request& r) {
         const size_t n_param = c.n_param, n_meas = c.n_meas, K = n_param + n_meas, km = n_param * n_meas;
         Staged out;
         uint64_t* hist_dev = nullptr;
@@ -640,9 +723,21 @@ int run_host(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Con
             qdev = *quant;
             out.add(quant->out, n_meas * quant->n_q, qdev.out);
         }
+        Effects edev;
+        if (effects) {
+            edev = *effects;  // (the edges stay the caller's host array; bins as checked)
+            const size_t cells = n_param * effects->bins * n_meas;
+            out.add(effects->sums, 2 * cells, edev.sums);
+            out.add(effects->counts, cells, edev.counts);
+            out.add(effects->cond_mean, cells, edev.cond_mean);
+            out.add(effects->cond_var, cells, edev.cond_var);
+            out.add(effects->eta2, km, edev.eta2);
+            out.add(effects->first, km, edev.first);
+            out.add(effects->bins_used, km, edev.bins_used);
+        }
         return host_form(P, c, out, [&](Call& d) {
             d.hist = hist_dev;
-            return run(P, r, d, keep, dev, qdev);
+            return run(P, r, d, keep, dev, qdev, edev);
         });
     });
 }
@@ -738,6 +833,38 @@ int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const ui
     Contrib o;
     o.moments = moments, o.info = info, o.cov = cov, o.beta = beta, o.contrib = contrib, o.r2 = r2, o.dropped = dropped;
     return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, cc, &o, nullptr, nullptr);
+}
+
+int ezpz_system_tolerance_mc_effects_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                            const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                            const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                            uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                            EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                            uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, const EzpzMcEffectConfig* ec,
+                                            const double* edges, double* sums_dev, uint64_t* counts_dev, double* cond_mean_dev,
+                                            double* cond_var_dev, double* eta2_dev, double* first_dev, uint32_t* bins_used_dev,
+                                            void* stream) {
+    const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                 stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
+    Effects o;
+    o.edges = edges, o.sums = sums_dev, o.counts = counts_dev, o.cond_mean = cond_mean_dev, o.cond_var = cond_var_dev;
+    o.eta2 = eta2_dev, o.first = first_dev, o.bins_used = bins_used_dev;
+    return run_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr, nullptr, nullptr, ec, &o);
+}
+
+int ezpz_system_tolerance_mc_effects(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                     const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                     const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                     const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals,
+                                     uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok,
+                                     const EzpzMcEffectConfig* ec, const double* edges, double* sums, uint64_t* counts,
+                                     double* cond_mean, double* cond_var, double* eta2, double* first, uint32_t* bins_used) {
+    const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                 stats, totals, hist, hipStreamPerThread};
+    Effects o;
+    o.edges = edges, o.sums = sums, o.counts = counts, o.cond_mean = cond_mean, o.cond_var = cond_var;
+    o.eta2 = eta2, o.first = first, o.bins_used = bins_used;
+    return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, nullptr, nullptr, ec, &o);
 }
 
 int ezpz_system_tolerance_mc_quantiles_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,

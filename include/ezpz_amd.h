@@ -1028,6 +1028,96 @@ int ezpz_system_tolerance_mc_quantiles_device(EzpzSystem* sys, const double* x0_
                                               uint8_t* keep_ok_dev, const double* probs, size_t n_q, const EzpzMcQuantileConfig* qc,
                                               EzpzMcQuantile* out_dev, void* stream);
 
+/* ---- Monte-Carlo main effects: the conditional mean of a reference dimension per driving dimension, and first-order indices at the
+ * price of the plain run (a project extension).  The contributors fit one slope to the curve "mean of reference dimension
+ * i as a function of driving dimension j across its tolerance zone", the Sobol first-order index compresses it to one number; this
+ * section returns the curve, binned, and from it the correlation ratio: the variance of the bin means over the total variance, which
+ * estimates the same first-order index from the samples of the plain run alone -- no extra solves.
+ * SHAPES.  k = n_param, m = n_meas, B = bins: 1 <= k, m <= 32; 2 <= B <= EZPZ_MC_EFFECT_MAX_BINS; k * B * m <= EZPZ_MC_EFFECT_MAX_CELLS.
+ * THE BIN.  edges [k][B - 1], absolute values, non-decreasing per dimension; +-inf may stand (+inf edges leave the upper bins empty),
+ * NaN is refused where the library reads the edges (host memory: every entry but ezpz_mc_effects_device).  bin(b, j) = the number
+ * of edges of dimension j that are <= p[b][j]: comparisons alone, a function of the drawn value alone; a value on an edge goes to
+ * the upper bin; a NaN p (possible only in ezpz_mc_effects[_device]) lands in bin 0, and so does everything under NaN edges.
+ * THE CELLS.  For every (j, c, i) -- dimension, bin, record -- n (uint64), sum_d and sum_d2 over the samples that are VALID FOR
+ * record i by the Monte-Carlo section's rule (ok -- ezpz_mc_effects: ok[b] != 0, ok == NULL: every one -- flag bit 0 of (b, i)
+ * clear, flags == NULL: every one, and m[b][i] finite) and have bin(b, j) == c, with d = m[b][i] - nominal_m[i], one rounded
+ * subtraction, and d * d rounded, then added.  THE ORDER OF EVERY SUM is the Monte-Carlo section's: block q is the samples [256 q,
+ * 256 q + 256); a leaf is +0.0 for a sample that does not count for the cell or lies past `samples`; inside a block the 256 leaves
+ * are summed by the adjacent-pair tree (for h = 1, 2, .. 128: v[t] += v[t + h] for every t that is a multiple of 2 h); the blocks'
+ * sums are added left to right from +0.0.  No floating-point atomics, no product contracted into a fused multiply-add: the same bits
+ * for any chunk, any stream and any device, and on the host.  A cell is therefore the sum_d / sum_d2 / n_valid of EzpzMcStats for the
+ * run restricted to one bin of one dimension, and for every j the sum over c of n[j][c][i] equals stats[i].n_valid exactly.
+ * Layout: sums [k][B][m][2] doubles (sum_d, sum_d2) and counts [k][B][m] uint64.
+ * THE CLOSING STEP, ezpz_mc_effect_indices (host only, no device; the run's kernel has the same body and gives the same bits): a
+ * pure function of sums, counts and nominal_m, from + - * /, comparisons and integer-to-double conversions alone, each line
+ * evaluated as written, left to right; every loop ascends c and skips the empty cells (n_c == 0).  s_c, q_c, n_c: a cell's sum_d,
+ * sum_d2 and n.
+ *   cond_mean [k][B][m]:  nominal_m[i] + s_c / n_c;  NaN for an empty cell
+ *   cond_var  [k][B][m]:  (q_c - s_c * s_c / n_c) / (n_c - 1), n_c - 1 formed as an integer;  NaN for n_c < 2
+ *   per (i, j):  N = sum of n_c (an integer);  S = sum of s_c and Q = sum of q_c, each from +0.0;  used = the number of non-empty cells
+ *   bins_used [m][k] (uint32) = used.   used < 2 (a FIXED dimension, all +inf edges, no valid sample): eta2 = first = +0.0.  Else:
+ *   dbar = S / N;   SST = Q - S * S / N;   SSB = SSW = +0.0, then per non-empty cell:
+ *     mu = s_c / n_c;   t = mu - dbar;   SSB = SSB + n_c * (t * t);   w_c = q_c - s_c * s_c / n_c;   SSW = SSW + w_c
+ *   SST not > 0 (a constant record; NaN), or N - used < 1:  eta2 = first = NaN.  Else:
+ *   eta2  [m][k] = SSB / SST
+ *   first [m][k] = (SSB - (used - 1) * (SSW / (N - used))) / SST        N - used and used - 1 formed as integers
+ * WHAT THE NUMBERS MEAN.  eta2 is the correlation ratio: the share of record i's sample variance that lies between the bin means of
+ * dimension j.  It estimates the first-order Sobol index Var(E[m_i | p_j]) / Var(m_i) with two biases.  THE BINS' BIAS, downward: a
+ * bin mean averages the curve over the bin, so the variance inside the bins is lost -- for a linear effect on B equal-width bins of
+ * a uniform dimension 1 / B^2 of the index, more where the curve bends inside a bin; more bins lose less.  THE SAMPLING BIAS, upward:
+ * the bin means of a dimension with no effect still scatter, by (used - 1) / (N - used) of the within-bin variance -- about
+ * (B - 1) / N of the total; `first` subtracts exactly that (the adjusted ratio, (used - 1) mean squares within taken off SSB) and
+ * is unbiased for a dimension with no effect.  It is not clamped and can be slightly negative.  More bins trade the first bias for
+ * noise in the second's correction; 8 to 16 bins at a few thousand samples are a reasonable start.
+ * ezpz_mc_effects[_device]: the reduction alone on any kept rows -- params [samples][n_param], m [samples][n_meas], flags (bytes,
+ * the same shape, may be NULL), ok [samples] bytes (may be NULL), nominal_m [m], edges [k][B - 1] -- no system involved.  The host
+ * form computes on the host, with no device, and gives the device form's bits; it has no rounds and ignores `chunk`.  The _device
+ * form takes device pointers for every array, edges included (which it therefore cannot check: the bin rule holds whatever they
+ * are), and only enqueues on `stream`, in rounds of `chunk` samples (rounded up to a multiple of 256; 0: 65536) on a workspace the
+ * library owns per device (a workspace that has to grow is first allocated behind the last call's launches); calls on one device go
+ * one behind the other whatever their streams.
+ * ezpz_system_tolerance_mc_effects[_device]: ezpz_system_tolerance_mc[_device] -- the same arguments, the same run, stats, totals,
+ * hist and keep_* byte for byte -- with one more kernel per round, behind the round's reduction, that folds the round's params, m,
+ * flags and ok into sums and counts, and one closing kernel behind the last round that fills cond_mean, cond_var, eta2, first and
+ * bins_used from them, with nominal_m the statistics' nominal[i].  ec (EzpzMcEffectConfig: bins; NULL: ezpz_default_mc_effect_config's
+ * 8) and edges are host pointers in both forms; edges other than the last run's are first uploaded behind the last run's launches.
+ * The _device form takes device pointers for the seven outputs too.  Not combined with contributors or quantiles in one call.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: a shape outside the limits above (k == 0 and m == 0
+ * included); an edge that is NaN or below its predecessor (host edges); with samples > 0: an output NULL, or an input NULL (flags and
+ * ok may be) -- ezpz_mc_effect_indices: whatever samples --; for the run every argument error of ezpz_system_tolerance_mc.
+ * samples == 0: EZPZ_OK after those checks, nothing written. */
+#define EZPZ_MC_EFFECT_MAX_BINS 64u
+#define EZPZ_MC_EFFECT_MAX_CELLS 4096u
+typedef struct EzpzMcEffectConfig { /* 8 bytes */
+    uint32_t bins; /* 2 .. 64; default 8 */
+    uint32_t reserved;
+} EzpzMcEffectConfig;
+void ezpz_default_mc_effect_config(EzpzMcEffectConfig* ec);
+int ezpz_mc_effect_indices(const double* sums, const uint64_t* counts, const double* nominal_m, size_t n_param, size_t n_meas,
+                           uint32_t bins, double* cond_mean, double* cond_var, double* eta2, double* first, uint32_t* bins_used);
+int ezpz_mc_effects(const double* params, const double* m, const uint8_t* flags, const uint8_t* ok, const double* nominal_m,
+                    const double* edges, uint64_t samples, size_t n_param, size_t n_meas, uint32_t bins, uint32_t chunk, double* sums,
+                    uint64_t* counts);
+int ezpz_mc_effects_device(const double* params_dev, const double* m_dev, const uint8_t* flags_dev, const uint8_t* ok_dev,
+                           const double* nominal_m_dev, const double* edges_dev, uint64_t samples, size_t n_param, size_t n_meas,
+                           uint32_t bins, uint32_t chunk, double* sums_dev, uint64_t* counts_dev, void* stream);
+int ezpz_system_tolerance_mc_effects(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                     const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                     const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                     const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals,
+                                     uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok,
+                                     const EzpzMcEffectConfig* ec, const double* edges, double* sums, uint64_t* counts,
+                                     double* cond_mean, double* cond_var, double* eta2, double* first, uint32_t* bins_used);
+int ezpz_system_tolerance_mc_effects_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                            const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                            const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                            uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                            EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                            uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, const EzpzMcEffectConfig* ec,
+                                            const double* edges, double* sums_dev, uint64_t* counts_dev, double* cond_mean_dev,
+                                            double* cond_var_dev, double* eta2_dev, double* first_dev, uint32_t* bins_used_dev,
+                                            void* stream);
+
 /* ---- Dimension targets: solve driving dimensions for measured targets (a project extension) -- the inverse of the
  * entries above: which values of the driving dimensions (the constraints at `positions`, as ezpz_system_solve_batch_params takes
  * them) put the reference dimensions `records` (measurement records, as ezpz_system_measure takes them; host memory in both forms)
