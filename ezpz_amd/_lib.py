@@ -121,6 +121,11 @@ class CMcEffectConfig(C.Structure):
 MC_EFFECT_MAX_DIM, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS = 32, 64, 4096  # the section's limits; EZPZ_MC_EFFECT_MAX_*
 assert C.sizeof(CMcEffectConfig) == 8
 
+MC_FACTORIAL_MAX_CORNERS, MC_FACTORIAL_MAX_MEAS = 20, 32  # EZPZ_MC_FACTORIAL_MAX_*
+MC_FACTORIAL_DTYPE = np.dtype([("n_valid", "<u8"), ("complete", "<u4"), ("corner_hi", "<u4"), ("corner_lo", "<u4"), ("reserved", "<u4"),
+                               ("mean_dev", "<f8"), ("var", "<f8"), ("m_hi", "<f8"), ("m_lo", "<f8")])  # EzpzMcFactorial
+assert MC_FACTORIAL_DTYPE.itemsize == 56
+
 
 class CBranchConfig(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("chunk", C.c_uint32), ("max_branches", C.c_uint32), ("eps_abs", C.c_double), ("eps_rel", C.c_double)]
@@ -204,6 +209,7 @@ EXPORTS = [
     "ezpz_system_tolerance_mc_quantiles_device",
     "ezpz_default_mc_effect_config", "ezpz_mc_effect_indices", "ezpz_mc_effects", "ezpz_mc_effects_device",
     "ezpz_system_tolerance_mc_effects", "ezpz_system_tolerance_mc_effects_device",
+    "ezpz_mc_factorial", "ezpz_mc_factorial_device", "ezpz_system_tolerance_mc_factorial", "ezpz_system_tolerance_mc_factorial_device",
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
     "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
     "ezpz_system_solve_branches_device",
@@ -319,6 +325,14 @@ def lib():
     L.ezpz_system_tolerance_mc_effects.argtypes = L.ezpz_system_tolerance_mc.argtypes + [C.POINTER(CMcEffectConfig)] + [vp] * 8
     L.ezpz_system_tolerance_mc_effects_device.restype = C.c_int
     L.ezpz_system_tolerance_mc_effects_device.argtypes = L.ezpz_system_tolerance_mc_effects.argtypes + [vp]
+    L.ezpz_mc_factorial.restype = C.c_int
+    L.ezpz_mc_factorial.argtypes = [vp, vp, vp, vp, u32, sz] + [vp] * 8
+    L.ezpz_mc_factorial_device.restype = C.c_int
+    L.ezpz_mc_factorial_device.argtypes = L.ezpz_mc_factorial.argtypes + [vp]
+    L.ezpz_system_tolerance_mc_factorial.restype = C.c_int
+    L.ezpz_system_tolerance_mc_factorial.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp] * 8
+    L.ezpz_system_tolerance_mc_factorial_device.restype = C.c_int
+    L.ezpz_system_tolerance_mc_factorial_device.argtypes = L.ezpz_system_tolerance_mc_factorial.argtypes + [vp]
     L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
     L.ezpz_seek_step.restype = C.c_int
     L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, MC_FACTORIAL_DTYPE, MC_FACTORIAL_MAX_CORNERS, MC_FACTORIAL_MAX_MEAS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1225,7 +1225,7 @@ class System:
     def tolerance_mc(self, x0, positions, dists, records, samples: int, seed: int = 0, nominal=None, limits=None, hist=None,
                      chunk: int = 0, keep: bool = False, config: Optional[Config] = None, contributors: bool = False,
                      pivot_rel: Optional[float] = None, quantiles=None, quantile_z: float = 0.0,
-                     effects: Optional["EffectsConfig"] = None) -> "McResult":
+                     effects: Optional["EffectsConfig"] = None, factorial: bool = False, keep_coef: bool = False) -> "McResult":
         """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
         solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
         statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
@@ -1240,11 +1240,17 @@ class System:
         quantile_z: the band's half width in standard errors of the rank.  Not together with contributors.
         effects: an `EffectsConfig` -- the same run through `ezpz_system_tolerance_mc_effects`: every reference dimension's sums and
         counts per bin of every driving dimension, reduced on the device, and from them the main-effect curves and the first-order
-        indices; the result also has `effects` (an `McEffects`, with the edges used).  Not together with contributors or quantiles."""
+        indices; the result also has `effects` (an `McEffects`, with the edges used).  Not together with contributors or quantiles.
+        factorial: the same run through `ezpz_system_tolerance_mc_factorial` -- every dimension CORNER or FIXED and samples ==
+        `mc_corner_count(dists)`: the corner run as a full two-level factorial design, every main effect and interaction by one
+        Walsh-Hadamard transform on the device; the result also has `factorial` (an `McFactorial`); keep_coef: with all 2^kc
+        coefficients per record.  Not together with contributors, quantiles or effects."""
         if quantiles is not None and contributors:
             raise ValueError("quantiles together with contributors: run them one after the other")
         if effects is not None and (contributors or quantiles is not None):
             raise ValueError("effects together with contributors or quantiles: run them one after the other")
+        if factorial and (contributors or quantiles is not None or effects is not None):
+            raise ValueError("factorial together with contributors, quantiles or effects: run them one after the other")
         x0 = self._mc_x0(x0)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
@@ -1273,6 +1279,13 @@ class System:
                 raise NonLinearSystemError(rc)
             return McResult(stats, totals, counts, kept if keep else None,
                             effects=McEffects(sums, cnt, stats["nominal"].copy(), edges, *out, bounds=bounds))
+        if factorial:
+            dims = _corner_dims(d)
+            out = _factorial_outputs(len(dims), k, keep_coef)
+            rc = lib().ezpz_system_tolerance_mc_factorial(*args, *(_ptr(a) for a in out))
+            if rc != 0:
+                raise NonLinearSystemError(rc)
+            return McResult(stats, totals, counts, kept if keep else None, factorial=McFactorial(*out, dims=dims, stats=stats))
         if not contributors:
             rc = lib().ezpz_system_tolerance_mc(*args)
             if rc != 0:
@@ -1293,7 +1306,10 @@ class System:
                             contrib_ptr: int = 0, r2_ptr: int = 0, dropped_ptr: int = 0, pivot_rel: Optional[float] = None,
                             quantiles=None, quantile_z: float = 0.0, quantiles_ptr: int = 0, effects: Optional["EffectsConfig"] = None,
                             effect_sums_ptr: int = 0, effect_counts_ptr: int = 0, cond_mean_ptr: int = 0, cond_var_ptr: int = 0,
-                            eta2_ptr: int = 0, first_ptr: int = 0, bins_used_ptr: int = 0):
+                            eta2_ptr: int = 0, first_ptr: int = 0, bins_used_ptr: int = 0, factorial: bool = False,
+                            factorial_info_ptr: int = 0, factorial_main_ptr: int = 0, factorial_pair_ptr: int = 0,
+                            factorial_ss_order_ptr: int = 0, factorial_ss_total_ptr: int = 0, factorial_first_ptr: int = 0,
+                            factorial_total_ptr: int = 0, factorial_coef_ptr: int = 0):
         """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], hist: uint64
         [n_meas, bins + 2]) and a hipStream_t handle; positions, dists, records, nominal, limits and hist = (lo, hi, bins) stay host
         values.  Enqueues only once the run's tables are the last run's.  With moments_ptr the run goes through
@@ -1304,11 +1320,16 @@ class System:
         `EffectsConfig`, host values) the run goes through `ezpz_system_tolerance_mc_effects_device` and fills effect_sums_ptr [n_param,
         bins, n_meas, 2], effect_counts_ptr (uint64 [n_param, bins, n_meas]), cond_mean_ptr and cond_var_ptr [n_param, bins, n_meas],
         eta2_ptr and first_ptr [n_meas, n_param] and bins_used_ptr (uint32 [n_meas, n_param]); the edges used [n_param, bins - 1] are
-        returned (None without effects)."""
+        returned (None without effects).  With factorial the run goes through `ezpz_system_tolerance_mc_factorial_device` and fills
+        factorial_info_ptr (MC_FACTORIAL_DTYPE [n_meas]), factorial_main_ptr, factorial_ss_total_ptr, factorial_first_ptr and
+        factorial_total_ptr [n_meas, kc], factorial_pair_ptr [n_meas, kc, kc], factorial_ss_order_ptr [n_meas, kc + 1] and, where
+        given, factorial_coef_ptr [n_meas, 2^kc]; it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given."""
         if quantiles is not None and moments_ptr:
             raise ValueError("quantiles together with contributors: run them one after the other")
         if effects is not None and (quantiles is not None or moments_ptr):
             raise ValueError("effects together with contributors or quantiles: run them one after the other")
+        if factorial and (quantiles is not None or moments_ptr or effects is not None):
+            raise ValueError("factorial together with contributors, quantiles or effects: run them one after the other")
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
@@ -1327,6 +1348,10 @@ class System:
             if rc != 0:
                 raise NonLinearSystemError(rc)
             return edges
+        elif factorial:
+            rc = lib().ezpz_system_tolerance_mc_factorial_device(*args, *(p or None for p in (
+                factorial_info_ptr, factorial_main_ptr, factorial_pair_ptr, factorial_ss_order_ptr, factorial_ss_total_ptr,
+                factorial_first_ptr, factorial_total_ptr, factorial_coef_ptr)), stream or None)
         elif moments_ptr:
             cc = _contrib_config(pivot_rel)
             rc = lib().ezpz_system_tolerance_mc_contrib_device(*args, C.byref(cc), moments_ptr, info_ptr or None, cov_ptr or None, beta_ptr or None,
@@ -1600,12 +1625,15 @@ class McResult:
     n_ok and n_all_in, and with keep the samples: params, m, flags, ok.  `stats` and `totals` are the library's records.  A run with
     contributors also has moments, n_complete, cov, beta, contrib, r2, dropped (those of its `contributors`, a `McContributors`) and
     `corr`.  A run with quantiles also has `quantiles` (MC_QUANTILE_DTYPE [n_meas, n_q]) and its fields as q_value, q_lo, q_hi,
-    q_band_lo, q_band_hi.  A run with effects also has `effects` (an `McEffects`)."""
+    q_band_lo, q_band_hi.  A run with effects also has `effects` (an `McEffects`), a run with factorial effects `factorial` (an
+    `McFactorial`)."""
 
-    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None, effects=None):
+    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None, effects=None, factorial=None):
         self.stats, self.totals, self.hist = stats, totals, hist
         if effects is not None:
             self.effects = effects
+        if factorial is not None:
+            self.factorial = factorial
         if quantiles is not None:
             self.quantiles = quantiles
             for f in ("value", "lo", "hi", "band_lo", "band_hi"):
@@ -1720,6 +1748,82 @@ def mc_quantiles(m, flags, ok, probs, z: float = 0.0) -> np.ndarray:
     if rc != 0:
         raise NonLinearSystemError(rc)
     return out
+
+
+def _corner_dims(d) -> List[int]:
+    """The places, in the list, of the CORNER dimensions: rank c is dims[c]."""
+    return [j for j in range(len(d)) if int(d["kind"][j]) == McDist.CORNER]
+
+
+def mc_corner_count(dists) -> int:
+    """2^kc for the kc CORNER dimensions of `dists`: the `samples` of a run with factorial effects."""
+    return 1 << len(_corner_dims(mc_dists(dists)))
+
+
+def _factorial_outputs(kc: int, n_meas: int, keep_coef: bool):
+    """info, main, pair, ss_order, ss_total, first, total, coef (None unless kept), in the library's order."""
+    return (np.zeros(n_meas, dtype=MC_FACTORIAL_DTYPE), np.zeros((n_meas, kc)), np.zeros((n_meas, kc, kc)), np.zeros((n_meas, kc + 1)),
+            np.zeros((n_meas, kc)), np.zeros((n_meas, kc)), np.zeros((n_meas, kc)), np.zeros((n_meas, 1 << kc)) if keep_coef else None)
+
+
+class McFactorial:
+    """What `mc_factorial` returns and a `tolerance_mc` run with factorial effects carries, per reference dimension i: info
+    (MC_FACTORIAL_DTYPE [n_meas]) and its fields n_valid, complete, corner_hi, corner_lo, mean_dev, var, m_hi, m_lo; main [n_meas, kc],
+    pair [n_meas, kc, kc], ss_order [n_meas, kc + 1], ss_total, first and total [n_meas, kc]; coef [n_meas, 2^kc] or None.  dims [kc]:
+    the place of the CORNER dimension of rank c in the run's list.  main_effect = 2 main (the classical main effect: the mean at the b
+    end minus the mean at the a end); interaction = total - first (the share of the variance a dimension causes through interactions
+    alone).  Every floating value of a record that is not complete is NaN."""
+
+    def __init__(self, info, main, pair, ss_order, ss_total, first, total, coef=None, dims=None, stats=None):
+        self.info, self.main, self.pair, self.ss_order, self.ss_total, self.first, self.total, self.coef = info, main, pair, ss_order, ss_total, first, total, coef
+        self.kc = main.shape[1]
+        self.dims = list(range(self.kc)) if dims is None else list(dims)
+        self.stats = stats
+        for f in ("n_valid", "complete", "corner_hi", "corner_lo", "mean_dev", "var", "m_hi", "m_lo"):
+            setattr(self, f, info[f])
+        self.main_effect = 2.0 * main
+        self.interaction = total - first
+
+    def largest(self, i: int, n: int = 5):
+        """The n largest |coef| of record i among the mains and the pairs: a list of (coef, dimensions), dimensions a tuple of one or two
+        places in the run's list, largest first (ties: mains before pairs, then ascending rank)."""
+        terms = [(float(self.main[i, c]), (self.dims[c],)) for c in range(self.kc)]
+        terms += [(float(self.pair[i, c, e]), (self.dims[c], self.dims[e])) for c in range(self.kc) for e in range(c + 1, self.kc)]
+        order = sorted(range(len(terms)), key=lambda t: -abs(terms[t][0]) if terms[t][0] == terms[t][0] else math.inf)
+        return [terms[t] for t in order[:int(n)]]
+
+    def worst_case(self, i: int) -> dict:
+        """The extremes of record i over the corners against the corners the linear signs predict: max, argmax, m_hi, corner_hi and
+        hi_is_linear (argmax == corner_hi), and min, argmin, m_lo, corner_lo and lo_is_linear.  Needs the run's statistics."""
+        if self.stats is None:
+            raise ValueError("worst_case: the statistics of a run (tolerance_mc(..., factorial=True))")
+        s = self.stats
+        return dict(max=float(s["max"][i]), argmax=int(s["argmax"][i]), m_hi=float(self.m_hi[i]), corner_hi=int(self.corner_hi[i]),
+                    hi_is_linear=bool(self.complete[i]) and int(s["argmax"][i]) == int(self.corner_hi[i]),
+                    min=float(s["min"][i]), argmin=int(s["argmin"][i]), m_lo=float(self.m_lo[i]), corner_lo=int(self.corner_lo[i]),
+                    lo_is_linear=bool(self.complete[i]) and int(s["argmin"][i]) == int(self.corner_lo[i]))
+
+
+def mc_factorial(m, flags, ok, nominal_m, keep_coef: bool = False) -> McFactorial:
+    """`ezpz_mc_factorial`: the factorial effects of the kept rows m [2^kc, n_meas] of a corner run, flags (the same shape; None: clear)
+    and ok [2^kc] (None: every one set), about nominal_m [n_meas].  Computed on the host; the device form gives the same bytes."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    if m.ndim != 2 or len(m) < 2 or len(m) & (len(m) - 1):
+        raise ValueError(f"m [2^kc, n_meas] with kc >= 1: got {m.shape}")
+    N, n_meas = m.shape
+    kc = N.bit_length() - 1
+    if flags is not None:
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(m.shape)
+    if ok is not None:
+        ok = np.ascontiguousarray(np.asarray(ok).reshape(N) != 0, dtype=np.uint8)
+    nominal_m = np.ascontiguousarray(nominal_m, dtype=np.float64)
+    if nominal_m.shape != (n_meas,):
+        raise ValueError(f"nominal_m ({n_meas},): got {nominal_m.shape}")
+    out = _factorial_outputs(min(kc, MC_FACTORIAL_MAX_CORNERS), min(n_meas, MC_FACTORIAL_MAX_MEAS), keep_coef)
+    rc = lib().ezpz_mc_factorial(_ptr(m), _ptr(flags), _ptr(ok), _ptr(nominal_m), kc, n_meas, *(_ptr(a) for a in out))
+    if rc != 0:
+        raise NonLinearSystemError(rc)
+    return McFactorial(*out)
 
 
 class EffectsConfig:

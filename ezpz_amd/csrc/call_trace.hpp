@@ -60,6 +60,9 @@ enum CallStage : uint32_t {
     // ezpz_mc_effects_device (mc_effects.hip)
     EFFECTS_WORKSPACE_GROWN = 120,  // a workspace that had to grow: waited for the last call's launches, allocated
     EFFECTS_LAUNCHED = 121,         // every round of the reduction enqueued
+    // ezpz_mc_factorial_device (mc_factorial.hip)
+    FACTORIAL_WORKSPACE_GROWN = 130,  // a workspace that had to grow: waited for the last call's launches, allocated
+    FACTORIAL_LAUNCHED = 131,         // the gather, the strided levels, the walk and the close enqueued
 };
 
 struct CallTrace {

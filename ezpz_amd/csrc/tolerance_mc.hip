@@ -12,12 +12,14 @@
 //                DESIGN.md 3p) every round's m, flags and ok kept on the device, mc_quantiles.hip's selection behind the last round;
 //                with effects (ezpz_system_tolerance_mc_effects[_device]) one more enqueue per round behind the
 //                reduction -- mc_effects.hip's, on the same four arrays and the run's edges -- and its closing kernel behind the last
-//                round
+//                round; with factorial effects (ezpz_system_tolerance_mc_factorial[_device]) every round's m, flags and ok
+//                kept on the device as for the quantiles, mc_factorial.hip's transform behind the last round
 //   run_sobol()  (ezpz_system_tolerance_sobol[_device]) k' + 2 sub-rounds a round into the round's rows, the reduction
 //                behind A's, mc_sobol.hip's sums behind the last one and its closing kernel behind the last round
 // A host form is its run between the upload of x0 and the copies back of its Staged outputs.
 #include "driven_params.hpp"
 #include "mc_effects.hip.hpp"
+#include "mc_factorial.hip.hpp"
 #include "mc_moments.hip.hpp"
 #include "mc_quantiles.hip.hpp"
 #include "mc_sobol.hip.hpp"
@@ -69,6 +71,9 @@ struct McPlan {
     mce::EffectWork effect_work;
     DevBuf<double> effect_edges;
     std::vector<double> effect_edges_kept;
+    // the run with factorial effects: the rows in all_m, all_flags and all_ok as for the quantiles, and the transform's
+    // workspace -- the [n_meas][2^kc] work array and the block sums
+    mcf::FactorialWork factorial_work;
 };
 
 McPlan& plan_of(EzpzSystem* sys) {
@@ -250,6 +255,27 @@ struct Quant {
     double z = 0.0;
 };
 
+// The outputs of a run with factorial effects (device pointers in run()) and the number of CORNER dimensions; info == NULL: the plain run.
+struct Fact {
+    mcf::FactorialOut out;
+    uint32_t kc = 0;
+};
+
+// The argument errors the factorial effects add to a run's; the outputs are only compared with NULL.
+int check_factorial(const Call& c, const Request& r, Fact& f) {
+    if (c.n_meas == 0 || c.n_meas > mcf::kMaxMeas) return EZPZ_ERR_INVALID_ARGUMENT;
+    f.kc = 0;
+    for (const mc::Dist& d : r.dists) {
+        if (d.kind != EZPZ_MC_CORNER && d.kind != EZPZ_MC_FIXED) return EZPZ_ERR_INVALID_ARGUMENT;
+        if (d.kind == EZPZ_MC_CORNER) ++f.kc;
+    }
+    if (f.kc == 0 || f.kc > mcf::kMaxCorners) return EZPZ_ERR_INVALID_ARGUMENT;
+    if (c.samples && c.samples != 1ull << f.kc) return EZPZ_ERR_INVALID_ARGUMENT;
+    const mcf::FactorialOut& o = f.out;
+    if (c.samples && (!o.info || !o.main || !o.pair || !o.ss_order || !o.ss_total || !o.first || !o.total)) return EZPZ_ERR_INVALID_ARGUMENT;
+    return EZPZ_OK;
+}
+
 // The outputs of a run with Sobol indices (device pointers in run_sobol) and its checked configuration.
 struct SobolOut {
     double* sums = nullptr;
@@ -307,6 +333,7 @@ struct Needs {
     size_t n_q;    // != 0: the selection's workspace, and of every sample's m, flags and ok the stores the plan has to hold itself
     bool own_m, own_flags, own_ok;  // (false: a caller's device keep-buffer stands in)
     uint32_t effect_bins = 0;       // != 0: the cells' workspace
+    uint32_t fact_kc = 0;           // != 0: the transform's workspace, and the stores of every sample's m, flags and ok as for n_q
 
     // Every buffer with the count it has to hold.  grow == false: does any of them have to grow (1) or none (0); grow == true:
     // grow them (EZPZ_OK or the error).  A buffer cannot be in one answer and missing from the other.
@@ -330,12 +357,13 @@ struct Needs {
             work(P.sobol_work, blocks, k, m);
         }
         if (contrib) work(P.moment_work, blocks, k + m);
-        if (n_q) {
+        if (n_q || fact_kc) {
             if (own_m) buf(P.all_m, samples * n_meas);
             if (own_flags) buf(P.all_flags, samples * n_meas);
             if (own_ok) buf(P.all_ok, samples);
-            work(P.select_work, m, (uint32_t)n_q);
         }
+        if (n_q) work(P.select_work, m, (uint32_t)n_q);
+        if (fact_kc) work(P.factorial_work, m, fact_kc);
         if (effect_bins) work(P.effect_work, blocks, k * effect_bins * m);
         return rc;
     }
@@ -473,20 +501,21 @@ int upload_effect_edges(McPlan& P, const Call& c, const Effects& eff) {
     return EZPZ_OK;
 }
 
-// The plain run, with contributors, with quantiles or with effects.  Device pointers throughout (but Keep's, see there): the plan's mutex is
+// The plain run, with contributors, with quantiles, with effects or with factorial effects.  Device pointers throughout (but Keep's, see there): the plan's mutex is
 // held, the system's device current, the request checked and samples > 0.
-int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Contrib& contrib, const Quant& quant, const Effects& eff) {
+int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Contrib& contrib, const Quant& quant, const Effects& eff,
+        const Fact& fact = Fact{}) {
     const size_t n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords;
     const uint64_t samples = c.samples, chunk = r.chunk;
     const hipStream_t stream = c.stream;
     int rc;
-    // the rows the selection reads: the caller's device buffers where given, else the plan's
-    const bool select = quant.n_q != 0;
+    // the rows the selection or the transform reads: the caller's device buffers where given, else the plan's
+    const bool select = quant.n_q != 0, transform = fact.out.info != nullptr, rows_kept = select || transform;
     double* all_m = !keep.host && keep.m ? keep.m : nullptr;
     uint8_t* all_flags = !keep.host && keep.flags ? keep.flags : nullptr;
     uint8_t* all_ok = !keep.host && keep.ok ? keep.ok : nullptr;
     const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, 1, contrib.moments != nullptr, quant.n_q, !all_m, !all_flags, !all_ok,
-                     eff.sums ? eff.bins : 0u};
+                     eff.sums ? eff.bins : 0u, transform ? fact.kc : 0u};
     if (eff.sums && (rc = upload_effect_edges(P, c, eff)) != EZPZ_OK) return rc;
     if ((rc = prepare(P, r, c, need)) != EZPZ_OK) return rc;
     if (r.hist_bins && n_meas) HIP_TRY(hipMemsetAsync(c.hist, 0, n_meas * (r.hist_bins + 2) * sizeof(uint64_t), stream));
@@ -528,7 +557,7 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
             ef.first_round = first == 0;
             if ((rc = mce::enqueue_effects(P.effect_work, ef, stream)) != EZPZ_OK) return rc;
         }
-        if (select) {  // (a caller's device buffer is filled by the copies below)
+        if (rows_kept) {  // (a caller's device buffer is filled by the copies below)
             if ((rc = copy_out(all_m ? nullptr : P.all_m.p + first * n_meas, P.m.p, count * n_meas * sizeof(double), false, stream)) != EZPZ_OK ||
                 (rc = copy_out(all_flags ? nullptr : P.all_flags.p + first * n_meas, P.flags.p, count * n_meas, false, stream)) != EZPZ_OK ||
                 (rc = copy_out(all_ok ? nullptr : P.all_ok.p + first, P.ok.p, count, false, stream)) != EZPZ_OK)
@@ -565,6 +594,10 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
     if (select && (rc = mcq::enqueue_select(P.select_work, all_m ? all_m : P.all_m.p, all_flags ? all_flags : P.all_flags.p,
                                             all_ok ? all_ok : P.all_ok.p, samples, (uint32_t)n_meas, quant.probs, (uint32_t)quant.n_q, quant.z,
                                             quant.out, c.sys->lim.cus, stream)) != EZPZ_OK)
+        return rc;
+    if (transform && (rc = mcf::enqueue_factorial(P.factorial_work, all_m ? all_m : P.all_m.p, all_flags ? all_flags : P.all_flags.p,
+                                                  all_ok ? all_ok : P.all_ok.p, P.nominal.p, fact.kc, (uint32_t)n_meas, fact.out, c.sys->lim.cus,
+                                                  stream)) != EZPZ_OK)
         return rc;
     call_stamp(MC_LAUNCHED);
     return P.order.record(stream);
@@ -742,6 +775,36 @@ int run_host(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Con
     });
 }
 
+// ---- the entries: factorial effects ------------------------------------------------------------------------------------------------
+int factorial_device(const Call& c, const Keep& keep, Fact& fact) {
+    return enter(c, [&](Request& r) { return check_factorial(c, r, fact); },
+                 [&](McPlan& P, Request& r) { return run(P, r, c, keep, Contrib{}, Quant{}, Effects{}, fact); });
+}
+
+// `fact` holds host pointers here.
+int factorial_host(const Call& c, const Keep& keep, Fact& fact) {
+    return enter(c, [&](Request& r) { return check_factorial(c, r, fact); }, [&](McPlan& P, Request& r) {
+        const size_t n_meas = c.n_meas, kc = fact.kc, N = (size_t)1 << kc;
+        Staged out;
+        uint64_t* hist_dev = nullptr;
+        out.add(c.hist, n_meas * (r.hist_bins ? r.hist_bins + 2 : 0), hist_dev);
+        Fact dev;
+        dev.kc = fact.kc;
+        out.add(fact.out.info, n_meas, dev.out.info);
+        out.add(fact.out.main, n_meas * kc, dev.out.main);
+        out.add(fact.out.pair, n_meas * kc * kc, dev.out.pair);
+        out.add(fact.out.ss_order, n_meas * (kc + 1), dev.out.ss_order);
+        out.add(fact.out.ss_total, n_meas * kc, dev.out.ss_total);
+        out.add(fact.out.first, n_meas * kc, dev.out.first);
+        out.add(fact.out.total, n_meas * kc, dev.out.total);
+        if (fact.out.coef) out.add(fact.out.coef, n_meas * N, dev.out.coef);
+        return host_form(P, c, out, [&](Call& d) {
+            d.hist = hist_dev;
+            return run(P, r, d, keep, Contrib{}, Quant{}, Effects{}, dev);
+        });
+    });
+}
+
 // ---- the entries: Sobol indices ----------------------------------------------------------------------------------------------------
 int sobol_device(const Call& c, const EzpzSobolConfig* sc, SobolOut& out, const Keep& keep) {
     return enter(c, [&](Request& r) { return check_sobol(c, sc, r, out); }, [&](McPlan& P, Request& r) { return run_sobol(P, r, c, out, keep); });
@@ -894,6 +957,38 @@ int ezpz_system_tolerance_mc_quantiles(EzpzSystem* sys, const double* x0, const 
     Quant q;
     q.probs = probs, q.n_q = n_q, q.out = out;
     return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, qc, &q);
+}
+
+int ezpz_system_tolerance_mc_factorial_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                              const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records,
+                                              size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
+                                              const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg,
+                                              EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev,
+                                              double* keep_params_dev, double* keep_m_dev, uint8_t* keep_flags_dev,
+                                              uint8_t* keep_ok_dev, EzpzMcFactorial* info_dev, double* main_dev, double* pair_dev,
+                                              double* ss_order_dev, double* ss_total_dev, double* first_dev, double* total_dev,
+                                              double* coef_dev, void* stream) {
+    const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                 stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
+    Fact f;
+    f.out.info = info_dev, f.out.main = main_dev, f.out.pair = pair_dev, f.out.ss_order = ss_order_dev, f.out.ss_total = ss_total_dev;
+    f.out.first = first_dev, f.out.total = total_dev, f.out.coef = coef_dev;
+    return factorial_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, f);
+}
+
+int ezpz_system_tolerance_mc_factorial(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
+                                       const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                       const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                       uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats,
+                                       EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags,
+                                       uint8_t* keep_ok, EzpzMcFactorial* info, double* main, double* pair, double* ss_order,
+                                       double* ss_total, double* first, double* total, double* coef) {
+    const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                 stats, totals, hist, hipStreamPerThread};
+    Fact f;
+    f.out.info = info, f.out.main = main, f.out.pair = pair, f.out.ss_order = ss_order, f.out.ss_total = ss_total;
+    f.out.first = first, f.out.total = total, f.out.coef = coef;
+    return factorial_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, f);
 }
 
 int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,

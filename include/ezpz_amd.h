@@ -1118,6 +1118,87 @@ int ezpz_system_tolerance_mc_effects_device(EzpzSystem* sys, const double* x0_de
                                             double* cond_var_dev, double* eta2_dev, double* first_dev, uint32_t* bins_used_dev,
                                             void* stream);
 
+/* ---- Factorial effects: every main effect and every interaction of a 2^k corner run (a project extension).  A run
+ * whose driving dimensions are all CORNER or FIXED is a full two-level factorial design: samples 0 .. 2^kc - 1 are the 2^kc corners.
+ * One Walsh-Hadamard transform of its measured values gives the coefficient of every subset of dimensions, and from those the exact
+ * variance decomposition of the two-point tolerance model -- first-order and total indices with no estimator variance, for the CORNER
+ * dimensions ezpz_system_tolerance_sobol refuses -- which pair interacts, and whether the extreme corner is the one the linear signs
+ * predict.  No extra solve.
+ * SHAPES.  kc = n_corner, the number of CORNER dimensions, 1 <= kc <= EZPZ_MC_FACTORIAL_MAX_CORNERS; N = 2^kc rows; m = n_meas,
+ * 1 <= m <= EZPZ_MC_FACTORIAL_MAX_MEAS.  Row b is the corner whose bit c is set when the CORNER dimension of rank c (its place among
+ * the CORNER dimensions of the list) is at its b end: the Monte-Carlo section's definition.
+ * VALIDITY is the Monte-Carlo section's: row b is VALID FOR record i when it is ok (ezpz_mc_factorial: ok[b] != 0, ok == NULL: every
+ * one), flag bit 0 of (b, i) is clear (flags == NULL: every one) and m[b][i] is finite.  n_valid[i] counts the valid rows; record i is
+ * COMPLETE when n_valid[i] == N.  For a record that is not complete every floating output of the record is NaN (0x7FF8000000000000),
+ * its row of coef included, and its masks are 0.
+ * THE VALUES.  y[b] = m[b][i] - nominal_m[i], one rounded subtraction.
+ * THE TRANSFORM, in place on the N values w = y, for level l = 0, 1, .. kc - 1 with h = 2^l: for every b with bit l clear
+ *   (w[b], w[b + h]) <- (w[b] + w[b + h], w[b + h] - w[b])          each one rounded operation, both on the old pair
+ * then coef[S] = w[S] * 2^-kc.  So y(b) = sum over S of coef[S] * prod over c in S of s_c(b), s_c = +1 at the b end and -1 at the a
+ * end; coef[0] is the mean deviation and 2 coef[1 << c] the classical main effect.  A butterfly's result depends on its two inputs
+ * alone: no tiling, grid or pass structure can change a bit, and a host loop gives the device's bits.
+ * THE OUTPUTS per record i:
+ *   main [m][kc]          coef[1 << c]
+ *   pair [m][kc][kc]      coef[(1 << c) | (1 << e)]; symmetric, the diagonal +0.0
+ *   ss_order [m][kc + 1]  ss_order[o] = the sum over S with popcount(S) == o of coef[S] * coef[S], the product rounded, then added
+ *   ss_total [m][kc]      the same sum over S with bit c set
+ * THE ORDER OF THESE SUMS is the Monte-Carlo section's: the leaves are S = 0 .. N - 1, +0.0 where S is outside the class or past N;
+ * block q is the leaves [256 q, 256 q + 256), summed by the adjacent-pair tree (for h = 1, 2, .. 128: v[t] += v[t + h] for every t that
+ * is a multiple of 2 h); the blocks' sums are added left to right from +0.0.  No floating-point atomics.
+ * THE CLOSING STEP, each line evaluated as written, loops ascending:
+ *   var = ss_order[1] + .. + ss_order[kc], left to right from +0.0: the population variance of y over the corners (Parseval)
+ *   first [m][kc] = (main[c] * main[c]) / var;   total [m][kc] = ss_total[c] / var;   both +0.0 when var == 0
+ *   corner_hi: bit c set iff main[c] > 0;   corner_lo: bit c set iff main[c] < 0
+ *   m_hi = m[corner_hi][i];   m_lo = m[corner_lo][i]      the measured values at the corners the linear signs call the maximum and
+ *                                                       the minimum: compare with EzpzMcStats' max and min
+ * info [m]: one EzpzMcFactorial per record -- n_valid, complete (0 or 1), corner_hi, corner_lo, mean_dev = coef[0], var, m_hi, m_lo.
+ * coef [m][N] is optional: NULL, not returned.
+ * ezpz_mc_factorial[_device]: the reduction alone on any kept rows -- m [N][n_meas], flags (bytes, the same shape, may be NULL), ok
+ * [N] bytes (may be NULL), nominal_m [m] -- no system involved.  The host form computes on the host, with no device, and gives the
+ * device form's bits.  The _device form takes device pointers for every array; it only enqueues on `stream` and does not
+ * synchronise, on a workspace the library owns per device (n_meas x N doubles and the block sums; a workspace that has to grow is
+ * first allocated behind the last call's launches); calls on one device go one behind the other whatever their streams.
+ * ezpz_system_tolerance_mc_factorial[_device]: ezpz_system_tolerance_mc[_device] -- the same arguments, the same run, stats, totals,
+ * hist and keep_* byte for byte -- plus the outputs above, with nominal_m the statistics' nominal[i].  Every dimension must be CORNER
+ * or FIXED and samples must be 2^kc.  The run keeps m, flags and ok of every corner on the device, in the caller's keep_* buffers where
+ * the _device form is given them and else in the plan's workspace, as the run with quantiles does, and the transform follows the last
+ * round on the same stream.  The _device form takes device pointers for the outputs too.  Not combined with contributors, quantiles
+ * or effects in one call.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: n_corner == 0 or above the limit; n_meas == 0 or above the
+ * limit; a required output or input NULL (flags, ok and coef may be); for the run: a dimension that is neither CORNER nor FIXED, no
+ * CORNER dimension, samples other than 0 and 2^kc, with samples > 0 a required output NULL, and every argument error of
+ * ezpz_system_tolerance_mc.  The run with samples == 0: EZPZ_OK after those checks, nothing written. */
+#define EZPZ_MC_FACTORIAL_MAX_CORNERS 20u
+#define EZPZ_MC_FACTORIAL_MAX_MEAS 32u
+typedef struct EzpzMcFactorial { /* one per record; 56 bytes */
+    uint64_t n_valid;
+    uint32_t complete, corner_hi, corner_lo, reserved;
+    double mean_dev, var, m_hi, m_lo;
+} EzpzMcFactorial;
+int ezpz_mc_factorial(const double* m, const uint8_t* flags, const uint8_t* ok, const double* nominal_m, uint32_t n_corner, size_t n_meas,
+                      EzpzMcFactorial* info, double* main, double* pair, double* ss_order, double* ss_total, double* first,
+                      double* total, double* coef);
+int ezpz_mc_factorial_device(const double* m_dev, const uint8_t* flags_dev, const uint8_t* ok_dev, const double* nominal_m_dev,
+                             uint32_t n_corner, size_t n_meas, EzpzMcFactorial* info_dev, double* main_dev, double* pair_dev,
+                             double* ss_order_dev, double* ss_total_dev, double* first_dev, double* total_dev, double* coef_dev,
+                             void* stream);
+int ezpz_system_tolerance_mc_factorial(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
+                                       const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                       const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                       uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats,
+                                       EzpzMcTotals* totals, uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags,
+                                       uint8_t* keep_ok, EzpzMcFactorial* info, double* main, double* pair, double* ss_order,
+                                       double* ss_total, double* first, double* total, double* coef);
+int ezpz_system_tolerance_mc_factorial_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                              const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records,
+                                              size_t n_meas, const double* lim_lo, const double* lim_hi, const double* hist_lo,
+                                              const double* hist_hi, uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg,
+                                              EzpzMcStats* stats_dev, EzpzMcTotals* totals_dev, uint64_t* hist_dev,
+                                              double* keep_params_dev, double* keep_m_dev, uint8_t* keep_flags_dev,
+                                              uint8_t* keep_ok_dev, EzpzMcFactorial* info_dev, double* main_dev, double* pair_dev,
+                                              double* ss_order_dev, double* ss_total_dev, double* first_dev, double* total_dev,
+                                              double* coef_dev, void* stream);
+
 /* ---- Dimension targets: solve driving dimensions for measured targets (a project extension) -- the inverse of the
  * entries above: which values of the driving dimensions (the constraints at `positions`, as ezpz_system_solve_batch_params takes
  * them) put the reference dimensions `records` (measurement records, as ezpz_system_measure takes them; host memory in both forms)
