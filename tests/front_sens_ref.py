@@ -15,13 +15,25 @@ from oracle import oracle as O
 from front_ref import FASM_NOP, FASM_RHS, FRONT_EXPORTS, FRONT_REMOTE_PARENT, tri
 
 LAM = 1e-9
+# name -> (family, points, seed) of gen.graph_sketch; tree60 is the system of test_graph_families_on_fronts
+WIDE = {"tree60": ("tree", 60, 11), "tree108": ("tree", 108, 7020), "tree144": ("tree", 144, 7036), "comb213": ("comb", 213, 7019)}
+# name -> the workgroup counts at which the planner gives its share of the LDS a plan
+WIDE_WGS = {"tree60": (1, 2, 4), "tree108": (1, 2, 4), "tree144": (4,), "comb213": (4,)}
 
 
 def inputs(name):
     """sketchN = gen.connected_sketch(N, 1000 + N); band / hub = gen.graph_sketch(name, 50, default_rng(21));
     mixed40 = gen.mixed_sketch(40, 77): all 13 kinds with a parameter, drawn weights -- mixed40:unit with every weight 1.0,
     mixed40:double with every weight 2.0, mixed40+corner with the disjoint corner of `corner` appended;
-    linear100 = gen.linear_chain(100): the linear build -- linear100:weighted with weights of default_rng(78).uniform(0.5, 2.0)."""
+    linear100 = gen.linear_chain(100): the linear build -- linear100:weighted with weights of default_rng(78).uniform(0.5, 2.0);
+    WIDE (tree60, tree108, tree144, comb213): gen.graph_sketch systems chosen by the shape of their plans -- fronts of up to 63
+    rows, remote children of more than 50 rows, minimum-degree plans (tests/test_front_sens_cpu.py pins those shapes)."""
+    if name in WIDE:
+        family, npts, seed = WIDE[name]
+        rng = np.random.default_rng(seed)
+        if seed >= 7000:  # the draw of tests/test_gpu_fuzz.py and test_fronts_cpu.py: the number of points comes first
+            assert int(rng.integers(20, 500)) == npts, name
+        return gen.graph_sketch(family, npts, rng)
     if name.startswith("mixed40"):
         recs, g = gen.mixed_sketch(40, 77)
         if name == "mixed40+corner":

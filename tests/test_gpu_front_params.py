@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import front_sens_ref as FS
 import gen
 from oracle import oracle as O
 from oracle import textual as T
@@ -102,6 +103,8 @@ def _rebuilt_each(E, recs, n, wgs, pos, params, x0, cfg=None):
 
 
 def _inputs(name):
+    if name in FS.WIDE:
+        return FS.inputs(name)
     if name.startswith("sketch"):
         return gen.connected_sketch(int(name[6:]), 1000 + int(name[6:]))
     return gen.graph_sketch(name, 50, np.random.default_rng(21))
@@ -126,8 +129,36 @@ def test_chain_against_the_oracle(E, npts, wgs):
                                     oracle_result=(xo, it, conv), what=("front params", npts, wgs, b))
 
 
+# The draw of the wide inputs (front_sens_ref.WIDE: fronts of up to 63 rows, remote children of more than 50 rows arriving as
+# chunks, minimum-degree plans; tests/test_front_sens_cpu.py pins those shapes).  At the file's default draw (1e-3, 0.02) the
+# oracle converges on all 8 systems of tree60 in 3 iterations and runs to its 35-iteration limit on all 8 of tree108 and comb213
+# and on 5 of tree144; at (1e-4, 1e-3) it converges on all 8 of tree108 in 3-4 iterations, on 4 of tree144 and on 5 of comb213
+# (the device: 8 of tree60 in 2 iterations, 8 of tree108, 4 of tree144, 6 of comb213 -- the rebuilt systems end the same way).
+WIDE_DRAW = dict(amplitude=1e-4, jitter=1e-3)
+
+
+@pytest.mark.parametrize("name,wgs", [("tree60", 1), ("tree60", 2), ("tree60", 4), ("tree108", 1), ("tree108", 2), ("tree108", 4)])
+def test_wide_fronts_against_the_oracle(E, name, wgs):
+    """tree60 (fronts of 58 rows, a remote child of 52 rows on 2 workgroups) at the default draw, tree108 (a minimum-degree plan)
+    at the small one: statuses equal to the oracle's, coordinates at the fronts' bar (tests/test_front_params_cpu.py: the oracle
+    converges on exactly these 8 draws of each)."""
+    recs, g = _inputs(name)
+    s = front_system(E, recs, len(g), wgs)
+    pos, params, x0 = _draw(E, recs, g, 8, 33, **({} if name == "tree60" else WIDE_DRAW))
+    x, st, mask = s.solve_batch_params(x0, pos, params, want_mask=True)
+    for b in range(8):
+        r = substituted(recs, pos, params[b])
+        rc, xo, it, conv, nun = O.solve_batch(r, x0[b:b + 1], None, linsolve=O.LINSOLVE_SPARSE)
+        assert rc == 0 and int(conv[0]) == 1
+        assert (int(st["iterations"][b]), int(st["converged"][b]), int(st["n_unsatisfied"][b])) == (int(it[0]), int(conv[0]), int(nun[0])), b
+        assert int(mask[b].sum()) == int(nun[0])
+        assert_batch_matches_oracle(r, x0[b:b + 1], x[b:b + 1], st["iterations"][b:b + 1], st["converged"][b:b + 1], None,
+                                    oracle_result=(xo, it, conv), what=("front params", name, wgs, b))
+
+
 # ---- 2. bit for bit against rebuilt systems ----------------------------------------------------------------------------------------
-REBUILT = [("sketch25", 1), ("sketch75", 2), ("sketch150", 3), ("band", 1), ("band", 4), ("hub", 1), ("hub", 4)]
+REBUILT = [("sketch25", 1), ("sketch75", 2), ("sketch150", 3), ("band", 1), ("band", 4), ("hub", 1), ("hub", 4),
+           ("tree60", 1), ("tree60", 2), ("tree108", 2), ("tree144", 4), ("comb213", 4)]
 
 
 @pytest.fixture(scope="module")
@@ -138,7 +169,7 @@ def rebuilt(E):
     def get(name, wgs):
         if (name, wgs) not in cache:
             recs, g = _inputs(name)
-            pos, params, x0 = _draw(E, recs, g, 8, 33)
+            pos, params, x0 = _draw(E, recs, g, 8, 33, **(WIDE_DRAW if name in FS.WIDE else {}))
             cache[(name, wgs)] = (recs, g, pos, params, x0, _rebuilt_each(E, recs, len(g), wgs, pos, params, x0))
         return cache[(name, wgs)]
 
@@ -309,8 +340,11 @@ def test_linear_only_system(E):
 
 
 # ---- 8. sweeps ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2)])
+@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2), ("tree60", 2)])
 def test_sweeps_same_bits_as_the_chain_of_calls(E, name, wgs):
+    """tree60 on 2 workgroups (fronts of 58 rows, a remote child of 52 rows arriving as chunks at every iteration of every step):
+    on the oracle all 24 of its steps converge within 5 iterations and none within 3, so its steps that run to the limit come
+    from a second sweep at 2 iterations."""
     recs, g = _inputs(name)
     s = front_system(E, recs, len(g), wgs)
     pos, params, x0 = driven_walk(E, recs, g, 4, 6, 21, amplitude=1e-3, jitter=0.02)
@@ -327,7 +361,14 @@ def test_sweeps_same_bits_as_the_chain_of_calls(E, name, wgs):
     _same(got, want, (name, wgs))
     conv = got[1]["converged"]
     print(name, wgs, "converged", int(conv.sum()), "of", conv.size)
-    assert 0 < conv.sum() < conv.size  # (steps that converge and steps that run to the iteration limit)
+    if name == "tree60":
+        assert conv.all()
+        short = E.Config(max_iterations=2)
+        cut = s.sweep_params(x0, pos, params, config=short, want_mask=True)
+        _same(cut, chain_of_calls(s, x0, pos, params, config=short), (name, wgs, "2 iterations"))
+        assert not cut[1]["converged"].any()
+    else:
+        assert 0 < conv.sum() < conv.size  # (steps that converge and steps that run to the iteration limit)
     _same(s.sweep_params(x0, pos, params, want_mask=True), chain_of_calls(s, x0, pos, params), (name, wgs, "default limit"))
     assert not np.array_equal(got[0][0], got[0][5])
     # one step is the params entry

@@ -79,11 +79,18 @@ def rhs_per_item(n):
 
 
 # ---- 1. against the numpy reference -------------------------------------------------------------------------------------------------
+WIDE_CASES = [(name, wgs) for name in FS.WIDE for wgs in FS.WIDE_WGS[name]]
+
+
 @pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch75", 2), ("sketch150", 3), ("band", 1), ("band", 4), ("hub", 1), ("hub", 4),
-                                      ("mixed40", 1), ("mixed40", 3), ("mixed40:unit", 3)])
+                                      ("mixed40", 1), ("mixed40", 3), ("mixed40:unit", 3)] + WIDE_CASES)
 def test_against_the_numpy_reference(E, name, wgs):
     """If a system exceeded the rule, the default route's error on it (the parent's code, an independent implementation) would be
-    measured and 4 x that granted instead: it has not been needed -- the errors are logged beside the bars."""
+    measured and 4 x that granted instead: it has not been needed -- the errors are logged beside the bars.
+    The wide inputs (front_sens_ref.WIDE; their plans' shapes: test_wide_inputs_are_what_they_claim): fronts of 58, 36, 59 and 63
+    rows -- at 63 lane 63 holds the right-hand side's row --, remote children of 52, 30, 34 and 56 rows whose last rows arrive as
+    chunks, minimum-degree plans (tree108, tree144).  (Measured, profiles/front_sens_bar.txt: tree60 6.5e-13 at most, tree108
+    1.5e-9 against 2.9e-8, tree144 1.3e-10 against 2.0e-9, comb213 1.8e-7 against 2.5e-6.)"""
     sysobj, s = _system(E, name, wgs), FS.system(name)
     plan = sysobj.param_sensitivity_plan(s["pos"])
     print(name, wgs, plan)
@@ -94,6 +101,26 @@ def test_against_the_numpy_reference(E, name, wgs):
         for b, (Sref, spread) in enumerate(FS.references(name)):
             assert deg[b] == R.degenerate_count(s["recs"], s["x"][b], s["pos"], s["params"][b]), (name, b)
             R.assert_matches(S[b], Sref, spread, f"fronts, {name} on {wgs} workgroup(s) [{b}]")
+
+
+@pytest.mark.parametrize("name,wgs", WIDE_CASES)
+def test_wide_inputs_on_the_default_route(E, name, wgs):
+    """The same systems with the route set to "default" and back: each is one component under that route's 1024-variable limit,
+    so it serves them too -- an independent device implementation beside the reference, at the same bar.  An error of the fronts
+    alone belongs to the fronts' kernel, one on both routes to the input.  (Measured: tree60 4.5e-13, tree108 3.1e-9, tree144
+    1.5e-10, comb213 1.9e-7 -- the size of the fronts' own errors.)"""
+    sysobj, s = _system(E, name, wgs), FS.system(name)
+    sysobj.set_sensitivity_route("default")
+    try:
+        assert sysobj.param_sensitivity_plan(s["pos"])["route"] == 0
+        S, st, deg = sysobj.param_sensitivity(s["x"], s["pos"], s["params"], lam=s["lam"], want_degenerate=True)
+    finally:
+        sysobj.set_sensitivity_route("fronts")
+    assert sysobj.param_sensitivity_plan(s["pos"])["route"] == 1
+    assert S.shape == (len(s["x"]), len(s["pos"]), s["n_vars"]) and not st.any() and not deg.any()
+    with logging_here():
+        for b, (Sref, spread) in enumerate(FS.references(name)):
+            R.assert_matches(S[b], Sref, spread, f"default route, {name} created on {wgs} workgroup(s) [{b}]")
 
 
 # ---- 2. above the limit ---------------------------------------------------------------------------------------------------------------
@@ -124,9 +151,10 @@ def test_above_the_limit(E):
 
 
 # ---- 3. the same bits, however asked ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,wgs", [("sketch75", 2), ("hub", 1)])
+@pytest.mark.parametrize("name,wgs", [("sketch75", 2), ("hub", 1), ("tree60", 2), ("comb213", 4)])
 def test_the_same_bits_however_asked(E, name, wgs):
-    """Parameters are the system's own values (None), so that a shorter list leaves the constraints it drops at the same values."""
+    """Parameters are the system's own values (None), so that a shorter list leaves the constraints it drops at the same values.
+    (comb213: S is 426 x 426 doubles per system, so its tiled call has 16 systems, the others' 64.)"""
     sysobj, s = _system(E, name, wgs), FS.system(name)
     pos, x = s["pos"], s["x"]
     k = len(pos)
@@ -148,7 +176,7 @@ def test_the_same_bits_however_asked(E, name, wgs):
         assert np.array_equal(a, full), n
     one, _ = sysobj.param_sensitivity(x[:1], pos, None, lam=s["lam"])
     assert np.array_equal(one[0], full[0])
-    tiled, st = sysobj.param_sensitivity(np.tile(x[:1], (64, 1)), pos, None, lam=s["lam"])
+    tiled, st = sysobj.param_sensitivity(np.tile(x[:1], (16 if name == "comb213" else 64, 1)), pos, None, lam=s["lam"])
     assert not st.any() and np.array_equal(tiled, np.broadcast_to(one, tiled.shape))
     order = np.asarray([1, 0])
     a, _ = sysobj.param_sensitivity(x[order], pos, None, lam=s["lam"])
@@ -159,18 +187,37 @@ def test_the_same_bits_however_asked(E, name, wgs):
     assert np.array_equal(b, a[order][:, perm])
 
 
-def test_a_workgroups_second_item(E):
-    """sketch25, 8 listed positions, 4096 tiled systems (13 MB of S): persistent workgroups take further items."""
-    sysobj, s = _system(E, "sketch25", 1), FS.system("sketch25")
+def _second_item(E, name, wgs, tiles):
+    """8 listed positions make one item per system; a 512-thread workgroup has a quarter of a CU at the least, so a launch has at
+    most 4 x CUs / wgs slots: with twice as many tiled systems every slot takes a further item."""
+    import torch
+
+    sysobj, s = _system(E, name, wgs), FS.system(name)
     pos = s["pos"][np.linspace(0, len(s["pos"]) - 1, 8).astype(int)]
+    plan = sysobj.param_sensitivity_plan(pos)
+    assert plan["front_workgroups"] == wgs and plan["rhs_per_item"] == 8 and plan["items_per_system"] == 1, plan
+    assert tiles >= 2 * (4 * int(torch.cuda.get_device_properties(0).multi_processor_count) // wgs)
     one, _ = sysobj.param_sensitivity(s["x"][:1], pos, None, lam=s["lam"])
-    big, st = sysobj.param_sensitivity(np.tile(s["x"][:1], (4096, 1)), pos, None, lam=s["lam"])
+    big, st = sysobj.param_sensitivity(np.tile(s["x"][:1], (tiles, 1)), pos, None, lam=s["lam"])
     assert not st.any() and np.array_equal(big, np.broadcast_to(one, big.shape))
 
 
+def test_a_workgroups_second_item(E):
+    """sketch25, 8 listed positions, 4096 tiled systems (13 MB of S): persistent workgroups take further items."""
+    _second_item(E, "sketch25", 1, 4096)
+
+
+def test_a_slots_second_item_with_a_wide_remote_child(E):
+    """tree60 on 2 workgroups, 8 listed positions, 2048 tiled systems (16 MB of S): the chunks of the 52-row remote child are
+    reused across items and epochs."""
+    _second_item(E, "tree60", 2, 2048)
+
+
 # ---- 4. failures stay local ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch150", 3)])
+@pytest.mark.parametrize("name,wgs", [("sketch25", 1), ("sketch150", 3), ("tree144", 4)])
 def test_failures_stay_local(E, name, wgs):
+    """A lambda below minus the smallest eigenvalue of JtJ: status 1 and NaN rows (a numerical status, no fault).  A NaN start in
+    system 2 of 4: its rows alone are NaN, the others' bits are the good call's, and so are those of the call after it."""
     sysobj, s = _system(E, name, wgs), FS.system(name)
     x = np.tile(s["x"], (2, 1))
     p = np.tile(s["params"], (2, 1))
@@ -185,6 +232,8 @@ def test_failures_stay_local(E, name, wgs):
     S, st = sysobj.param_sensitivity(xx, s["pos"], p, lam=s["lam"])
     assert st.tolist() == [0, 0, 1, 0] and np.isnan(S[2]).all()
     assert np.array_equal(S[[0, 1, 3]], good[[0, 1, 3]])
+    after, st = sysobj.param_sensitivity(x, s["pos"], p, lam=s["lam"])
+    assert not st.any() and np.array_equal(after, good)
 
 
 # ---- 5. exact zeros -----------------------------------------------------------------------------------------------------------------------
