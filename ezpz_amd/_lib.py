@@ -25,6 +25,7 @@ MC_TOTALS_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_all_in", "<
 assert MC_DIST_DTYPE.itemsize == 24 and MC_STATS_DTYPE.itemsize == 88 and MC_TOTALS_DTYPE.itemsize == 24
 MC_MOMENTS_INFO_DTYPE = np.dtype([("samples", "<u8"), ("n_complete", "<u8")])  # EzpzMcMomentsInfo
 MC_MOMENT_MAX = 64  # EZPZ_MC_MOMENT_MAX
+MC_SEQUENCE = 1  # EZPZ_MC_SEQUENCE: bit 0 of EzpzMcDist.reserved
 assert MC_MOMENTS_INFO_DTYPE.itemsize == 16
 BRANCH_INFO_DTYPE = np.dtype([("samples", "<u8"), ("n_ok", "<u8"), ("n_branches", "<u8"), ("n_overflow", "<u8")])  # EzpzBranchInfo
 BRANCH_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("dist_inf", "<f8"), ("status", STATUS_DTYPE)])  # EzpzBranch

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, MC_FACTORIAL_DTYPE, MC_FACTORIAL_MAX_CORNERS, MC_FACTORIAL_MAX_MEAS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_SEQUENCE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, MC_FACTORIAL_DTYPE, MC_FACTORIAL_MAX_CORNERS, MC_FACTORIAL_MAX_MEAS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1225,7 +1225,8 @@ class System:
     def tolerance_mc(self, x0, positions, dists, records, samples: int, seed: int = 0, nominal=None, limits=None, hist=None,
                      chunk: int = 0, keep: bool = False, config: Optional[Config] = None, contributors: bool = False,
                      pivot_rel: Optional[float] = None, quantiles=None, quantile_z: float = 0.0,
-                     effects: Optional["EffectsConfig"] = None, factorial: bool = False, keep_coef: bool = False) -> "McResult":
+                     effects: Optional["EffectsConfig"] = None, factorial: bool = False, keep_coef: bool = False,
+                     sampling: str = "philox") -> "McResult":
         """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
         solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
         statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
@@ -1244,7 +1245,12 @@ class System:
         factorial: the same run through `ezpz_system_tolerance_mc_factorial` -- every dimension CORNER or FIXED and samples ==
         `mc_corner_count(dists)`: the corner run as a full two-level factorial design, every main effect and interaction by one
         Walsh-Hadamard transform on the device; the result also has `factorial` (an `McFactorial`); keep_coef: with all 2^kc
-        coefficients per record.  Not together with contributors, quantiles or effects."""
+        coefficients per record.  Not together with contributors, quantiles or effects.
+        sampling: "philox" -- the list as given -- or "sequence": every UNIFORM and NORMAL dimension of this call drawn from the
+        low-discrepancy sequence (`McDist.uniform(..., sequence=True)`): for a smooth response mean, std and what is built on them
+        converge nearly as 1 / samples; tail yields gain little.  At most 64 positions up to the last such dimension, 2^32 samples."""
+        if sampling != "philox":
+            dists = _with_sampling(dists, sampling)
         if quantiles is not None and contributors:
             raise ValueError("quantiles together with contributors: run them one after the other")
         if effects is not None and (contributors or quantiles is not None):
@@ -1568,25 +1574,28 @@ class McDist:
     """A driving dimension's tolerance distribution (EzpzMcDist): the deviation added to its nominal value."""
     FIXED, UNIFORM, NORMAL, CORNER = range(4)
 
-    def __init__(self, kind: int, a: float = 0.0, b: float = 0.0):
-        self.kind, self.a, self.b = int(kind), float(a), float(b)
+    def __init__(self, kind: int, a: float = 0.0, b: float = 0.0, sequence: bool = False):
+        self.kind, self.a, self.b, self.sequence = int(kind), float(a), float(b), bool(sequence)
 
     def __repr__(self):
-        return "McDist.%s(%r, %r)" % (("fixed", "uniform", "normal", "corner")[self.kind] if 0 <= self.kind < 4 else self.kind, self.a, self.b)
+        return "McDist.%s(%r, %r%s)" % (("fixed", "uniform", "normal", "corner")[self.kind] if 0 <= self.kind < 4 else self.kind, self.a, self.b,
+                                        ", sequence=True" if self.sequence else "")
 
     @staticmethod
     def fixed() -> "McDist":
         return McDist(McDist.FIXED)
 
     @staticmethod
-    def uniform(lo: float, hi: float) -> "McDist":
-        """A deviation uniform in [lo, hi)."""
-        return McDist(McDist.UNIFORM, lo, hi)
+    def uniform(lo: float, hi: float, sequence: bool = False) -> "McDist":
+        """A deviation uniform in [lo, hi).  sequence: a low-discrepancy draw (EZPZ_MC_SEQUENCE) -- a Sobol' point with a seed-keyed
+        shift in place of the pseudo-random words; at most the first 64 positions of a list, at most 2^32 samples."""
+        return McDist(McDist.UNIFORM, lo, hi, sequence)
 
     @staticmethod
-    def normal(sigma: float, trunc: float = 0.0) -> "McDist":
-        """A normal deviation of standard deviation sigma, truncated at +-trunc sigmas (0: not truncated, else >= 1)."""
-        return McDist(McDist.NORMAL, sigma, trunc)
+    def normal(sigma: float, trunc: float = 0.0, sequence: bool = False) -> "McDist":
+        """A normal deviation of standard deviation sigma, truncated at +-trunc sigmas (0: not truncated, else >= 1).  sequence: as
+        for `uniform`, through the inverse of the normal distribution; untruncated it reaches about +-6.34 sigma."""
+        return McDist(McDist.NORMAL, sigma, trunc, sequence)
 
     @staticmethod
     def corner(lo: float, hi: float) -> "McDist":
@@ -1600,8 +1609,19 @@ def mc_dists(dists) -> np.ndarray:
         return np.ascontiguousarray(dists)
     out = np.zeros(len(dists), dtype=MC_DIST_DTYPE)
     for j, d in enumerate(dists):
-        out[j] = (d.kind, 0, d.a, d.b)
+        out[j] = (d.kind, MC_SEQUENCE if getattr(d, "sequence", False) else 0, d.a, d.b)
     return out
+
+
+def _with_sampling(dists, sampling: str) -> np.ndarray:
+    """The list as the library reads it, for `System.tolerance_mc`'s sampling: "sequence" flags every UNIFORM and NORMAL dimension."""
+    if sampling not in ("philox", "sequence"):
+        raise ValueError(f"sampling: 'philox' or 'sequence', got {sampling!r}")
+    d = mc_dists(dists)
+    if sampling == "sequence":
+        d = d.copy()
+        d["reserved"][(d["kind"] == McDist.UNIFORM) | (d["kind"] == McDist.NORMAL)] |= MC_SEQUENCE
+    return d
 
 
 def mc_sample(seed: int, dists, nominal, first: int, count: int) -> np.ndarray:

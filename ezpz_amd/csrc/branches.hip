@@ -224,7 +224,11 @@ int check_run(EzpzSystem* sys, const void* x0, const double* x0_host, const Ezpz
     if (int rc = ezpz_mc_sample(0, dist, zeros.data(), n, 0, 0, nullptr)) return rc;
     r.dists.resize(n);
     uint32_t corners = 0;
-    for (size_t v = 0; v < n; ++v) r.dists[v] = mc::Dist{dist[v].kind, dist[v].kind == EZPZ_MC_CORNER ? corners++ : 0u, dist[v].a, dist[v].b, 0.0};
+    for (size_t v = 0; v < n; ++v) {
+        // (a flagged dimension has 2^32 samples: ezpz_mc_sample's error for first + count past them)
+        if (mc::sequenced(dist[v]) && samples > 1ull << 32) return EZPZ_ERR_INVALID_ARGUMENT;
+        r.dists[v] = mc::dist_of(dist[v], dist[v].kind == EZPZ_MC_CORNER ? corners++ : 0u, 0.0);
+    }
     if (batch && samples && (!x0 || !info || !branches || !x_branch)) return EZPZ_ERR_INVALID_ARGUMENT;
     return EZPZ_OK;
 }

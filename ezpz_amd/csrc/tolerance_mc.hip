@@ -82,29 +82,6 @@ McPlan& plan_of(EzpzSystem* sys) {
     return *static_cast<McPlan*>(sys->tolerance_mc.get());
 }
 
-// The argument errors of the distributions, and the sampler's table.
-int check_dists(const EzpzMcDist* dist, const double* nominal, size_t n_param, std::vector<mc::Dist>& out) {
-    out.clear();
-    if (n_param == 0) return EZPZ_OK;
-    if (!dist || !nominal || n_param > 0xFFFFFFFEull) return EZPZ_ERR_INVALID_ARGUMENT;
-    out.resize(n_param);
-    uint32_t corners = 0;
-    for (size_t j = 0; j < n_param; ++j) {
-        const EzpzMcDist& d = dist[j];
-        if (d.kind > EZPZ_MC_CORNER || !std::isfinite(d.a) || !std::isfinite(d.b) || !std::isfinite(nominal[j]))
-            return EZPZ_ERR_INVALID_ARGUMENT;
-        if (d.kind == EZPZ_MC_UNIFORM && d.a > d.b) return EZPZ_ERR_INVALID_ARGUMENT;
-        if (d.kind == EZPZ_MC_NORMAL && (d.a < 0.0 || d.b < 0.0 || (d.b > 0.0 && d.b < 1.0))) return EZPZ_ERR_INVALID_ARGUMENT;
-        uint32_t rank = 0;
-        if (d.kind == EZPZ_MC_CORNER) {
-            if (corners == mc::kMaxCorners) return EZPZ_ERR_INVALID_ARGUMENT;
-            rank = corners++;
-        }
-        out[j] = mc::Dist{d.kind, rank, d.a, d.b, nominal[j]};
-    }
-    return EZPZ_OK;
-}
-
 // What every entry is given, as given: a device form's pointers and stream, or a host form's pointers and hipStreamPerThread.  (The
 // Sobol entries have no limits and no histogram.)
 struct Call {
@@ -131,6 +108,7 @@ struct Request {
     std::vector<uint32_t> words;  // the packed measurement records (compared by the measure entry against its kept list)
     std::vector<double> tab;      // lim_lo | lim_hi | hist_lo | hist_scale | the draw's nominal
     bool limits = false;
+    bool sequence = false;  // some dimension is flagged (EZPZ_MC_SEQUENCE): the round's sampler is the walk
     uint32_t hist_bins = 0;
     uint64_t seed = 0, chunk = 0;
 };
@@ -175,7 +153,8 @@ int check_run(const Call& c, Request& r) {
         for (size_t j = 0; j < n_param; ++j) own[j] = sys->host_cs[c.positions[j]].param;
         nominal = own.data();
     }
-    if (int rc = check_dists(c.dist, nominal, n_param, r.dists)) return rc;
+    if (int rc = mc::check_dists(c.dist, nominal, n_param, 0, c.samples, r.dists)) return rc;
+    for (const mc::Dist& d : r.dists) r.sequence = r.sequence || d.sequence != 0;
     for (size_t j = 0; j < n_param; ++j) r.tab.push_back(nominal[j]);
     if (c.samples && (!c.stats || !c.totals || (conf.hist_bins && n_meas && !c.hist) || (sys->counts.n_vars && !c.x0))) return EZPZ_ERR_INVALID_ARGUMENT;
     r.limits = c.lim_lo != nullptr;
@@ -297,6 +276,8 @@ int check_sobol(const Call& c, const EzpzSobolConfig* sc, Request& r, SobolOut& 
     o.fixed_mask = 0;
     for (size_t j = 0; j < n_param; ++j) {
         if (r.dists[j].kind == EZPZ_MC_CORNER) return EZPZ_ERR_INVALID_ARGUMENT;
+        // (a flagged dimension's matrix B would be matrix A XOR a constant: the two are not independent, and pick-freeze needs that)
+        if (r.dists[j].sequence) return EZPZ_ERR_INVALID_ARGUMENT;
         if (r.dists[j].kind == EZPZ_MC_FIXED) o.fixed_mask |= 1u << j;
     }
     if (c.samples && (!o.sums || !o.n_complete || !o.var || (n_param && (!o.first || !o.total || !o.first_var || !o.total_var))))
@@ -448,6 +429,23 @@ struct Pick {
     uint32_t which;
 };
 
+// The sampler of a list with flagged dimensions: the walk, its table in LDS.  EZPZ_MC_SEQUENCE_KERNEL=const: the walk on constant
+// memory; =direct: every point evaluated directly (A/B runs; the same bytes from all three).
+void launch_sequence_sampler(const McPlan& P, const Request& r, const Call& c, uint64_t first, uint64_t count) {
+    static const int variant = [] {
+        const char* e = std::getenv("EZPZ_MC_SEQUENCE_KERNEL");
+        return !e ? 0 : !std::strcmp(e, "const") ? 1 : !std::strcmp(e, "direct") ? 2 : 0;
+    }();
+    const uint32_t n_param = (uint32_t)r.dists.size();
+    const uint64_t runs = (count + mc::kWalkRun - 1) / mc::kWalkRun;
+    if (variant == 2)
+        hipLaunchKernelGGL(mc::mc_sample_direct_kernel, dim3(stride_grid(count * n_param, c.sys)), dim3(256), 0, c.stream, P.dist.p, r.seed, first, count, n_param, P.params.p);
+    else if (variant == 1)
+        hipLaunchKernelGGL(mc::mc_sample_walk_kernel<false>, dim3(stride_grid(runs * n_param, c.sys)), dim3(256), 0, c.stream, P.dist.p, r.seed, first, count, n_param, P.params.p);
+    else
+        hipLaunchKernelGGL(mc::mc_sample_walk_kernel<true>, dim3(stride_grid(runs * n_param, c.sys)), dim3(256), 0, c.stream, P.dist.p, r.seed, first, count, n_param, P.params.p);
+}
+
 // Samples [first, first + count) drawn -- run()'s sampler for pick == NULL -- solved from copies of x0 and measured into m and flags.
 int sub_round(McPlan& P, const Request& r, const Call& c, const Pick* pick, uint64_t first, uint64_t count, double* m, uint8_t* flags) {
     EzpzSystem* sys = c.sys;
@@ -455,6 +453,8 @@ int sub_round(McPlan& P, const Request& r, const Call& c, const Pick* pick, uint
     int rc;
     if (n_param && pick)
         hipLaunchKernelGGL(mc::mc_sample_pick_kernel, dim3(stride_grid(count * n_param, sys)), dim3(256), 0, c.stream, P.dist.p, r.seed, pick->seed_b, pick->which, first, count, (uint32_t)n_param, P.params.p);
+    else if (n_param && r.sequence)
+        launch_sequence_sampler(P, r, c, first, count);
     else if (n_param)
         hipLaunchKernelGGL(mc::mc_sample_kernel, dim3(stride_grid(count * n_param, sys)), dim3(256), 0, c.stream, P.dist.p, r.seed, first, count, (uint32_t)n_param, P.params.p);
     if (n) hipLaunchKernelGGL(mc::mc_broadcast_kernel, dim3(stride_grid(count * n, sys)), dim3(256), 0, c.stream, c.x0, (uint32_t)n, count, P.x_in.p);
@@ -840,12 +840,7 @@ void ezpz_default_mc_config(EzpzMcConfig* mc_cfg) {
 
 int ezpz_mc_sample(uint64_t seed, const EzpzMcDist* dist, const double* nominal, size_t n_param, uint64_t first, size_t count,
                    double* params_out) {
-    std::vector<mc::Dist> dists;
-    if (int rc = check_dists(dist, nominal, n_param, dists)) return rc;
-    if (count && n_param && !params_out) return EZPZ_ERR_INVALID_ARGUMENT;
-    for (size_t s = 0; s < count; ++s)
-        for (size_t j = 0; j < n_param; ++j) params_out[s * n_param + j] = mc::draw(seed, first + s, (uint32_t)j, dists[j]);
-    return EZPZ_OK;
+    return mc::sample_host(seed, dist, nominal, n_param, first, count, params_out);
 }
 
 int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,

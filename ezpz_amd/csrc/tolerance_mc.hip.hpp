@@ -1,7 +1,7 @@
 // Monte-Carlo tolerance analysis (include/ezpz_amd.h: ezpz_mc_sample, ezpz_system_tolerance_mc[_device]): the three
 // kernels of a round -- mc_sample_kernel (the round's driven values), mc_broadcast_kernel (its copies of x0) and mc_reduce_kernel
 // (the round's statistics, folded into the running results) -- and mc_sample_pick_kernel, the sampler of the Sobol indices' pick-freeze
-// matrices.  The sampler itself -- one __host__ __device__ body behind the host
+// matrices, and mc_sample_walk_kernel, the sampler of a list with low-discrepancy dimensions.  The sampler itself -- one __host__ __device__ body behind the host
 // entry and the sampler kernel -- is in mc_sampler.hip.hpp; the host plan and the entries are in tolerance_mc.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +24,57 @@ __global__ __launch_bounds__(256) void mc_sample_kernel(const Dist* __restrict__
     for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
         const uint64_t s = idx / n_param;
         const uint32_t j = (uint32_t)(idx - s * n_param);
+        params[idx] = draw_plain(seed, first + s, j, dist[j]);
+    }
+}
+
+// ---- the same for a list with flagged dimensions (EZPZ_MC_SEQUENCE) -----------------------------------------------
+// A work item is kWalkRun consecutive samples of one dimension, and neighbouring lanes take neighbouring dimensions of the same
+// samples, so a wavefront's stores of one step are whole runs of a row.  A flagged dimension evaluates its first point directly --
+// one table word per set bit of the Gray code -- and steps to each next one with one word and one XOR; the shift is one Philox
+// block per work item.  The arithmetic is integer: the walk gives the bits of the direct evaluation wherever it starts, so the
+// rounds and the grid stride do not show.  An unflagged dimension of the list is the plain draw.  kLds: the first min(n_param, 64)
+// rows of the table are staged in LDS (8 KiB at most) and the steps read them there; else every read goes to constant memory.
+constexpr uint32_t kWalkRun = 8;
+template <bool kLds>
+__global__ __launch_bounds__(256) void mc_sample_walk_kernel(const Dist* __restrict__ dist, uint64_t seed, uint64_t first, uint64_t count,
+                                                             uint32_t n_param, double* __restrict__ params) {
+    __shared__ uint32_t s_v[kLds ? kSequenceDims * kSequenceBits : 1];
+    if (kLds) {
+        const uint32_t words = (n_param < kSequenceDims ? n_param : kSequenceDims) * kSequenceBits;
+        for (uint32_t i = threadIdx.x; i < words; i += 256) s_v[i] = kSequenceDevice[0][i];
+        __syncthreads();
+    }
+    const uint64_t runs = (count + kWalkRun - 1) / kWalkRun, total = runs * n_param, stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
+        const uint64_t run = idx / n_param;
+        const uint32_t j = (uint32_t)(idx - run * n_param);
+        const uint64_t s0 = run * kWalkRun, s1 = s0 + kWalkRun < count ? s0 + kWalkRun : count;
+        const Dist d = dist[j];
+        double* out = params + s0 * n_param + j;
+        if (!d.sequence) {
+            for (uint64_t s = s0; s < s1; ++s, out += n_param) *out = draw_plain(seed, first + s, j, d);
+            continue;
+        }
+        // (a flagged dimension: j < 64 and first + count <= 2^32, by check_dists)
+        const uint32_t* v = kLds ? s_v + j * kSequenceBits : kSequenceDevice[j];
+        const uint32_t shift = sequence_shift(seed, j);
+        uint32_t b = (uint32_t)(first + s0), x = sequence_point(v, b);
+        for (uint64_t s = s0;; out += n_param) {
+            *out = sequence_value(x ^ shift, d);
+            if (++s == s1) break;
+            x = sequence_step(v, x, ++b);
+        }
+    }
+}
+
+// ... and with every point evaluated directly, one draw per work item as in mc_sample_kernel: the measurements' other side
+__global__ __launch_bounds__(256) void mc_sample_direct_kernel(const Dist* __restrict__ dist, uint64_t seed, uint64_t first, uint64_t count,
+                                                               uint32_t n_param, double* __restrict__ params) {
+    const uint64_t total = count * n_param, stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
+        const uint64_t s = idx / n_param;
+        const uint32_t j = (uint32_t)(idx - s * n_param);
         params[idx] = draw(seed, first + s, j, dist[j]);
     }
 }
@@ -37,7 +88,7 @@ __global__ __launch_bounds__(256) void mc_sample_pick_kernel(const Dist* __restr
     for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
         const uint64_t s = idx / n_param;
         const uint32_t j = (uint32_t)(idx - s * n_param);
-        params[idx] = draw(pick == kPickAll || j == pick ? seed_b : seed_a, first + s, j, dist[j]);
+        params[idx] = draw_plain(pick == kPickAll || j == pick ? seed_b : seed_a, first + s, j, dist[j]);  // (no flagged dimension: check_sobol)
     }
 }
 

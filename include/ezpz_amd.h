@@ -705,6 +705,30 @@ int ezpz_system_measure_vjp_device(EzpzSystem* sys, const EzpzConstraint* record
  * there in the last bits of log, cos and sqrt -- the ONLY thing in this section that is not bit-reproducible between the two.
  * EZPZ_ERR_INVALID_ARGUMENT with nothing written: an unknown kind, a non-finite a, b or nominal, a > b for UNIFORM, sigma < 0, a
  * truncation in (0, 1) (or negative), more than 20 CORNER dimensions, dist or nominal NULL with n_param > 0.
+ * THE SEQUENCE (a project extension).  Bit 0 of EzpzMcDist.reserved, EZPZ_MC_SEQUENCE, asks for a low-discrepancy
+ * draw of that dimension: a Sobol' point with a seed-keyed digital shift in place of the Philox words.  It is read on UNIFORM and
+ * NORMAL dimensions and ignored on FIXED and CORNER; the other bits of `reserved` stay ignored; with the bit clear every byte of
+ * every draw above is what it was.  For a flagged dimension at list position j and sample b:
+ *   g = b ^ (b >> 1);   x = the XOR over the set bits c of g of V[j][c]
+ *   V: the 32-bit Joe-Kuo direction numbers (new-joe-kuo-6.21201) of Sobol' dimensions 0 .. 63, bit 31 first (V[j][0] = 2^31) -- with
+ *   the Gray-coded index, x of row b is row b of the unscrambled 32-bit Sobol' sequence in its usual order
+ *   s = w0 of Philox4x32-10 with counter (0, 0, j, 0xFFFFFFFF) and the seed as key (no plain draw uses the attempt 0xFFFFFFFF)
+ *   u = ((x ^ s) + 0.5) * 2^-32, exact in a double and inside (0, 1), open at both ends
+ *   UNIFORM  a + (b - a) * u
+ *   NORMAL   a * z;  without a truncation z = PHI_INV(u);  with a truncation T:  p = P_lo + (P_hi - P_lo) * u,  P_lo = 0.5 *
+ *            erfc(T / sqrt(2)) and P_hi = 1 - P_lo computed once on the host,  z = PHI_INV(p) clamped to [-T, T].  No attempts.
+ * PHI_INV is Wichura's algorithm AS 241, routine PPND16 (Applied Statistics 37 (1988) 477-484), evaluated as published, no product
+ * contracted.  Its central branch, |p - 0.5| <= 0.425 -- 85 % of the draws -- is a rational polynomial of + - * / alone: those draws,
+ * and every flagged UNIFORM draw, are bit-identical on the host and on the device.  Its two tail branches use log and sqrt and fall
+ * under the caveat above.  An untruncated flagged NORMAL reaches about +-6.34 sigma and no further: u ends at 2^-33 from 0 and 1.
+ * The draw still depends on (seed, b, j) and dist[j] alone, so every reduction below takes it as it takes a plain one.  What it
+ * buys: for a smooth response the error of mean and std (and of what is built on them: beta, contrib, cond_mean) falls nearly as
+ * 1 / samples where a plain run's falls as 1 / sqrt(samples); it does NOT help yields at a tail limit or extreme quantiles much,
+ * and the variance estimates of a plain run (var / n as the error of mean) overstate a flagged run's error.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing written or enqueued: a flagged UNIFORM or NORMAL dimension at a position j >= 64; a
+ * flagged dimension with first + count > 2^32 (ezpz_mc_sample) or samples > 2^32 (the runs); ezpz_system_tolerance_sobol[_device]
+ * with a flagged dimension -- its matrix B would be matrix A XOR a constant, not an independent matrix, and pick-freeze on the two
+ * means nothing (as a CORNER dimension has no second matrix at all).
  * THE RUN.  ezpz_system_tolerance_mc[_device] works in rounds of `chunk` samples (rounded up to a multiple of 256; 0: the library's
  * choice, 65536 or less for a large system), everything on one stream: the sampler writes the round's params, a second kernel its
  * copies of x0, ezpz_system_solve_batch_params_device solves them -- that entry itself: whatever params route the system has, the
@@ -745,8 +769,9 @@ int ezpz_system_measure_vjp_device(EzpzSystem* sys, const EzpzConstraint* record
 #define EZPZ_MC_UNIFORM 1u
 #define EZPZ_MC_NORMAL 2u
 #define EZPZ_MC_CORNER 3u
+#define EZPZ_MC_SEQUENCE 1u /* bit 0 of EzpzMcDist.reserved: THE SEQUENCE */
 typedef struct EzpzMcDist { /* 24 bytes */
-    uint32_t kind, reserved;
+    uint32_t kind, reserved; /* reserved: EZPZ_MC_SEQUENCE or 0; the other bits are ignored */
     double a, b;
 } EzpzMcDist;
 typedef struct EzpzMcConfig { /* 16 bytes */
