@@ -1251,12 +1251,7 @@ class System:
         converge nearly as 1 / samples; tail yields gain little.  At most 64 positions up to the last such dimension, 2^32 samples."""
         if sampling != "philox":
             dists = _with_sampling(dists, sampling)
-        if quantiles is not None and contributors:
-            raise ValueError("quantiles together with contributors: run them one after the other")
-        if effects is not None and (contributors or quantiles is not None):
-            raise ValueError("effects together with contributors or quantiles: run them one after the other")
-        if factorial and (contributors or quantiles is not None or effects is not None):
-            raise ValueError("factorial together with contributors, quantiles or effects: run them one after the other")
+        kind = _mc_kind(contributors, quantiles, effects, factorial)
         x0 = self._mc_x0(x0)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
@@ -1267,43 +1262,15 @@ class System:
         kept = (np.zeros((samples, n_param)), np.zeros((samples, k)), np.zeros((samples, k), np.uint8),
                 np.zeros(samples, np.uint8)) if keep else (None,) * 4
         cfg = (config or Config())._c()
+        kind = kind(self, pos, d, nominal, k, samples, pivot_rel=pivot_rel, quantiles=quantiles, quantile_z=quantile_z, effects=effects,
+                    keep_coef=keep_coef)
         args = (self._h, _ptr(x0), _ptr(pos), n_param, _ptr(d), _ptr(nominal), _ptr(recs), k, _ptr(lim_lo), _ptr(lim_hi), _ptr(hist_lo), _ptr(hist_hi),
                 samples, C.byref(mc), C.byref(cfg), stats.ctypes.data, totals.ctypes.data, _ptr(counts), *(_ptr(a) for a in kept))
-        if quantiles is not None:
-            probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
-            out = np.zeros((k, len(probs)), dtype=MC_QUANTILE_DTYPE)
-            qc = CMcQuantileConfig(float(quantile_z), 0)
-            rc = lib().ezpz_system_tolerance_mc_quantiles(*args, _ptr(probs), len(probs), C.byref(qc), _ptr(out))
-            if rc != 0:
-                raise NonLinearSystemError(rc)
-            return McResult(stats, totals, counts, kept if keep else None, quantiles=out)
-        if effects is not None:
-            ec, edges, bounds = _effects_request(effects, d, pos, nominal, self)
-            sums, cnt, out = _effect_outputs(n_param, k, ec.bins)
-            rc = lib().ezpz_system_tolerance_mc_effects(*args, C.byref(ec), _ptr(edges), _ptr(sums), _ptr(cnt), *(_ptr(a) for a in out))
-            if rc != 0:
-                raise NonLinearSystemError(rc)
-            return McResult(stats, totals, counts, kept if keep else None,
-                            effects=McEffects(sums, cnt, stats["nominal"].copy(), edges, *out, bounds=bounds))
-        if factorial:
-            dims = _corner_dims(d)
-            out = _factorial_outputs(len(dims), k, keep_coef)
-            rc = lib().ezpz_system_tolerance_mc_factorial(*args, *(_ptr(a) for a in out))
-            if rc != 0:
-                raise NonLinearSystemError(rc)
-            return McResult(stats, totals, counts, kept if keep else None, factorial=McFactorial(*out, dims=dims, stats=stats))
-        if not contributors:
-            rc = lib().ezpz_system_tolerance_mc(*args)
-            if rc != 0:
-                raise NonLinearSystemError(rc)
-            return McResult(stats, totals, counts, kept if keep else None)
-        cc = _contrib_config(pivot_rel)
-        moments, info, out = _contrib_outputs(n_param, k)
-        rc = lib().ezpz_system_tolerance_mc_contrib(*args, C.byref(cc), moments.ctypes.data, info.ctypes.data, *(_ptr(a) for a in out))
+        outputs = kind.outputs()
+        rc = getattr(lib(), kind.entry)(*args, *(_mc_arg(a) for a in (*kind.inputs, *outputs)))
         if rc != 0:
             raise NonLinearSystemError(rc)
-        n_complete = int(info["n_complete"][0]) if samples else 0
-        return McResult(stats, totals, counts, kept if keep else None, McContributors(moments, n_complete, n_param, k, *out))
+        return McResult(stats, totals, counts, kept if keep else None, **kind.result(stats, *outputs))
 
     def tolerance_mc_device(self, x0_ptr: int, positions, dists, records, samples: int, stats_ptr: int, totals_ptr: int, hist_ptr: int = 0,
                             seed: int = 0, nominal=None, limits=None, hist=None, chunk: int = 0, keep_params_ptr: int = 0,
@@ -1330,42 +1297,21 @@ class System:
         factorial_info_ptr (MC_FACTORIAL_DTYPE [n_meas]), factorial_main_ptr, factorial_ss_total_ptr, factorial_first_ptr and
         factorial_total_ptr [n_meas, kc], factorial_pair_ptr [n_meas, kc, kc], factorial_ss_order_ptr [n_meas, kc + 1] and, where
         given, factorial_coef_ptr [n_meas, 2^kc]; it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given."""
-        if quantiles is not None and moments_ptr:
-            raise ValueError("quantiles together with contributors: run them one after the other")
-        if effects is not None and (quantiles is not None or moments_ptr):
-            raise ValueError("effects together with contributors or quantiles: run them one after the other")
-        if factorial and (quantiles is not None or moments_ptr or effects is not None):
-            raise ValueError("factorial together with contributors, quantiles or effects: run them one after the other")
+        given = locals()  # (the keywords by name: a kind names the ones that hold its outputs)
+        kind = _mc_kind(bool(moments_ptr), quantiles, effects, factorial)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
+        kind = kind(self, pos, d, nominal, len(recs), int(samples), pivot_rel=pivot_rel, quantiles=quantiles, quantile_z=quantile_z,
+                    effects=effects)
         args = (self._h, x0_ptr or None, _ptr(pos), len(pos), _ptr(d), _ptr(nominal), _ptr(recs), len(recs), _ptr(lim_lo), _ptr(lim_hi), _ptr(hist_lo),
                 _ptr(hist_hi), int(samples), C.byref(mc), C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
                 keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None)
-        if quantiles is not None:
-            probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
-            qc = CMcQuantileConfig(float(quantile_z), 0)
-            rc = lib().ezpz_system_tolerance_mc_quantiles_device(*args, _ptr(probs), len(probs), C.byref(qc), quantiles_ptr or None, stream or None)
-        elif effects is not None:
-            ec, edges, _ = _effects_request(effects, d, pos, nominal, self)
-            rc = lib().ezpz_system_tolerance_mc_effects_device(*args, C.byref(ec), _ptr(edges), effect_sums_ptr or None, effect_counts_ptr or None,
-                                                               cond_mean_ptr or None, cond_var_ptr or None, eta2_ptr or None, first_ptr or None,
-                                                               bins_used_ptr or None, stream or None)
-            if rc != 0:
-                raise NonLinearSystemError(rc)
-            return edges
-        elif factorial:
-            rc = lib().ezpz_system_tolerance_mc_factorial_device(*args, *(p or None for p in (
-                factorial_info_ptr, factorial_main_ptr, factorial_pair_ptr, factorial_ss_order_ptr, factorial_ss_total_ptr,
-                factorial_first_ptr, factorial_total_ptr, factorial_coef_ptr)), stream or None)
-        elif moments_ptr:
-            cc = _contrib_config(pivot_rel)
-            rc = lib().ezpz_system_tolerance_mc_contrib_device(*args, C.byref(cc), moments_ptr, info_ptr or None, cov_ptr or None, beta_ptr or None,
-                                                               contrib_ptr or None, r2_ptr or None, dropped_ptr or None, stream or None)
-        else:
-            rc = lib().ezpz_system_tolerance_mc_device(*args, stream or None)
+        rc = getattr(lib(), kind.entry + "_device")(*args, *(_mc_arg(a) for a in kind.inputs), *(given[name] or None for name in kind.device_outputs),
+                                                    stream or None)
         if rc != 0:
             raise NonLinearSystemError(rc)
+        return kind.device_returns
 
     # ---- Sobol tolerance indices (ezpz_system_tolerance_sobol) ------------------------------------------------------------------------
     def tolerance_sobol(self, x0, positions, dists, records, samples: int, seed: int = 0, seed_b: Optional[int] = None, chunk: int = 0,
@@ -1637,6 +1583,103 @@ def mc_sample(seed: int, dists, nominal, first: int, count: int) -> np.ndarray:
     if rc != 0:
         raise NonLinearSystemError(rc)
     return out
+
+
+def _mc_kind(contributors, quantiles, effects, factorial):
+    """The class of the one kind of a `tolerance_mc` run: the kinds exclude one another."""
+    if quantiles is not None and contributors:
+        raise ValueError("quantiles together with contributors: run them one after the other")
+    if effects is not None and (contributors or quantiles is not None):
+        raise ValueError("effects together with contributors or quantiles: run them one after the other")
+    if factorial and (contributors or quantiles is not None or effects is not None):
+        raise ValueError("factorial together with contributors, quantiles or effects: run them one after the other")
+    return (_McQuantiles if quantiles is not None else _McEffectsKind if effects is not None else _McFactorialKind if factorial
+            else _McContrib if contributors else _McPlain)
+
+
+class _McPlain:
+    """A kind of `tolerance_mc` run, made from the checked request and the caller's settings.  entry: the host entry's name (the
+    device form's has "_device" behind it); inputs: the entry's arguments between the common ones and its outputs; device_outputs:
+    the keywords of `tolerance_mc_device` that hold its outputs, in the entry's order, and device_returns: what that form returns;
+    outputs(): the host form's output arrays, in the same order; result(stats, *outputs): what they add to `McResult`'s keywords."""
+    entry, inputs, device_outputs, device_returns = "ezpz_system_tolerance_mc", (), (), None
+
+    def __init__(self, system, pos, d, nominal, n_meas, samples, **settings):
+        self.n_param, self.n_meas, self.samples = len(pos), n_meas, samples
+
+    def outputs(self):
+        return ()
+
+    def result(self, stats):
+        return {}
+
+
+class _McContrib(_McPlain):
+    entry = "ezpz_system_tolerance_mc_contrib"
+    device_outputs = ("moments_ptr", "info_ptr", "cov_ptr", "beta_ptr", "contrib_ptr", "r2_ptr", "dropped_ptr")
+
+    def __init__(self, *request, pivot_rel, **settings):
+        super().__init__(*request)
+        self.inputs = (C.byref(_contrib_config(pivot_rel)),)
+
+    def outputs(self):
+        moments, info, out = _contrib_outputs(self.n_param, self.n_meas)
+        return (moments, info, *out)
+
+    def result(self, stats, moments, info, *out):
+        n_complete = int(info["n_complete"][0]) if self.samples else 0
+        return dict(contributors=McContributors(moments, n_complete, self.n_param, self.n_meas, *out))
+
+
+class _McQuantiles(_McPlain):
+    entry, device_outputs = "ezpz_system_tolerance_mc_quantiles", ("quantiles_ptr",)
+
+    def __init__(self, *request, quantiles, quantile_z, **settings):
+        super().__init__(*request)
+        probs = np.ascontiguousarray(quantiles, dtype=np.float64).reshape(-1)
+        self.inputs = (probs, len(probs), C.byref(CMcQuantileConfig(float(quantile_z), 0)))
+
+    def outputs(self):
+        return (np.zeros((self.n_meas, self.inputs[1]), dtype=MC_QUANTILE_DTYPE),)
+
+    def result(self, stats, out):
+        return dict(quantiles=out)
+
+
+class _McEffectsKind(_McPlain):
+    entry = "ezpz_system_tolerance_mc_effects"
+    device_outputs = ("effect_sums_ptr", "effect_counts_ptr", "cond_mean_ptr", "cond_var_ptr", "eta2_ptr", "first_ptr", "bins_used_ptr")
+
+    def __init__(self, system, pos, d, nominal, *request, effects, **settings):
+        super().__init__(system, pos, d, nominal, *request)
+        self.ec, self.edges, self.bounds = _effects_request(effects, d, pos, nominal, system)
+        self.inputs, self.device_returns = (C.byref(self.ec), self.edges), self.edges  # (the device form returns the edges used)
+
+    def outputs(self):
+        sums, cnt, out = _effect_outputs(self.n_param, self.n_meas, self.ec.bins)
+        return (sums, cnt, *out)
+
+    def result(self, stats, sums, cnt, *out):
+        return dict(effects=McEffects(sums, cnt, stats["nominal"].copy(), self.edges, *out, bounds=self.bounds))
+
+
+class _McFactorialKind(_McPlain):
+    entry = "ezpz_system_tolerance_mc_factorial"
+    device_outputs = tuple("factorial_%s_ptr" % name for name in ("info", "main", "pair", "ss_order", "ss_total", "first", "total", "coef"))
+
+    def __init__(self, system, pos, d, *request, keep_coef=False, **settings):
+        super().__init__(system, pos, d, *request)
+        self.dims, self.keep_coef = _corner_dims(d), keep_coef
+
+    def outputs(self):
+        return _factorial_outputs(len(self.dims), self.n_meas, self.keep_coef)
+
+    def result(self, stats, *out):
+        return dict(factorial=McFactorial(*out, dims=self.dims, stats=stats))
+
+
+def _mc_arg(a):
+    return _ptr(a) if a is None or isinstance(a, np.ndarray) else a
 
 
 class McResult:

@@ -15,17 +15,7 @@ namespace mce {
 static_assert(sizeof(EzpzMcEffectConfig) == 8, "the layout include/ezpz_amd.h documents");
 static_assert(kMaxBins <= 256, "a bin is staged as a byte");
 
-int EffectWork::ensure(uint64_t blocks, uint32_t cells) {
-    int rc;
-    if ((rc = part.ensure(blocks * cells * 2)) != EZPZ_OK || (rc = part_n.ensure(blocks * cells)) != EZPZ_OK) return rc;
-    if (!ticket.p) {
-        if ((rc = ticket.ensure(1)) != EZPZ_OK) return rc;
-        HIP_TRY(hipMemset(ticket.p, 0, ticket.cap * sizeof(unsigned int)));
-    }
-    return EZPZ_OK;
-}
-
-int enqueue_effects(EffectWork& work, EffectArgs a, hipStream_t stream) {
+int enqueue_effects(mcb::Work& work, EffectArgs a, hipStream_t stream) {
     a.part = work.part.p;
     a.part_n = work.part_n.p;
     a.ticket = work.ticket.p;
@@ -53,19 +43,11 @@ int enqueue_close(const CloseArgs& a, hipStream_t stream) {
 }  // namespace mce
 }  // namespace ezpz
 
-namespace {
-
 using namespace ezpz::mce;
 
-// ezpz_mc_effects_device has no system: its workspace is the process's, one per device (system.hpp: plan_of_device) -- a sibling of
-// ezpz_mc_sobol_sums_device's plan
-struct EffectPlan {
-    std::mutex mu;      // a call holds it from its first allocation to its last enqueue
-    LaunchOrder order;  // the completion of the last call's launches
-    EffectWork work;
-};
-
-}  // namespace
+namespace {
+struct EffectWork : mcb::Work {};  // (a type of its own: the process keeps a plan per type)
+}
 
 extern "C" {
 
@@ -94,34 +76,25 @@ int ezpz_mc_effects_device(const double* params_dev, const double* m_dev, const 
     if (samples == 0) return EZPZ_OK;
     const uint64_t chunk = round_chunk(chunk_in ? chunk_in : kDefaultSampleChunk, samples, kBlock);
     hipStream_t stream = (hipStream_t)stream_;
-    EffectPlan* P = nullptr;
-    int device = -1;
-    if (int rc = plan_of_device(P, device)) return rc;
-    std::lock_guard<std::mutex> lock(P->mu);
     const uint32_t k = (uint32_t)n_param, m = (uint32_t)n_meas, cells = k * bins * m;
-    int rc;
-    if (P->work.grows(chunk / kBlock, cells)) {
-        if ((rc = P->order.before_overwrite()) != EZPZ_OK || (rc = P->work.ensure(chunk / kBlock, cells)) != EZPZ_OK) return rc;
-        call_stamp(EFFECTS_WORKSPACE_GROWN);
-    }
-    if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    EffectArgs a{};
-    a.nominal_m = nominal_m_dev;
-    a.edges = edges_dev;
-    a.k = k, a.n_meas = m, a.bins = bins;
-    a.sums = sums_dev;
-    a.counts = counts_dev;
-    for (uint64_t first = 0; first < samples; first += chunk) {
-        a.params = params_dev + first * k;
-        a.m = m_dev + first * m;
-        a.flags = flags_dev ? flags_dev + first * m : nullptr;
-        a.ok = ok_dev ? ok_dev + first : nullptr;
-        a.count = std::min<uint64_t>(chunk, samples - first);
-        a.first_round = first == 0;
-        if ((rc = enqueue_effects(P->work, a, stream)) != EZPZ_OK) return rc;
-    }
-    call_stamp(EFFECTS_LAUNCHED);
-    return P->order.record(stream);
+    return mcb::on_process_plan<EffectWork>(stream, EFFECTS_WORKSPACE_GROWN, EFFECTS_LAUNCHED, [&](mcb::ProcessPlan<EffectWork>& P) {
+        EffectArgs a{};
+        a.nominal_m = nominal_m_dev;
+        a.edges = edges_dev;
+        a.k = k, a.n_meas = m, a.bins = bins;
+        a.sums = sums_dev;
+        a.counts = counts_dev;
+        for (uint64_t first = 0; first < samples; first += chunk) {
+            a.params = params_dev + first * k;
+            a.m = m_dev + first * m;
+            a.flags = flags_dev ? flags_dev + first * m : nullptr;
+            a.ok = ok_dev ? ok_dev + first : nullptr;
+            a.count = std::min<uint64_t>(chunk, samples - first);
+            a.first_round = first == 0;
+            if (int rc = enqueue_effects(P.work, a, stream)) return rc;
+        }
+        return (int)EZPZ_OK;
+    }, chunk / kBlock * cells * 2, chunk / kBlock * cells);
 }
 
 }  // extern "C"

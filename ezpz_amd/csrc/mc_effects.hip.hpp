@@ -15,9 +15,7 @@
 #include <vector>
 
 #include "../../include/ezpz_amd.h"
-#ifndef EZPZ_MCE_HOST_ONLY  // (a host-only user takes the closing step and the host reduction alone: tools/asan_effects.cpp)
-#include "system.hpp"
-#endif
+#include "mc_block_sum.hip.hpp"  // (a host-only user, EZPZ_MCE_HOST_ONLY, takes the closing step and the host reduction alone: tools/asan_effects.cpp)
 
 namespace ezpz {
 namespace mce {
@@ -27,7 +25,7 @@ namespace mce {
 constexpr uint32_t kMaxDim = 32;  // k and m
 constexpr uint32_t kMaxBins = EZPZ_MC_EFFECT_MAX_BINS;
 constexpr uint32_t kMaxCells = EZPZ_MC_EFFECT_MAX_CELLS;
-constexpr uint32_t kBlock = 256;  // samples per block of the sums: fixed by the interface
+using mcb::kBlock;  // samples per block of the sums
 
 // Cell (j, c, i) -- dimension, bin, record -- is number e = (j * B + c) * m + i: sums [k][B][m][2], counts [k][B][m].
 EZPZ_MCE_HD uint32_t cell_at(uint32_t B, uint32_t m, uint32_t j, uint32_t c, uint32_t i) { return (j * B + c) * m + i; }
@@ -49,11 +47,6 @@ EZPZ_MCE_HD uint32_t bin_of(const double* edges, uint32_t n_edges, double p) {
     for (uint32_t e = 0; e < n_edges; ++e) bin += edges[e] <= p ? 1u : 0u;
     return bin;
 }
-
-struct OneCaller {  // the host entry
-    EZPZ_MCE_HD uint32_t id() const { return 0; }
-    EZPZ_MCE_HD uint32_t count() const { return 1; }
-};
 
 // ---- the closing step ------------------------------------------------------------------------------------------------------------
 // Elements are dealt out by the caller's id: first the k B m cells (cond_mean, cond_var), then the m k pairs (eta2, first,
@@ -137,14 +130,8 @@ inline int indices_host(const double* sums, const uint64_t* counts, const double
                         double* cond_mean, double* cond_var, double* eta2, double* first, uint32_t* bins_used) {
     if (int rc = check_shape(n_param, n_meas, bins)) return rc;
     if (!sums || !counts || !nominal_m || !cond_mean || !cond_var || !eta2 || !first || !bins_used) return EZPZ_ERR_INVALID_ARGUMENT;
-    indices(OneCaller{}, sums, counts, nominal_m, (uint32_t)n_param, (uint32_t)n_meas, bins, cond_mean, cond_var, eta2, first, bins_used);
+    indices(mcb::OneCaller{}, sums, counts, nominal_m, (uint32_t)n_param, (uint32_t)n_meas, bins, cond_mean, cond_var, eta2, first, bins_used);
     return EZPZ_OK;
-}
-
-inline double pair_tree_256(double* v) {
-    for (uint32_t h = 1; h < kBlock; h *= 2)
-        for (uint32_t t = 0; t < kBlock; t += 2 * h) v[t] = v[t] + v[t + h];
-    return v[0];
 }
 
 inline int effects_host(const double* params, const double* m_in, const uint8_t* flags, const uint8_t* ok, const double* nominal_m,
@@ -184,8 +171,8 @@ inline int effects_host(const double* params, const double* m_in, const uint8_t*
                         n += hit;
                     }
                     const uint32_t at = cell_at(B, m, j, c, i);
-                    sums[2 * at] = sums[2 * at] + pair_tree_256(leaves.data());
-                    sums[2 * at + 1] = sums[2 * at + 1] + pair_tree_256(leaves.data() + kBlock);
+                    sums[2 * at] = sums[2 * at] + mcb::pair_tree_256(leaves.data());
+                    sums[2 * at + 1] = sums[2 * at + 1] + mcb::pair_tree_256(leaves.data() + kBlock);
                     counts[at] += n;
                 }
     }
@@ -221,13 +208,8 @@ struct CloseArgs {  // mc_effects_close_kernel: the closing step's, on the sums 
 };
 
 #ifdef EZPZ_MCE_KERNELS  // (mc_effects.hip alone: the kernels have one home; the run of tolerance_mc.hip takes the host side below)
-struct WorkgroupCallers {
-    __device__ inline uint32_t id() const { return threadIdx.x; }
-    __device__ inline uint32_t count() const { return blockDim.x; }
-};
-
 __global__ __launch_bounds__(256) void mc_effects_close_kernel(CloseArgs a) {
-    indices(WorkgroupCallers{}, a.sums, a.counts, a.nominal_m, a.k, a.m, a.bins, a.cond_mean, a.cond_var, a.eta2, a.first, a.bins_used);
+    indices(mcb::WorkgroupCallers{}, a.sums, a.counts, a.nominal_m, a.k, a.m, a.bins, a.cond_mean, a.cond_var, a.eta2, a.first, a.bins_used);
 }
 
 // ---- a round's cells ---------------------------------------------------------------------------------------------------------------
@@ -250,67 +232,20 @@ struct Cell {
     const uint8_t* bin;    // the dimension's column of the staged bins
     const uint32_t* bad;   // the validity words
     uint32_t m, k, c, bit;
+    uint32_t n;            // the samples counted so far
+    __device__ inline Pair operator()(uint32_t s) {
+        const bool hit = bin[s * k] == c && !(bad[s] & bit);
+        const double v = d[s * m];
+        n += hit ? 1u : 0u;
+        return Pair{hit ? v : 0.0, hit ? v * v : 0.0};
+    }
 };
-
-__device__ inline Pair leaves_of(const Cell& u, uint32_t s, uint32_t& n) {
-    const bool hit = u.bin[s * u.k] == u.c && !(u.bad[s] & u.bit);
-    const double v = u.d[s * u.m];
-    n += hit ? 1u : 0u;
-    return Pair{hit ? v : 0.0, hit ? v * v : 0.0};
-}
-
-template <int N>
-__device__ inline Pair pair_sum(const Cell& u, uint32_t s, uint32_t& n) {
-    if constexpr (N == 1) {
-        return leaves_of(u, s, n);
-    } else {
-        const Pair left = pair_sum<N / 2>(u, s, n);
-        return left + pair_sum<N / 2>(u, s + N / 2, n);
-    }
-}
-
-// the adjacent-pair tree over the block's 256 samples: the 32 eights through the binary counter (l0 .. l4: the pending sums of 8,
-// 16, 32, 64 and 128 leaves)
-__device__ inline Pair block_sum(const Cell& u, uint32_t& n) {
-    Pair l0{}, l1{}, l2{}, l3{}, l4{}, out{};
-#pragma unroll 1
-    for (uint32_t g = 0; g < kBlock / 8; ++g) {
-        Pair v = pair_sum<8>(u, 8 * g, n);
-        if (!(g & 1u)) {
-            l0 = v;
-            continue;
-        }
-        v = l0 + v;
-        if (!(g & 2u)) {
-            l1 = v;
-            continue;
-        }
-        v = l1 + v;
-        if (!(g & 4u)) {
-            l2 = v;
-            continue;
-        }
-        v = l2 + v;
-        if (!(g & 8u)) {
-            l3 = v;
-            continue;
-        }
-        v = l3 + v;
-        if (!(g & 16u)) {
-            l4 = v;
-            continue;
-        }
-        out = l4 + v;
-    }
-    return out;
-}
 
 inline size_t effects_lds_bytes(uint32_t k, uint32_t m) { return (size_t)kBlock * m * sizeof(double) + (size_t)kBlock * k; }
 
 __global__ __launch_bounds__(256) void mc_effects_kernel(EffectArgs a) {
     extern __shared__ double s_stage[];  // d [256][m] | bins [256][k] bytes
     __shared__ uint32_t s_bad[kBlock];
-    __shared__ uint32_t s_last;
     const uint32_t t = threadIdx.x, q = blockIdx.x, k = a.k, m = a.n_meas, B = a.bins, cells = k * B * m;
     double* s_d = s_stage;
     uint8_t* s_bin = reinterpret_cast<uint8_t*>(s_d + (size_t)kBlock * m);
@@ -338,27 +273,14 @@ __global__ __launch_bounds__(256) void mc_effects_kernel(EffectArgs a) {
     uint32_t* part_n = a.part_n + (uint64_t)q * cells;
     for (uint32_t e = t; e < cells; e += 256) {
         const uint32_t j = e / (B * m), rest = e - j * (B * m), c = rest / m, i = rest - c * m;
-        const Cell u{s_d + i, s_bin + j, s_bad, m, k, c, 1u << i};
-        uint32_t n = 0;
-        const Pair v = block_sum(u, n);
+        Cell u{s_d + i, s_bin + j, s_bad, m, k, c, 1u << i, 0};
+        const Pair v = mcb::tree_sum<Pair>(u, 0, kBlock / 8);
         part[2 * e] = v.a, part[2 * e + 1] = v.b;
-        part_n[e] = n;
+        part_n[e] = u.n;
     }
-    // the partials are out before the ticket is drawn; whoever draws the last one sees every block's
-    __threadfence();
-    __syncthreads();
-    if (t == 0) s_last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
+    if (!mcb::last_block(a.ticket)) return;
     const uint32_t blocks = gridDim.x;
-    for (uint32_t e = t; e < 2 * cells; e += 256) {
-        double sum = a.first_round ? 0.0 : a.sums[e];
-        // (the sums depend on each other, the loads do not: unrolled, several blocks' partials are in flight at once)
-#pragma unroll 8
-        for (uint32_t b = 0; b < blocks; ++b) sum += a.part[(uint64_t)b * cells * 2 + e];
-        a.sums[e] = sum;
-    }
+    mcb::fold_partials(a.part, 2 * cells, a.first_round, a.sums);
     for (uint32_t e = t; e < cells; e += 256) {
         uint64_t n = a.first_round ? 0 : a.counts[e];
 #pragma unroll 8
@@ -371,17 +293,9 @@ __global__ __launch_bounds__(256) void mc_effects_kernel(EffectArgs a) {
 #endif  // EZPZ_MCE_KERNELS
 
 // ---- the host side (mc_effects.hip), shared with the run of tolerance_mc.hip -------------------------------------------------------
-// The reduction's workspace: whoever owns one orders the launches that use it (a LaunchOrder beside it) and waits for them before
-// it grows.
-struct EffectWork {
-    DevBuf<double> part;
-    DevBuf<uint32_t> part_n;
-    DevBuf<unsigned int> ticket;
-    bool grows(uint64_t blocks, uint32_t cells) const { return blocks * cells * 2 > part.cap || blocks * cells > part_n.cap || !ticket.p; }
-    int ensure(uint64_t blocks, uint32_t cells);
-};
-// one round: `a` with the samples' arrays, the edges, count, k, n_meas, bins, first_round, sums and counts set
-int enqueue_effects(EffectWork& work, EffectArgs a, hipStream_t stream);
+// one round: `a` with the samples' arrays, the edges, count, k, n_meas, bins, first_round, sums and counts set; the workspace holds
+// blocks * cells * 2 partials and blocks * cells counts
+int enqueue_effects(mcb::Work& work, EffectArgs a, hipStream_t stream);
 int enqueue_close(const CloseArgs& a, hipStream_t stream);
 
 #endif  // __HIPCC__ && !EZPZ_MCE_HOST_ONLY

@@ -62,20 +62,7 @@ int enqueue_factorial(FactorialWork& work, const double* m, const uint8_t* flags
 }  // namespace mcf
 }  // namespace ezpz
 
-namespace {
-
 using namespace ezpz::mcf;
-
-// ezpz_mc_factorial_device has no system: its workspace is the process's, one per device (system.hpp: plan_of_device) -- a sibling of
-// ezpz_mc_quantiles_device's plan
-struct FactorialPlan {
-    std::mutex mu;      // a call holds it from its first allocation to its last enqueue
-    LaunchOrder order;  // the completion of the last call's launches
-    FactorialWork work;
-    uint32_t cus = 0;
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -92,29 +79,15 @@ int ezpz_mc_factorial_device(const double* m_dev, const uint8_t* flags_dev, cons
     if (int rc = check(n_corner, n_meas, m_dev, nominal_m_dev, info_dev, main_dev, pair_dev, ss_order_dev, ss_total_dev, first_dev, total_dev))
         return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    FactorialPlan* P = nullptr;
-    int device = -1;
-    if (int rc = plan_of_device(P, device)) return rc;
-    std::lock_guard<std::mutex> lock(P->mu);
-    int rc;
-    if (!P->cus) {
-        int cus = 0;
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        P->cus = (uint32_t)std::max(cus, 1);
-    }
-    if (P->work.grows((uint32_t)n_meas, n_corner)) {
-        if ((rc = P->order.before_overwrite()) != EZPZ_OK || (rc = P->work.ensure((uint32_t)n_meas, n_corner)) != EZPZ_OK) return rc;
-        call_stamp(FACTORIAL_WORKSPACE_GROWN);
-    }
-    if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    FactorialOut out;
-    out.info = info_dev;
-    out.main = main_dev, out.pair = pair_dev, out.ss_order = ss_order_dev, out.ss_total = ss_total_dev, out.first = first_dev;
-    out.total = total_dev, out.coef = coef_dev;
-    if ((rc = enqueue_factorial(P->work, m_dev, flags_dev, ok_dev, nominal_m_dev, n_corner, (uint32_t)n_meas, out, P->cus, stream)) != EZPZ_OK)
-        return rc;
-    call_stamp(FACTORIAL_LAUNCHED);
-    return P->order.record(stream);
+    return mcb::on_process_plan<FactorialWork>(stream, FACTORIAL_WORKSPACE_GROWN, FACTORIAL_LAUNCHED, [&](mcb::ProcessPlan<FactorialWork>& P) {
+        uint32_t cus = 0;
+        if (int rc = P.units(cus)) return rc;
+        FactorialOut out;
+        out.info = info_dev;
+        out.main = main_dev, out.pair = pair_dev, out.ss_order = ss_order_dev, out.ss_total = ss_total_dev, out.first = first_dev;
+        out.total = total_dev, out.coef = coef_dev;
+        return enqueue_factorial(P.work, m_dev, flags_dev, ok_dev, nominal_m_dev, n_corner, (uint32_t)n_meas, out, cus, stream);
+    }, (uint32_t)n_meas, n_corner);
 }
 
 }  // extern "C"

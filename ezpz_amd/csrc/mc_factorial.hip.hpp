@@ -17,9 +17,7 @@
 #include <vector>
 
 #include "../../include/ezpz_amd.h"
-#ifndef EZPZ_MCF_HOST_ONLY  // (a host-only user takes the closing body and the host form alone: tools/asan_factorial.cpp)
-#include "system.hpp"
-#endif
+#include "mc_block_sum.hip.hpp"  // (a host-only user, EZPZ_MCF_HOST_ONLY, takes the closing body and the host form alone: tools/asan_factorial.cpp)
 
 namespace ezpz {
 namespace mcf {
@@ -28,7 +26,7 @@ namespace mcf {
 
 constexpr uint32_t kMaxCorners = EZPZ_MC_FACTORIAL_MAX_CORNERS;
 constexpr uint32_t kMaxMeas = EZPZ_MC_FACTORIAL_MAX_MEAS;
-constexpr uint32_t kBlock = 256;                     // leaves per block of the sums: fixed by the interface
+using mcb::kBlock;                                   // leaves per block of the sums
 constexpr uint32_t kMaxSums = 2 * kMaxCorners + 1;  // ss_order [kc + 1] | ss_total [kc]
 
 EZPZ_MCF_HD double quiet_nan() {
@@ -103,12 +101,6 @@ inline int check(uint32_t n_corner, size_t n_meas, const void* m, const void* no
     return EZPZ_OK;
 }
 
-inline double pair_tree_256(double* v) {
-    for (uint32_t h = 1; h < kBlock; h *= 2)
-        for (uint32_t t = 0; t < kBlock; t += 2 * h) v[t] = v[t] + v[t + h];
-    return v[0];
-}
-
 // ---- the host form, whole: ezpz_mc_factorial forwards to it (tools/asan_factorial.cpp drives it) --------------------------------------
 inline int factorial_host(const double* m, const uint8_t* flags, const uint8_t* ok, const double* nominal_m, uint32_t n_corner, size_t n_meas,
                           EzpzMcFactorial* info, double* main, double* pair, double* ss_order, double* ss_total, double* first, double* total,
@@ -159,7 +151,7 @@ inline int factorial_host(const double* m, const uint8_t* flags, const uint8_t* 
                     const size_t S = first_S + t;
                     leaves[t] = S < N && in_class((uint32_t)S, k, kc) ? w[S] * w[S] : 0.0;
                 }
-                sum = sum + pair_tree_256(leaves.data());
+                sum = sum + mcb::pair_tree_256(leaves.data());
             }
             (k <= kc ? so[k] : st[k - kc - 1]) = sum;
         }

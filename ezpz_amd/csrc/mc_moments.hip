@@ -12,17 +12,7 @@ namespace mcm {
 
 static_assert(sizeof(EzpzMcContribConfig) == 16 && sizeof(EzpzMcMomentsInfo) == 16, "the layouts include/ezpz_amd.h documents");
 
-int MomentWork::ensure(uint64_t blocks, uint32_t K) {
-    int rc;
-    if ((rc = part.ensure(blocks * entries_of(K))) != EZPZ_OK || (rc = part_n.ensure(blocks)) != EZPZ_OK) return rc;
-    if (!ticket.p) {
-        if ((rc = ticket.ensure(1)) != EZPZ_OK) return rc;
-        HIP_TRY(hipMemset(ticket.p, 0, ticket.cap * sizeof(unsigned int)));
-    }
-    return EZPZ_OK;
-}
-
-int enqueue_moments(MomentWork& work, MomentArgs a, hipStream_t stream) {
+int enqueue_moments(mcb::Work& work, MomentArgs a, hipStream_t stream) {
     a.part = work.part.p;
     a.part_n = work.part_n.p;
     a.ticket = work.ticket.p;
@@ -48,16 +38,14 @@ using namespace ezpz::mcm;
 
 constexpr uint64_t kBlock = 256;
 
-// ezpz_mc_moments has no system: its workspace is the process's, one per device (system.hpp: plan_of_device)
-struct MomentPlan {
-    std::mutex mu;  // a call holds it from its first allocation to its last enqueue
-    LaunchOrder order;  // the completion of the last call's launches
-    MomentWork work;
-    // the host form's buffers: a round of the samples, the nominals, the outputs
+// ezpz_mc_moments has no system: its workspace is the process's (mcb::ProcessPlan), with the host form's buffers beside the sums'
+struct MomentWork : mcb::Work {
+    // a round of the samples, the nominals, the outputs
     DevBuf<double> params, m, nominal, moments_out;
     DevBuf<uint8_t> flags, ok;
     DevBuf<EzpzMcMomentsInfo> info_out;
 };
+using MomentPlan = mcb::ProcessPlan<MomentWork>;
 
 // Every argument error of the reduction alone, before anything is enqueued or written; the pointers are only compared with NULL.
 int check_moments(const void* params, const void* m, const void* nominal_p, const void* nominal_m, uint64_t samples, size_t n_param,
@@ -66,14 +54,6 @@ int check_moments(const void* params, const void* m, const void* nominal_p, cons
     if (samples && (!moments || !info || (n_param && (!params || !nominal_p)) || (n_meas && (!m || !nominal_m)))) return EZPZ_ERR_INVALID_ARGUMENT;
     if (samples > 0xFFFFFFFFFFFFull) return EZPZ_ERR_TOO_LARGE;
     chunk = round_chunk(chunk_in ? chunk_in : kDefaultSampleChunk, samples, kBlock);
-    return EZPZ_OK;
-}
-
-int grow(MomentPlan& P, uint64_t chunk, uint32_t K) {
-    if (!P.work.grows(chunk / kBlock, K)) return EZPZ_OK;
-    int rc;
-    if ((rc = P.order.before_overwrite()) != EZPZ_OK || (rc = P.work.ensure(chunk / kBlock, K)) != EZPZ_OK) return rc;
-    call_stamp(MOMENTS_WORKSPACE_GROWN);
     return EZPZ_OK;
 }
 
@@ -111,25 +91,21 @@ int ezpz_mc_moments_device(const double* params_dev, const double* m_dev, const 
         return rc;
     if (samples == 0) return EZPZ_OK;
     hipStream_t stream = (hipStream_t)stream_;
-    MomentPlan* P = nullptr;
-    int device = -1;
-    if (int rc = plan_of_device(P, device)) return rc;
-    std::lock_guard<std::mutex> lock(P->mu);
-    int rc;
-    if ((rc = grow(*P, chunk, (uint32_t)(n_param + n_meas))) != EZPZ_OK || (rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    MomentArgs a = args_of(nominal_p_dev, nominal_m_dev, samples, n_param, n_meas, moments_dev, info_dev);
-    for (uint64_t first = 0; first < samples; first += chunk) {
-        a.params = params_dev + first * n_param;
-        a.m = m_dev + first * n_meas;
-        a.flags = flags_dev ? flags_dev + first * n_meas : nullptr;
-        a.ok = ok_dev ? ok_dev + first : nullptr;
-        a.first = first;
-        a.count = std::min<uint64_t>(chunk, samples - first);
-        a.first_round = first == 0;
-        if ((rc = enqueue_moments(P->work, a, stream)) != EZPZ_OK) return rc;
-    }
-    call_stamp(MOMENTS_LAUNCHED);
-    return P->order.record(stream);
+    const uint64_t blocks = chunk / kBlock;
+    return mcb::on_process_plan<MomentWork>(stream, MOMENTS_WORKSPACE_GROWN, MOMENTS_LAUNCHED, [&](MomentPlan& P) {
+        MomentArgs a = args_of(nominal_p_dev, nominal_m_dev, samples, n_param, n_meas, moments_dev, info_dev);
+        for (uint64_t first = 0; first < samples; first += chunk) {
+            a.params = params_dev + first * n_param;
+            a.m = m_dev + first * n_meas;
+            a.flags = flags_dev ? flags_dev + first * n_meas : nullptr;
+            a.ok = ok_dev ? ok_dev + first : nullptr;
+            a.first = first;
+            a.count = std::min<uint64_t>(chunk, samples - first);
+            a.first_round = first == 0;
+            if (int rc = enqueue_moments(P.work, a, stream)) return rc;
+        }
+        return (int)EZPZ_OK;
+    }, blocks * entries_of((uint32_t)(n_param + n_meas)), blocks);
 }
 
 int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags, const uint8_t* ok, const double* nominal_p,
@@ -146,35 +122,41 @@ int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags,
     const hipStream_t stream = hipStreamPerThread;
     int rc;
     // (the buffers of an earlier host call are idle: it waited for its launches)
-    if ((rc = grow(*P, chunk, K)) != EZPZ_OK || (rc = P->params.ensure(chunk * n_param)) != EZPZ_OK || (rc = P->m.ensure(chunk * n_meas)) != EZPZ_OK ||
-        (rc = P->flags.ensure(flags ? chunk * n_meas : 0)) != EZPZ_OK || (rc = P->ok.ensure(ok ? chunk : 0)) != EZPZ_OK ||
-        (rc = P->nominal.ensure(K)) != EZPZ_OK || (rc = P->moments_out.ensure(entries_of(K))) != EZPZ_OK || (rc = P->info_out.ensure(1)) != EZPZ_OK)
+    MomentWork& W = P->work;
+    const uint64_t blocks = chunk / kBlock;
+    if (W.grows(blocks * entries_of(K), blocks)) {
+        if ((rc = P->order.before_overwrite()) != EZPZ_OK || (rc = W.ensure(blocks * entries_of(K), blocks)) != EZPZ_OK) return rc;
+        call_stamp(MOMENTS_WORKSPACE_GROWN);
+    }
+    if ((rc = W.params.ensure(chunk * n_param)) != EZPZ_OK || (rc = W.m.ensure(chunk * n_meas)) != EZPZ_OK ||
+        (rc = W.flags.ensure(flags ? chunk * n_meas : 0)) != EZPZ_OK || (rc = W.ok.ensure(ok ? chunk : 0)) != EZPZ_OK ||
+        (rc = W.nominal.ensure(K)) != EZPZ_OK || (rc = W.moments_out.ensure(entries_of(K))) != EZPZ_OK || (rc = W.info_out.ensure(1)) != EZPZ_OK)
         return rc;
-    if (n_param) HIP_TRY(hipMemcpy(P->nominal.p, nominal_p, n_param * sizeof(double), hipMemcpyHostToDevice));
-    if (n_meas) HIP_TRY(hipMemcpy(P->nominal.p + n_param, nominal_m, n_meas * sizeof(double), hipMemcpyHostToDevice));
+    if (n_param) HIP_TRY(hipMemcpy(W.nominal.p, nominal_p, n_param * sizeof(double), hipMemcpyHostToDevice));
+    if (n_meas) HIP_TRY(hipMemcpy(W.nominal.p + n_param, nominal_m, n_meas * sizeof(double), hipMemcpyHostToDevice));
     if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    MomentArgs a = args_of(P->nominal.p, P->nominal.p + n_param, samples, n_param, n_meas, P->moments_out.p, P->info_out.p);
-    a.params = P->params.p;
-    a.m = P->m.p;
-    a.flags = flags ? P->flags.p : nullptr;
-    a.ok = ok ? P->ok.p : nullptr;
+    MomentArgs a = args_of(W.nominal.p, W.nominal.p + n_param, samples, n_param, n_meas, W.moments_out.p, W.info_out.p);
+    a.params = W.params.p;
+    a.m = W.m.p;
+    a.flags = flags ? W.flags.p : nullptr;
+    a.ok = ok ? W.ok.p : nullptr;
     for (uint64_t first = 0; first < samples; first += chunk) {
         const uint64_t count = std::min<uint64_t>(chunk, samples - first);
         if (first) HIP_TRY(hipStreamSynchronize(stream));  // (the last round has read the buffers)
-        if (n_param) HIP_TRY(hipMemcpy(P->params.p, params + first * n_param, count * n_param * sizeof(double), hipMemcpyHostToDevice));
-        if (n_meas) HIP_TRY(hipMemcpy(P->m.p, m + first * n_meas, count * n_meas * sizeof(double), hipMemcpyHostToDevice));
-        if (flags && n_meas) HIP_TRY(hipMemcpy(P->flags.p, flags + first * n_meas, count * n_meas, hipMemcpyHostToDevice));
-        if (ok) HIP_TRY(hipMemcpy(P->ok.p, ok + first, count, hipMemcpyHostToDevice));
+        if (n_param) HIP_TRY(hipMemcpy(W.params.p, params + first * n_param, count * n_param * sizeof(double), hipMemcpyHostToDevice));
+        if (n_meas) HIP_TRY(hipMemcpy(W.m.p, m + first * n_meas, count * n_meas * sizeof(double), hipMemcpyHostToDevice));
+        if (flags && n_meas) HIP_TRY(hipMemcpy(W.flags.p, flags + first * n_meas, count * n_meas, hipMemcpyHostToDevice));
+        if (ok) HIP_TRY(hipMemcpy(W.ok.p, ok + first, count, hipMemcpyHostToDevice));
         a.first = first;
         a.count = count;
         a.first_round = first == 0;
-        if ((rc = enqueue_moments(P->work, a, stream)) != EZPZ_OK) return rc;
+        if ((rc = enqueue_moments(W, a, stream)) != EZPZ_OK) return rc;
     }
     call_stamp(MOMENTS_LAUNCHED);
     if ((rc = P->order.record(stream)) != EZPZ_OK) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(moments, P->moments_out.p, entries_of(K) * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(info, P->info_out.p, sizeof(EzpzMcMomentsInfo), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(moments, W.moments_out.p, entries_of(K) * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(info, W.info_out.p, sizeof(EzpzMcMomentsInfo), hipMemcpyDeviceToHost));
     return EZPZ_OK;
 }
 

@@ -13,9 +13,7 @@
 #include <cstring>
 
 #include "../../include/ezpz_amd.h"
-#ifndef EZPZ_MCM_HOST_ONLY  // (a host-only user takes the closing step alone: tools/asan_contrib.cpp)
-#include "system.hpp"
-#endif
+#include "mc_block_sum.hip.hpp"  // (a host-only user, EZPZ_MCM_HOST_ONLY, takes the closing step alone: tools/asan_contrib.cpp)
 
 namespace ezpz {
 namespace mcm {
@@ -39,13 +37,6 @@ EZPZ_MCM_HD double quiet_nan() {
     return v;
 #endif
 }
-
-// ---- the callers of the closing step: who takes which element, and the barrier between its phases ------------------------------
-struct OneCaller {  // the host entry
-    EZPZ_MCM_HD uint32_t id() const { return 0; }
-    EZPZ_MCM_HD uint32_t count() const { return 1; }
-    EZPZ_MCM_HD void sync() const {}
-};
 
 // ---- the closing step ------------------------------------------------------------------------------------------------------------
 // cov [K][K], beta and contrib [m][k], r2 [m], dropped [1]: the outputs.  L [k][k] (the unit lower factor, its strict lower part
@@ -161,7 +152,7 @@ inline int contributors_host(const double* moments, uint64_t n_complete, size_t 
     if (!moments || !cov || !dropped || (n_meas && !r2) || (n_meas && n_param && (!beta || !contrib))) return EZPZ_ERR_INVALID_ARGUMENT;
     double* L = new double[n_param * n_param + n_param + 1];  // the factor | the pivots
     uint8_t* kept = new uint8_t[n_param + 1];
-    contributors(OneCaller{}, moments, n_complete, (uint32_t)n_param, (uint32_t)n_meas, pivot_rel, cov, beta, contrib, r2, dropped, L,
+    contributors(mcb::OneCaller{}, moments, n_complete, (uint32_t)n_param, (uint32_t)n_meas, pivot_rel, cov, beta, contrib, r2, dropped, L,
                  L + n_param * n_param, kept);
     delete[] L;
     delete[] kept;
@@ -196,12 +187,6 @@ struct MomentArgs {  // mc_moments_kernel: one round
 };
 
 #ifdef EZPZ_MCM_KERNELS  // (mc_moments.hip alone: the kernels have one home; the run of tolerance_mc.hip takes the host side below)
-struct WorkgroupCallers {  // mc_contrib_kernel: the 256 threads of its one workgroup
-    __device__ inline uint32_t id() const { return threadIdx.x; }
-    __device__ inline uint32_t count() const { return blockDim.x; }
-    __device__ inline void sync() const { __syncthreads(); }
-};
-
 // The factor and the pivots live in LDS (k <= 64: 32.5 KiB); the covariance and the coefficients are read where they are written,
 // in the caller's arrays.
 __global__ __launch_bounds__(256) void mc_contrib_kernel(ContribArgs a) {
@@ -209,7 +194,7 @@ __global__ __launch_bounds__(256) void mc_contrib_kernel(ContribArgs a) {
     double* L = s_work;
     double* d = L + (size_t)a.k * a.k;
     uint8_t* kept = (uint8_t*)(d + a.k);
-    contributors(WorkgroupCallers{}, a.moments, a.info->n_complete, a.k, a.m, a.pivot_rel, a.cov, a.beta, a.contrib, a.r2, a.dropped, L, d, kept);
+    contributors(mcb::WorkgroupCallers{}, a.moments, a.info->n_complete, a.k, a.m, a.pivot_rel, a.cov, a.beta, a.contrib, a.r2, a.dropped, L, d, kept);
 }
 
 // ---- a round's second-moment sums --------------------------------------------------------------------------------------------------
@@ -235,7 +220,8 @@ __device__ inline double pair_sum(const double* za, const double* zb, uint32_t K
     }
 }
 
-// the tile's 64 leaves of one entry: eight leaves at a time through the binary counter (l0, l1, l2: the pending sums of 8, 16, 32)
+// the tile's 64 leaves of one entry: eight leaves at a time through the binary counter (l0, l1, l2: the pending sums of 8, 16, 32).
+// (mcb::tree_sum is this tree; the kernel keeps its own copy, on which it takes 190 VGPRs for the shared one's 194)
 __device__ inline double tile_sum(const double* za, const double* zb, uint32_t K, bool product) {
     double l0 = 0.0, l1 = 0.0, l2 = 0.0, out = 0.0;
 #pragma unroll 1
@@ -263,7 +249,7 @@ __device__ inline double tile_sum(const double* za, const double* zb, uint32_t K
 __global__ __launch_bounds__(256) void mc_moments_kernel(MomentArgs a) {
     extern __shared__ double s_z[];  // [kTile][K]
     __shared__ uint32_t s_bad[kTile];
-    __shared__ uint32_t s_last, s_complete;
+    __shared__ uint32_t s_complete;
     const uint32_t t = threadIdx.x, q = blockIdx.x, k = a.k, n_meas = a.n_meas, K = k + n_meas, E = entries_of(K);
     // this thread's entries: row ea and column eb of the triangle, or the sum of z[ea] (eb == ea, no product)
     uint32_t ea[kRounds], eb[kRounds];
@@ -325,30 +311,14 @@ __global__ __launch_bounds__(256) void mc_moments_kernel(MomentArgs a) {
 #pragma unroll
     for (uint32_t r = 0; r < kRounds; ++r)
         if (t + 256 * r < E) a.part[(uint64_t)q * E + t + 256 * r] = acc[r];
-    // the partials are out before the ticket is drawn; whoever draws the last one sees every block's
-    __threadfence();
-    __syncthreads();
-    if (t == 0) {
-        a.part_n[q] = s_complete;
-        __threadfence();
-        s_last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    const uint32_t blocks = gridDim.x;
-    for (uint32_t e = t; e < E; e += 256) {
-        double sum = a.first_round ? 0.0 : a.moments[e];
-        // (the sums depend on each other, the loads do not: unrolled, several blocks' partials are in flight at once)
-#pragma unroll 8
-        for (uint32_t b = 0; b < blocks; ++b) sum += a.part[(uint64_t)b * E + e];
-        a.moments[e] = sum;
-    }
+    if (t == 0) a.part_n[q] = s_complete;
+    if (!mcb::last_block(a.ticket)) return;
+    mcb::fold_partials(a.part, E, a.first_round, a.moments);
     if (t == 0) {
         EzpzMcMomentsInfo info;
         info.n_complete = a.first_round ? 0 : a.info->n_complete;
         info.samples = a.samples;
-        for (uint32_t b = 0; b < blocks; ++b) info.n_complete += a.part_n[b];
+        for (uint32_t b = 0; b < gridDim.x; ++b) info.n_complete += a.part_n[b];
         *a.info = info;
         *a.ticket = 0;
     }
@@ -357,17 +327,9 @@ __global__ __launch_bounds__(256) void mc_moments_kernel(MomentArgs a) {
 #endif  // EZPZ_MCM_KERNELS
 
 // ---- the host side (mc_moments.hip), shared with the run of tolerance_mc.hip ---------------------------------------------------------
-// The reduction's workspace: whoever owns one orders the launches that use it (a LaunchOrder beside it) and waits for them before
-// it grows.
-struct MomentWork {
-    DevBuf<double> part;
-    DevBuf<uint32_t> part_n;
-    DevBuf<unsigned int> ticket;
-    bool grows(uint64_t blocks, uint32_t K) const { return blocks * entries_of(K) > part.cap || blocks > part_n.cap || !ticket.p; }
-    int ensure(uint64_t blocks, uint32_t K);
-};
-// one round: `a` with the samples' arrays, first, count, samples, k, n_meas, first_round, moments and info set
-int enqueue_moments(MomentWork& work, MomentArgs a, hipStream_t stream);
+// one round: `a` with the samples' arrays, first, count, samples, k, n_meas, first_round, moments and info set; the workspace holds
+// blocks * entries_of(K) partials and `blocks` counts
+int enqueue_moments(mcb::Work& work, MomentArgs a, hipStream_t stream);
 int enqueue_contributors(const ContribArgs& a, hipStream_t stream);
 
 #endif  // __HIPCC__ && !EZPZ_MCM_HOST_ONLY

@@ -3,6 +3,7 @@
 // ezpz_system_tolerance_mc_quantiles in tolerance_mc.hip) and the selection alone on a caller's rows, on a workspace the process owns
 // per device.
 #define EZPZ_QUANTILES_KERNELS
+#include "mc_block_sum.hip.hpp"
 #include "mc_quantiles.hip.hpp"
 
 using namespace ezpz;
@@ -50,20 +51,7 @@ int enqueue_select(SelectWork& work, const double* m, const uint8_t* flags, cons
 }  // namespace mcq
 }  // namespace ezpz
 
-namespace {
-
 using namespace ezpz::mcq;
-
-// ezpz_mc_quantiles_device has no system: its workspace is the process's, one per device (system.hpp: plan_of_device)
-// -- a sibling of ezpz_mc_sobol_sums_device's plan
-struct SelectPlan {
-    std::mutex mu;      // a call holds it from its first allocation to its last enqueue
-    LaunchOrder order;  // the completion of the last call's launches
-    SelectWork work;
-    uint32_t cus = 0;
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -82,26 +70,11 @@ int ezpz_mc_quantiles_device(const double* m_dev, const uint8_t* flags_dev, cons
     if (int rc = check(samples, n_meas, probs, n_q, qc, m_dev, out_dev, z)) return rc;
     if (samples == 0 || n_q == 0) return EZPZ_OK;
     hipStream_t stream = (hipStream_t)stream_;
-    SelectPlan* P = nullptr;
-    int device = -1;
-    if (int rc = plan_of_device(P, device)) return rc;
-    std::lock_guard<std::mutex> lock(P->mu);
-    int rc;
-    if (!P->cus) {
-        int cus = 0;
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        P->cus = (uint32_t)std::max(cus, 1);
-    }
-    if (P->work.grows((uint32_t)n_meas, (uint32_t)n_q)) {
-        if ((rc = P->order.before_overwrite()) != EZPZ_OK || (rc = P->work.ensure((uint32_t)n_meas, (uint32_t)n_q)) != EZPZ_OK) return rc;
-        call_stamp(QUANTILES_WORKSPACE_GROWN);
-    }
-    if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    if ((rc = enqueue_select(P->work, m_dev, flags_dev, ok_dev, samples, (uint32_t)n_meas, probs, (uint32_t)n_q, z, out_dev, P->cus,
-                             stream)) != EZPZ_OK)
-        return rc;
-    call_stamp(QUANTILES_LAUNCHED);
-    return P->order.record(stream);
+    return mcb::on_process_plan<SelectWork>(stream, QUANTILES_WORKSPACE_GROWN, QUANTILES_LAUNCHED, [&](mcb::ProcessPlan<SelectWork>& P) {
+        uint32_t cus = 0;
+        if (int rc = P.units(cus)) return rc;
+        return enqueue_select(P.work, m_dev, flags_dev, ok_dev, samples, (uint32_t)n_meas, probs, (uint32_t)n_q, z, out_dev, cus, stream);
+    }, (uint32_t)n_meas, (uint32_t)n_q);
 }
 
 }  // extern "C"

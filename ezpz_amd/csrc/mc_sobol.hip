@@ -12,17 +12,7 @@ namespace sobol {
 
 static_assert(sizeof(EzpzSobolConfig) == 16, "the layout include/ezpz_amd.h documents");
 
-int SumWork::ensure(uint64_t blocks, uint32_t k, uint32_t m) {
-    int rc;
-    if ((rc = part.ensure(blocks * m * width_of(k))) != EZPZ_OK || (rc = part_n.ensure(blocks * m)) != EZPZ_OK) return rc;
-    if (!ticket.p) {
-        if ((rc = ticket.ensure(1)) != EZPZ_OK) return rc;
-        HIP_TRY(hipMemset(ticket.p, 0, ticket.cap * sizeof(unsigned int)));
-    }
-    return EZPZ_OK;
-}
-
-int enqueue_sums(SumWork& work, SumArgs a, hipStream_t stream) {
+int enqueue_sums(mcb::Work& work, SumArgs a, hipStream_t stream) {
     a.part = work.part.p;
     a.part_n = work.part_n.p;
     a.ticket = work.ticket.p;
@@ -47,19 +37,11 @@ int enqueue_close(const CloseArgs& a, hipStream_t stream) {
 }  // namespace sobol
 }  // namespace ezpz
 
-namespace {
-
 using namespace ezpz::sobol;
 
-// ezpz_mc_sobol_sums_device has no system: its workspace is the process's, one per device (system.hpp:
-// plan_of_device) -- a sibling of ezpz_mc_moments' plan
-struct SumPlan {
-    std::mutex mu;      // a call holds it from its first allocation to its last enqueue
-    LaunchOrder order;  // the completion of the last call's launches
-    SumWork work;
-};
-
-}  // namespace
+namespace {
+struct SumWork : mcb::Work {};  // (a type of its own: the process keeps a plan per type)
+}
 
 extern "C" {
 
@@ -88,34 +70,25 @@ int ezpz_mc_sobol_sums_device(const double* f_dev, const uint8_t* flags_dev, con
     if (samples == 0) return EZPZ_OK;
     const uint64_t chunk = round_chunk(chunk_in ? chunk_in : kDefaultSampleChunk, samples, kBlock);
     hipStream_t stream = (hipStream_t)stream_;
-    SumPlan* P = nullptr;
-    int device = -1;
-    if (int rc = plan_of_device(P, device)) return rc;
-    std::lock_guard<std::mutex> lock(P->mu);
     const uint32_t k = (uint32_t)n_param, m = (uint32_t)n_meas;
-    int rc;
-    if (P->work.grows(chunk / kBlock, k, m)) {
-        if ((rc = P->order.before_overwrite()) != EZPZ_OK || (rc = P->work.ensure(chunk / kBlock, k, m)) != EZPZ_OK) return rc;
-        call_stamp(SOBOL_WORKSPACE_GROWN);
-    }
-    if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    SumArgs a{};
-    a.nominal_m = nominal_m_dev;
-    a.stride_s = (uint64_t)(k + 2) * m, a.stride_r = m;
-    a.ok_stride_s = k + 2, a.ok_stride_r = 1;
-    a.k = k, a.m = m, a.fixed_mask = fixed_mask;
-    a.sums = sums_dev;
-    a.n_complete = n_complete_dev;
-    for (uint64_t first = 0; first < samples; first += chunk) {
-        a.f = f_dev + first * a.stride_s;
-        a.flags = flags_dev ? flags_dev + first * a.stride_s : nullptr;
-        a.ok = ok_dev ? ok_dev + first * a.ok_stride_s : nullptr;
-        a.count = std::min<uint64_t>(chunk, samples - first);
-        a.first_round = first == 0;
-        if ((rc = enqueue_sums(P->work, a, stream)) != EZPZ_OK) return rc;
-    }
-    call_stamp(SOBOL_LAUNCHED);
-    return P->order.record(stream);
+    return mcb::on_process_plan<SumWork>(stream, SOBOL_WORKSPACE_GROWN, SOBOL_LAUNCHED, [&](mcb::ProcessPlan<SumWork>& P) {
+        SumArgs a{};
+        a.nominal_m = nominal_m_dev;
+        a.stride_s = (uint64_t)(k + 2) * m, a.stride_r = m;
+        a.ok_stride_s = k + 2, a.ok_stride_r = 1;
+        a.k = k, a.m = m, a.fixed_mask = fixed_mask;
+        a.sums = sums_dev;
+        a.n_complete = n_complete_dev;
+        for (uint64_t first = 0; first < samples; first += chunk) {
+            a.f = f_dev + first * a.stride_s;
+            a.flags = flags_dev ? flags_dev + first * a.stride_s : nullptr;
+            a.ok = ok_dev ? ok_dev + first * a.ok_stride_s : nullptr;
+            a.count = std::min<uint64_t>(chunk, samples - first);
+            a.first_round = first == 0;
+            if (int rc = enqueue_sums(P.work, a, stream)) return rc;
+        }
+        return (int)EZPZ_OK;
+    }, chunk / kBlock * m * width_of(k), chunk / kBlock * m);
 }
 
 }  // extern "C"

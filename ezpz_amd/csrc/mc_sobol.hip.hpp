@@ -15,9 +15,7 @@
 #include <vector>
 
 #include "../../include/ezpz_amd.h"
-#ifndef EZPZ_SOBOL_HOST_ONLY  // (a host-only user takes the closing step and the host reduction alone: tools/asan_sobol.cpp)
-#include "system.hpp"
-#endif
+#include "mc_block_sum.hip.hpp"  // (a host-only user, EZPZ_SOBOL_HOST_ONLY, takes the closing step and the host reduction alone: tools/asan_sobol.cpp)
 
 namespace ezpz {
 namespace sobol {
@@ -25,7 +23,7 @@ namespace sobol {
 #define EZPZ_SOBOL_HD __host__ __device__ inline
 
 constexpr uint32_t kMax = EZPZ_SOBOL_MAX;
-constexpr uint32_t kBlock = 256;  // samples per block of the sums: fixed by the interface
+using mcb::kBlock;  // samples per block of the sums
 
 EZPZ_SOBOL_HD uint32_t width_of(uint32_t k) { return 4 + 4 * k; }  // the sums of one record
 // A UNIT is what one lane sums: the pair (record i, dimension j) with its four sums P, Q, P2, Q2 -- or, for j == k, the record's
@@ -45,11 +43,6 @@ EZPZ_SOBOL_HD double quiet_nan() {
     return v;
 #endif
 }
-
-struct OneCaller {  // the host entry
-    EZPZ_SOBOL_HD uint32_t id() const { return 0; }
-    EZPZ_SOBOL_HD uint32_t count() const { return 1; }
-};
 
 // ---- the closing step ------------------------------------------------------------------------------------------------------------
 // Elements are dealt out by the caller's id: element e < m * (k + 1) is var[i] (j == k) or the four indices of (i, j); every caller
@@ -105,14 +98,8 @@ inline int indices_host(const double* sums, const uint64_t* n_complete, size_t n
                         double* total, double* first_var, double* total_var) {
     if (int rc = check_shape(n_param, n_meas)) return rc;
     if (!sums || !n_complete || !var || (n_param && (!first || !total || !first_var || !total_var))) return EZPZ_ERR_INVALID_ARGUMENT;
-    indices(OneCaller{}, sums, n_complete, (uint32_t)n_param, (uint32_t)n_meas, var, first, total, first_var, total_var);
+    indices(mcb::OneCaller{}, sums, n_complete, (uint32_t)n_param, (uint32_t)n_meas, var, first, total, first_var, total_var);
     return EZPZ_OK;
-}
-
-inline double pair_tree_256(double* v) {
-    for (uint32_t h = 1; h < kBlock; h *= 2)
-        for (uint32_t t = 0; t < kBlock; t += 2 * h) v[t] = v[t] + v[t + h];
-    return v[0];
 }
 
 // bit i of the answer: sample b (which exists) is INCOMPLETE for record i
@@ -167,7 +154,7 @@ inline int sums_host(const double* f, const uint8_t* flags, const uint8_t* ok, c
                 }
                 for (uint32_t c = 0; c < 4; ++c) {
                     double& s = sums[sum_at(k, i, j, c)];
-                    s = s + pair_tree_256(leaves.data() + c * kBlock);
+                    s = s + mcb::pair_tree_256(leaves.data() + c * kBlock);
                 }
             }
         }
@@ -201,13 +188,8 @@ struct CloseArgs {  // mc_sobol_close_kernel: the closing step's, on the sums wh
 };
 
 #ifdef EZPZ_SOBOL_KERNELS  // (mc_sobol.hip alone: the kernels have one home; the run of tolerance_mc.hip takes the host side below)
-struct WorkgroupCallers {
-    __device__ inline uint32_t id() const { return threadIdx.x; }
-    __device__ inline uint32_t count() const { return blockDim.x; }
-};
-
 __global__ __launch_bounds__(256) void mc_sobol_close_kernel(CloseArgs a) {
-    indices(WorkgroupCallers{}, a.sums, a.n_complete, a.k, a.m, a.var, a.first, a.total, a.first_var, a.total_var);
+    indices(mcb::WorkgroupCallers{}, a.sums, a.n_complete, a.k, a.m, a.var, a.first, a.total, a.first_var, a.total_var);
 }
 
 // a sub-round's ok bytes, by the Monte-Carlo section's rule (row A's come from mc_reduce_kernel)
@@ -236,77 +218,24 @@ struct Unit {
     const double *fa, *fj;  // the unit's element of row 0 and of row 2 + j (row 1: fa + stride_r) of the block's first sample
     uint64_t stride_s, stride_r;
     double nominal;
-    uint32_t bit;   // the record's bit in the completeness words
-    bool base;      // j == k: sA, sB, sAA, sBB
+    const uint32_t* bad;  // the completeness words
+    uint32_t bit;         // the record's bit in them
+    bool base;            // j == k: sA, sB, sAA, sBB
+    __device__ inline Quad operator()(uint32_t s) const {
+        if (bad[s] & bit) return Quad{0.0, 0.0, 0.0, 0.0};
+        const double dA = fa[s * stride_s] - nominal, dB = fa[s * stride_s + stride_r] - nominal;
+        if (base) return Quad{dA, dB, dA * dA, dB * dB};
+        const double dj = fj[s * stride_s] - nominal;
+        const double t = dj - dA;
+        const double p = dB * t, q = t * t;
+        return Quad{p, q, p * p, q * q};
+    }
 };
-
-__device__ inline Quad leaves_of(const Unit& u, const uint32_t* s_bad, uint32_t s) {
-    if (s_bad[s] & u.bit) return Quad{0.0, 0.0, 0.0, 0.0};
-    const double dA = u.fa[s * u.stride_s] - u.nominal, dB = u.fa[s * u.stride_s + u.stride_r] - u.nominal;
-    if (u.base) return Quad{dA, dB, dA * dA, dB * dB};
-    const double dj = u.fj[s * u.stride_s] - u.nominal;
-    const double t = dj - dA;
-    const double p = dB * t, q = t * t;
-    return Quad{p, q, p * p, q * q};
-}
-
-template <int N>
-__device__ inline Quad pair_sum(const Unit& u, const uint32_t* s_bad, uint32_t s) {
-    if constexpr (N == 1) {
-        return leaves_of(u, s_bad, s);
-    } else {
-        const Quad left = pair_sum<N / 2>(u, s_bad, s);
-        return left + pair_sum<N / 2>(u, s_bad, s + N / 2);
-    }
-}
-
-// the adjacent-pair tree over the samples [s0, s0 + 8 n8), n8 = 1, 2, .. 32 a power of two: the eights through the binary counter
-// (l0 .. l4: the pending sums of 8, 16, 32, 64 and 128 leaves)
-__device__ inline Quad subtree_sum(const Unit& u, const uint32_t* s_bad, uint32_t s0, uint32_t n8) {
-    Quad l0{}, l1{}, l2{}, l3{}, l4{}, out{};
-#pragma unroll 1
-    for (uint32_t g = 0; g < n8; ++g) {
-        Quad v = pair_sum<8>(u, s_bad, s0 + 8 * g);
-        if (!(g & 1u)) {
-            l0 = v;
-            continue;
-        }
-        v = l0 + v;
-        if (!(g & 2u)) {
-            l1 = v;
-            continue;
-        }
-        v = l1 + v;
-        if (!(g & 4u)) {
-            l2 = v;
-            continue;
-        }
-        v = l2 + v;
-        if (!(g & 8u)) {
-            l3 = v;
-            continue;
-        }
-        v = l3 + v;
-        if (!(g & 16u)) {
-            l4 = v;
-            continue;
-        }
-        out = l4 + v;
-    }
-    // (the last eight has every low bit set: the whole sum was stored at the level of n8's own bit)
-    if (n8 == 1) out = l0;
-    if (n8 == 2) out = l1;
-    if (n8 == 4) out = l2;
-    if (n8 == 8) out = l3;
-    if (n8 == 16) out = l4;
-    return out;
-}
 
 __global__ __launch_bounds__(256) void mc_sobol_kernel(SumArgs a) {
     __shared__ uint32_t s_bad[kBlock];
     __shared__ uint32_t s_n[kMax];
     __shared__ double s_join[kBlock * 4];  // [c][g][w]: group g's sum c of the unit of lane w
-    __shared__ uint32_t s_last;
     const uint32_t t = threadIdx.x, q = blockIdx.x, k = a.k, m = a.m, R = k + 2, U = m * (k + 1), E = m * width_of(k);
     const uint64_t base = (uint64_t)q * kBlock;  // the block's first sample, in the round
     const uint32_t all = m == 32 ? 0xFFFFFFFFu : (1u << m) - 1u;
@@ -350,9 +279,9 @@ __global__ __launch_bounds__(256) void mc_sobol_kernel(SumArgs a) {
             un.fj = un.fa + (uint64_t)(2 + (j < k ? j : 0)) * a.stride_r;
             un.stride_s = a.stride_s, un.stride_r = a.stride_r;
             un.nominal = a.nominal_m[i];
-            un.bit = 1u << i;
+            un.bad = s_bad, un.bit = 1u << i;
             un.base = j == k;
-            v = subtree_sum(un, s_bad, g * S, S / 8);
+            v = mcb::tree_sum<Quad>(un, g * S, S / 8);
         }
         if (G == 1) {
             part[sum_at(k, i, j, 0)] = v.a, part[sum_at(k, i, j, 1)] = v.b, part[sum_at(k, i, j, 2)] = v.c, part[sum_at(k, i, j, 3)] = v.d;
@@ -371,24 +300,11 @@ __global__ __launch_bounds__(256) void mc_sobol_kernel(SumArgs a) {
             part[sum_at(k, i, j, c)] = col[0];
         }
     }
-    // the partials are out before the ticket is drawn; whoever draws the last one sees every block's
-    __threadfence();
-    __syncthreads();
+    __syncthreads();  // (the counts are whole)
     if (t < m) a.part_n[(uint64_t)q * m + t] = s_n[t];
-    __threadfence();
-    __syncthreads();
-    if (t == 0) s_last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
+    if (!mcb::last_block(a.ticket)) return;
     const uint32_t blocks = gridDim.x;
-    for (uint32_t e = t; e < E; e += 256) {
-        double sum = a.first_round ? 0.0 : a.sums[e];
-        // (the sums depend on each other, the loads do not: unrolled, several blocks' partials are in flight at once)
-#pragma unroll 8
-        for (uint32_t b = 0; b < blocks; ++b) sum += a.part[(uint64_t)b * E + e];
-        a.sums[e] = sum;
-    }
+    mcb::fold_partials(a.part, E, a.first_round, a.sums);
     if (t < m) {
         uint64_t n = a.first_round ? 0 : a.n_complete[t];
         for (uint32_t b = 0; b < blocks; ++b) n += a.part_n[(uint64_t)b * m + t];
@@ -400,17 +316,9 @@ __global__ __launch_bounds__(256) void mc_sobol_kernel(SumArgs a) {
 #endif  // EZPZ_SOBOL_KERNELS
 
 // ---- the host side (mc_sobol.hip), shared with the run of tolerance_mc.hip -------------------------------------------------------
-// The reduction's workspace: whoever owns one orders the launches that use it (a LaunchOrder beside it) and waits for them before
-// it grows.
-struct SumWork {
-    DevBuf<double> part;
-    DevBuf<uint32_t> part_n;
-    DevBuf<unsigned int> ticket;
-    bool grows(uint64_t blocks, uint32_t k, uint32_t m) const { return blocks * m * width_of(k) > part.cap || blocks * m > part_n.cap || !ticket.p; }
-    int ensure(uint64_t blocks, uint32_t k, uint32_t m);
-};
-// one round: `a` with the rows' arrays and strides, count, k, m, fixed_mask, first_round, sums and n_complete set
-int enqueue_sums(SumWork& work, SumArgs a, hipStream_t stream);
+// one round: `a` with the rows' arrays and strides, count, k, m, fixed_mask, first_round, sums and n_complete set; the workspace
+// holds blocks * m * width_of(k) partials and blocks * m counts
+int enqueue_sums(mcb::Work& work, SumArgs a, hipStream_t stream);
 int enqueue_ok(const EzpzStatus* status, uint64_t count, uint8_t* ok, hipStream_t stream);
 int enqueue_close(const CloseArgs& a, hipStream_t stream);
 

@@ -1,22 +1,18 @@
 // Monte-Carlo tolerance analysis (include/ezpz_amd.h: ezpz_mc_sample, ezpz_system_tolerance_mc and its _device form; DESIGN.md
 // 3k): the host side of tolerance_mc.hip.hpp's kernels -- the check of a request, the plan a system keeps (the round's workspace,
 // the sampler's and the limits' tables, the host forms' buffers) and the rounds.  Every kind of run is one pipeline with a tail of
-// its own.  enter() checks the request and takes the plan; prepare() brings the plan's tables and buffers to what the run needs --
+// its own.  entry() checks the request and takes the plan; prepare() brings the plan's tables and buffers to what the run needs --
 // Needs lists every buffer with its count once, and both "does anything grow" and "grow it" are that list -- and measures the
 // nominal; sub_round() is sampler -> copies of x0 -> ezpz_system_solve_batch_params_device -> ezpz_system_measure_device, all on
 // the caller's stream: the driven solve and the measurement are those entries themselves, with their routes, their locks and their
-// ordering.  What a kind adds stands in its run function alone:
-//   run()        one sub-round a round and the reduction behind it; with contributors (ezpz_system_tolerance_mc_contrib[_device];
-//                DESIGN.md 3n) one more enqueue per round behind the reduction -- mc_moments.hip's, on the round's params, m, flags
-//                and ok -- and the closing kernel behind the last round; with quantiles (ezpz_system_tolerance_mc_quantiles[_device];
-//                DESIGN.md 3p) every round's m, flags and ok kept on the device, mc_quantiles.hip's selection behind the last round;
-//                with effects (ezpz_system_tolerance_mc_effects[_device]) one more enqueue per round behind the
-//                reduction -- mc_effects.hip's, on the same four arrays and the run's edges -- and its closing kernel behind the last
-//                round; with factorial effects (ezpz_system_tolerance_mc_factorial[_device]) every round's m, flags and ok
-//                kept on the device as for the quantiles, mc_factorial.hip's transform behind the last round
-//   run_sobol()  (ezpz_system_tolerance_sobol[_device]) k' + 2 sub-rounds a round into the round's rows, the reduction
-//                behind A's, mc_sobol.hip's sums behind the last one and its closing kernel behind the last round
-// A host form is its run between the upload of x0 and the copies back of its Staged outputs.
+// ordering.  What a kind adds stands in its tail alone -- Plain, Contrib, Quant, Effects, Fact, SobolOut: its checks, the one list of
+// its outputs, its workspaces and what it enqueues -- and the run is a template on the tail that names none of them:
+//   run()        one sub-round a round, the reduction behind it, then the tail's behind_round(); the rows kept on the device where
+//                the tail reads them; the tail's behind_run() behind the last round
+//   run_sobol()  (SobolOut alone) k' + 2 sub-rounds a round into the round's rows, the reduction behind A's, mc_sobol.hip's sums
+//                behind the last one and its closing kernel behind the last round
+// A host form is its run between the upload of x0 and the copies back of its Staged outputs.  A new kind is a tail, its two
+// extern "C" entries and, where it has a workspace, a field of McPlan.
 #include "driven_params.hpp"
 #include "mc_effects.hip.hpp"
 #include "mc_factorial.hip.hpp"
@@ -33,7 +29,7 @@ namespace {
 static_assert(sizeof(EzpzMcDist) == 24 && sizeof(EzpzMcStats) == 88 && sizeof(EzpzMcTotals) == 24 && sizeof(EzpzMcConfig) == 16,
               "the layouts include/ezpz_amd.h documents");
 
-constexpr uint32_t kBlock = 256;              // samples per block of the sums: fixed by the interface
+using mcb::kBlock;  // samples per block of the sums
 constexpr uint32_t kMaxHistBins = 64;
 // samples per round where the caller leaves the choice: kDefaultSampleChunk, while one of the round's two value arrays stays below
 constexpr uint64_t kChunkValueBytes = 256ull << 20;
@@ -56,19 +52,19 @@ struct McPlan {
     DevBuf<double> x0_in;
     DevBuf<unsigned char> host_out;
     // the run with contributors: the moments' workspace
-    mcm::MomentWork moment_work;
+    mcb::Work moment_work;
     // the run with Sobol indices: the round's rows -- [k + 2][chunk][n_meas] values and flags, [k + 2][chunk] ok bytes
     // -- and the sums' workspace
     DevBuf<double> rows_f;
     DevBuf<uint8_t> rows_flags, rows_ok;
-    sobol::SumWork sobol_work;
+    mcb::Work sobol_work;
     // the run with quantiles: every sample's m, flags and ok -- samples x n_meas x 9 + samples bytes, the one
     // workspace here that grows with samples -- and the selection's workspace
     DevBuf<double> all_m;
     DevBuf<uint8_t> all_flags, all_ok;
     mcq::SelectWork select_work;
     // the run with effects: the cells' workspace, and the edges [k][bins - 1] with what the buffer holds
-    mce::EffectWork effect_work;
+    mcb::Work effect_work;
     DevBuf<double> effect_edges;
     std::vector<double> effect_edges_kept;
     // the run with factorial effects: the rows in all_m, all_flags and all_ok as for the quantiles, and the transform's
@@ -184,143 +180,26 @@ struct Keep {
     bool host;  // the pointers are host memory: a round waits for its launches and copies out
 };
 
-// The outputs of a run with contributors (device pointers) and its checked configuration; moments == NULL: the plain run.
-struct Contrib {
-    double* moments = nullptr;
-    EzpzMcMomentsInfo* info = nullptr;
-    double *cov = nullptr, *beta = nullptr, *contrib = nullptr, *r2 = nullptr;
-    uint64_t* dropped = nullptr;
-    double pivot_rel = 0.0;
+// Every sample's m, flags and ok on the device, for a tail that reads them behind the last round: a caller's device keep-buffer
+// where one is given -- the round's copies into it fill it -- else (NULL) the plan's all_m, all_flags, all_ok.
+struct Rows {
+    double* m = nullptr;
+    uint8_t *flags = nullptr, *ok = nullptr;
 };
 
-// The argument errors the contributors add to a run's; the pointers are only compared with NULL.
-int check_contrib(size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcContribConfig* cc, Contrib& c) {
-    if (int rc = mcm::check_shape(n_param, n_meas)) return rc;
-    if (int rc = mcm::check_config(cc, c.pivot_rel)) return rc;
-    if (samples && (!c.moments || !c.info || !c.cov || !c.dropped || (n_meas && !c.r2) || (n_meas && n_param && (!c.beta || !c.contrib))))
-        return EZPZ_ERR_INVALID_ARGUMENT;
-    return EZPZ_OK;
-}
-
-// The outputs of a run with effects (device pointers in run(); edges: host memory) and its checked bins; sums == NULL: the plain run.
-struct Effects {
-    const double* edges = nullptr;
-    double* sums = nullptr;
-    uint64_t* counts = nullptr;
-    double *cond_mean = nullptr, *cond_var = nullptr, *eta2 = nullptr, *first = nullptr;
-    uint32_t* bins_used = nullptr;
-    uint32_t bins = 0;
-};
-
-// The argument errors the effects add to a run's; the outputs are only compared with NULL, the edges are read.
-int check_effects(size_t n_param, size_t n_meas, uint64_t samples, const EzpzMcEffectConfig* ec, Effects& e) {
-    EzpzMcEffectConfig conf;
-    mce::default_config(&conf);
-    if (ec) conf = *ec;
-    if (int rc = mce::check_shape(n_param, n_meas, conf.bins)) return rc;
-    if (samples && (!e.edges || !e.sums || !e.counts || !e.cond_mean || !e.cond_var || !e.eta2 || !e.first || !e.bins_used))
-        return EZPZ_ERR_INVALID_ARGUMENT;
-    if (e.edges)
-        if (int rc = mce::check_edges(e.edges, n_param, conf.bins)) return rc;
-    e.bins = conf.bins;
-    return EZPZ_OK;
-}
-
-// The quantiles of a run (probs: host memory; out: a device pointer in run()) and the checked z; n_q == 0: the plain run.
-struct Quant {
-    const double* probs = nullptr;
-    size_t n_q = 0;
-    EzpzMcQuantile* out = nullptr;
-    double z = 0.0;
-};
-
-// The outputs of a run with factorial effects (device pointers in run()) and the number of CORNER dimensions; info == NULL: the plain run.
-struct Fact {
-    mcf::FactorialOut out;
-    uint32_t kc = 0;
-};
-
-// The argument errors the factorial effects add to a run's; the outputs are only compared with NULL.
-int check_factorial(const Call& c, const Request& r, Fact& f) {
-    if (c.n_meas == 0 || c.n_meas > mcf::kMaxMeas) return EZPZ_ERR_INVALID_ARGUMENT;
-    f.kc = 0;
-    for (const mc::Dist& d : r.dists) {
-        if (d.kind != EZPZ_MC_CORNER && d.kind != EZPZ_MC_FIXED) return EZPZ_ERR_INVALID_ARGUMENT;
-        if (d.kind == EZPZ_MC_CORNER) ++f.kc;
-    }
-    if (f.kc == 0 || f.kc > mcf::kMaxCorners) return EZPZ_ERR_INVALID_ARGUMENT;
-    if (c.samples && c.samples != 1ull << f.kc) return EZPZ_ERR_INVALID_ARGUMENT;
-    const mcf::FactorialOut& o = f.out;
-    if (c.samples && (!o.info || !o.main || !o.pair || !o.ss_order || !o.ss_total || !o.first || !o.total)) return EZPZ_ERR_INVALID_ARGUMENT;
-    return EZPZ_OK;
-}
-
-// The outputs of a run with Sobol indices (device pointers in run_sobol) and its checked configuration.
-struct SobolOut {
-    double* sums = nullptr;
-    uint64_t* n_complete = nullptr;
-    double *var = nullptr, *first = nullptr, *total = nullptr, *first_var = nullptr, *total_var = nullptr;
-    uint64_t seed_b = 0;
-    uint32_t fixed_mask = 0;
-};
-
-// The argument errors the indices add to a run's, and the run's chunk; the pointers are only compared with NULL.
-int check_sobol(const Call& c, const EzpzSobolConfig* sc, Request& r, SobolOut& o) {
-    const size_t n_param = c.n_param, n_meas = c.n_meas;
-    if (int rc = sobol::check_shape(n_param, n_meas)) return rc;
-    EzpzSobolConfig s;
-    sobol::default_config(&s);
-    if (sc) s = *sc;
-    if (s.seed_b == r.seed) return EZPZ_ERR_INVALID_ARGUMENT;
-    o.seed_b = s.seed_b;
-    o.fixed_mask = 0;
-    for (size_t j = 0; j < n_param; ++j) {
-        if (r.dists[j].kind == EZPZ_MC_CORNER) return EZPZ_ERR_INVALID_ARGUMENT;
-        // (a flagged dimension's matrix B would be matrix A XOR a constant: the two are not independent, and pick-freeze needs that)
-        if (r.dists[j].sequence) return EZPZ_ERR_INVALID_ARGUMENT;
-        if (r.dists[j].kind == EZPZ_MC_FIXED) o.fixed_mask |= 1u << j;
-    }
-    if (c.samples && (!o.sums || !o.n_complete || !o.var || (n_param && (!o.first || !o.total || !o.first_var || !o.total_var))))
-        return EZPZ_ERR_INVALID_ARGUMENT;
-    if (!(c.mc_cfg && c.mc_cfg->chunk)) {  // the library's choice: the rows and the copies of x0 each below the round's bound
-        const uint64_t per_sample = std::max<uint64_t>({(uint64_t)c.sys->counts.n_vars, (uint64_t)(n_param + 2) * n_meas, 1}) * sizeof(double);
-        const uint64_t chunk = std::max<uint64_t>(std::min<uint64_t>(kChunkValueBytes / per_sample, kDefaultSampleChunk) / kBlock * kBlock, kBlock);
-        r.chunk = std::min<uint64_t>(chunk, whole_blocks(c.samples));
-    }
-    return EZPZ_OK;
-}
-
-// What every entry does before its run, in the order the argument errors take precedence: the run's checks, the kind's own
-// (`extra`), nothing to do for no samples -- up to here no output and nothing of the plan is touched -- then `body` on the plan
-// with its mutex held and the system's device current.
-template <class Extra, class Body>
-int enter(const Call& c, Extra&& extra, Body&& body) {
-    Request r;
-    if (int rc = check_run(c, r)) return rc;
-    if (int rc = extra(r)) return rc;
-    if (c.samples == 0) return EZPZ_OK;
-    McPlan& P = plan_of(c.sys);
-    std::lock_guard<std::mutex> lock(P.mu);
-    EZPZ_ON_DEVICE(c.sys->device);
-    return body(P, r);
-}
-
-// What a run needs of the plan's device buffers (the tables and the host forms' buffers apart).  visit() is the one list of them.
+// What a run needs of the plan's device buffers (the tables and the host forms' buffers apart): the round's, listed here, and the
+// tail's, which the tail lists.  visit() is the one list of them.
 struct Needs {
     uint64_t chunk, samples;
     size_t n_vars, n_param, n_meas;
-    size_t rows;   // 1: run()'s m, flags and ok; k + 2: run_sobol()'s rows and sums
-    bool contrib;  // the moments' workspace
-    size_t n_q;    // != 0: the selection's workspace, and of every sample's m, flags and ok the stores the plan has to hold itself
-    bool own_m, own_flags, own_ok;  // (false: a caller's device keep-buffer stands in)
-    uint32_t effect_bins = 0;       // != 0: the cells' workspace
-    uint32_t fact_kc = 0;           // != 0: the transform's workspace, and the stores of every sample's m, flags and ok as for n_q
+    size_t rows;  // 1: run()'s m, flags and ok; k + 2: run_sobol()'s rows
+    Rows kept;    // where the tail has the rows kept: the caller's buffers that stand in for the plan's
 
     // Every buffer with the count it has to hold.  grow == false: does any of them have to grow (1) or none (0); grow == true:
     // grow them (EZPZ_OK or the error).  A buffer cannot be in one answer and missing from the other.
-    int visit(McPlan& P, bool grow) const {
+    template <class Tail>
+    int visit(McPlan& P, const Tail& tail, bool grow) const {
         const uint64_t blocks = chunk / kBlock;
-        const uint32_t k = (uint32_t)n_param, m = (uint32_t)n_meas;
         int rc = EZPZ_OK;
         auto buf = [&](auto& b, uint64_t count) {
             if (rc == EZPZ_OK) rc = grow ? b.ensure(count) : (int)(count > b.cap);
@@ -335,37 +214,274 @@ struct Needs {
             buf(P.m, chunk * n_meas), buf(P.flags, chunk * n_meas), buf(P.ok, chunk);
         } else {
             buf(P.rows_f, rows * chunk * n_meas), buf(P.rows_flags, rows * chunk * n_meas), buf(P.rows_ok, rows * chunk);
-            work(P.sobol_work, blocks, k, m);
         }
-        if (contrib) work(P.moment_work, blocks, k + m);
-        if (n_q || fact_kc) {
-            if (own_m) buf(P.all_m, samples * n_meas);
-            if (own_flags) buf(P.all_flags, samples * n_meas);
-            if (own_ok) buf(P.all_ok, samples);
+        if (tail.keeps_rows()) {
+            if (!kept.m) buf(P.all_m, samples * n_meas);
+            if (!kept.flags) buf(P.all_flags, samples * n_meas);
+            if (!kept.ok) buf(P.all_ok, samples);
         }
-        if (n_q) work(P.select_work, m, (uint32_t)n_q);
-        if (fact_kc) work(P.factorial_work, m, fact_kc);
-        if (effect_bins) work(P.effect_work, blocks, k * effect_bins * m);
+        tail.needs(P, *this, work);
         return rc;
     }
 };
 
+// ---- the kinds: each a tail of the run --------------------------------------------------------------------------------------------
+// A tail holds what its entry was given (its outputs: device pointers in a run, host pointers in a host form's entry) and owns what
+// is the kind's: check() -- its argument errors, behind the run's; outputs() -- the ONE list of its outputs with their element
+// counts, which is both a host form's staging and the rule "an output with elements must be given"; needs() -- its workspaces;
+// keeps_rows() -- does it read every sample's rows behind the last round; upload() -- what it writes from the host before the
+// launches; behind_round() and behind_run() -- what it enqueues behind a round's reduction and behind the last round.
+struct Plain {
+    int check(const Call&, Request&) { return EZPZ_OK; }
+    template <class F>
+    void outputs(size_t, size_t, F&&) {}
+    template <class W>
+    void needs(McPlan&, const Needs&, W&) const {}
+    bool keeps_rows() const { return false; }
+    int upload(McPlan&, const Call&) const { return EZPZ_OK; }
+    int behind_round(McPlan&, const Call&, uint64_t, uint64_t) const { return EZPZ_OK; }
+    int behind_run(McPlan&, const Call&, const Rows&) const { return EZPZ_OK; }
+};
+
+// is an output that has elements missing (the pointers are only compared with NULL; without samples nothing is written)
+template <class Tail>
+bool output_missing(Tail& tail, const Call& c) {
+    bool missing = false;
+    if (c.samples) tail.outputs(c.n_param, c.n_meas, [&](auto*& p, size_t count) { missing = missing || (count && !p); });
+    return missing;
+}
+
+// Contributors (ezpz_system_tolerance_mc_contrib[_device]): mc_moments.hip's sums on every round's params, m, flags and
+// ok, its closing kernel behind the last round.
+struct Contrib : Plain {
+    const EzpzMcContribConfig* cc = nullptr;
+    double* moments = nullptr;
+    EzpzMcMomentsInfo* info = nullptr;
+    double *cov = nullptr, *beta = nullptr, *contrib = nullptr, *r2 = nullptr;
+    uint64_t* dropped = nullptr;
+    double pivot_rel = 0.0;  // as checked
+
+    int check(const Call& c, Request&) {
+        if (int rc = mcm::check_shape(c.n_param, c.n_meas)) return rc;
+        if (int rc = mcm::check_config(cc, pivot_rel)) return rc;
+        return output_missing(*this, c) ? EZPZ_ERR_INVALID_ARGUMENT : EZPZ_OK;
+    }
+    template <class F>
+    void outputs(size_t k, size_t m, F&& f) {
+        const size_t K = k + m;
+        f(moments, mcm::entries_of((uint32_t)K)), f(cov, K * K), f(beta, k * m), f(contrib, k * m), f(r2, m), f(info, 1), f(dropped, 1);
+    }
+    template <class W>
+    void needs(McPlan& P, const Needs& n, W& work) const {
+        const uint64_t blocks = n.chunk / kBlock;
+        work(P.moment_work, blocks * mcm::entries_of((uint32_t)(n.n_param + n.n_meas)), blocks);
+    }
+    int behind_round(McPlan& P, const Call& c, uint64_t first, uint64_t count) const {
+        mcm::MomentArgs a{};
+        a.params = P.params.p, a.m = P.m.p, a.flags = P.flags.p, a.ok = P.ok.p;
+        a.nominal_p = P.tab.p + 4 * c.n_meas, a.nominal_m = P.nominal.p;
+        a.first = first, a.count = count, a.samples = c.samples;
+        a.k = (uint32_t)c.n_param, a.n_meas = (uint32_t)c.n_meas, a.first_round = first == 0;
+        a.moments = moments, a.info = info;
+        return mcm::enqueue_moments(P.moment_work, a, c.stream);
+    }
+    int behind_run(McPlan&, const Call& c, const Rows&) const {
+        mcm::ContribArgs a{};
+        a.moments = moments, a.info = info;
+        a.k = (uint32_t)c.n_param, a.m = (uint32_t)c.n_meas;
+        a.pivot_rel = pivot_rel;
+        a.cov = cov, a.beta = beta, a.contrib = contrib, a.r2 = r2, a.dropped = dropped;
+        return mcm::enqueue_contributors(a, c.stream);
+    }
+};
+
+// Quantiles (ezpz_system_tolerance_mc_quantiles[_device]): every round's rows kept, mc_quantiles.hip's selection behind
+// the last round.  probs: host memory.  n_q == 0: the plain run.
+struct Quant : Plain {
+    const EzpzMcQuantileConfig* qc = nullptr;
+    const double* probs = nullptr;
+    size_t n_q = 0;
+    EzpzMcQuantile* out = nullptr;
+    double z = 0.0;  // as checked
+
+    int check(const Call& c, Request&) { return mcq::check(c.samples, c.n_meas, probs, n_q, qc, c.sys, out, z); }  // (the rows are the run's own)
+    template <class F>
+    void outputs(size_t, size_t m, F&& f) {
+        f(out, m * n_q);
+    }
+    template <class W>
+    void needs(McPlan& P, const Needs& n, W& work) const {
+        if (n_q) work(P.select_work, (uint32_t)n.n_meas, (uint32_t)n_q);
+    }
+    bool keeps_rows() const { return n_q != 0; }
+    int behind_run(McPlan& P, const Call& c, const Rows& rows) const {
+        if (!n_q) return EZPZ_OK;
+        return mcq::enqueue_select(P.select_work, rows.m, rows.flags, rows.ok, c.samples, (uint32_t)c.n_meas, probs, (uint32_t)n_q, z, out,
+                                   c.sys->lim.cus, c.stream);
+    }
+};
+
+// Main effects (ezpz_system_tolerance_mc_effects[_device]): mc_effects.hip's cells on every round's params, m, flags,
+// ok and the run's edges, its closing kernel behind the last round.  edges: host memory, read by check().
+struct Effects : Plain {
+    const EzpzMcEffectConfig* ec = nullptr;
+    const double* edges = nullptr;
+    double* sums = nullptr;
+    uint64_t* counts = nullptr;
+    double *cond_mean = nullptr, *cond_var = nullptr, *eta2 = nullptr, *first = nullptr;
+    uint32_t* bins_used = nullptr;
+    uint32_t bins = 0;  // as checked
+
+    int check(const Call& c, Request&) {
+        EzpzMcEffectConfig conf;
+        mce::default_config(&conf);
+        if (ec) conf = *ec;
+        if (int rc = mce::check_shape(c.n_param, c.n_meas, conf.bins)) return rc;
+        bins = conf.bins;
+        if ((c.samples && !edges) || output_missing(*this, c)) return EZPZ_ERR_INVALID_ARGUMENT;
+        return edges ? mce::check_edges(edges, c.n_param, bins) : EZPZ_OK;
+    }
+    template <class F>
+    void outputs(size_t k, size_t m, F&& f) {
+        const size_t cells = k * bins * m;
+        f(sums, 2 * cells), f(counts, cells), f(cond_mean, cells), f(cond_var, cells), f(eta2, k * m), f(first, k * m), f(bins_used, k * m);
+    }
+    template <class W>
+    void needs(McPlan& P, const Needs& n, W& work) const {
+        const uint64_t cells = n.chunk / kBlock * n.n_param * bins * n.n_meas;  // of every block
+        work(P.effect_work, cells * 2, cells);
+    }
+    // the edges where the kernels read them: others than the buffer holds wait for the last run's launches first
+    int upload(McPlan& P, const Call& c) const {
+        const size_t count = c.n_param * (bins - 1);
+        if (P.effect_edges.p && P.effect_edges_kept.size() == count &&
+            std::equal(edges, edges + count, P.effect_edges_kept.begin(), [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }))
+            return EZPZ_OK;
+        release_thread_kernel(c.sys->device);
+        int rc;
+        if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
+        P.effect_edges_kept.clear();
+        if ((rc = P.effect_edges.ensure(count)) != EZPZ_OK) return rc;
+        HIP_TRY(hipMemcpy(P.effect_edges.p, edges, count * sizeof(double), hipMemcpyHostToDevice));
+        P.effect_edges_kept.assign(edges, edges + count);
+        call_stamp(MC_TABLES_UPLOADED);
+        return EZPZ_OK;
+    }
+    int behind_round(McPlan& P, const Call& c, uint64_t first_sample, uint64_t count) const {
+        mce::EffectArgs a{};
+        a.params = P.params.p, a.m = P.m.p, a.flags = P.flags.p, a.ok = P.ok.p;
+        a.nominal_m = P.nominal.p;
+        a.edges = P.effect_edges.p;
+        a.count = count;
+        a.k = (uint32_t)c.n_param, a.n_meas = (uint32_t)c.n_meas, a.bins = bins, a.first_round = first_sample == 0;
+        a.sums = sums, a.counts = counts;
+        return mce::enqueue_effects(P.effect_work, a, c.stream);
+    }
+    int behind_run(McPlan& P, const Call& c, const Rows&) const {
+        mce::CloseArgs a{};
+        a.sums = sums, a.counts = counts;
+        a.nominal_m = P.nominal.p;
+        a.k = (uint32_t)c.n_param, a.m = (uint32_t)c.n_meas, a.bins = bins;
+        a.cond_mean = cond_mean, a.cond_var = cond_var, a.eta2 = eta2, a.first = first, a.bins_used = bins_used;
+        return mce::enqueue_close(a, c.stream);
+    }
+};
+
+// Factorial effects (ezpz_system_tolerance_mc_factorial[_device]): every round's rows kept as for the quantiles,
+// mc_factorial.hip's transform behind the last round.  coef is optional: no elements where it is NULL.
+struct Fact : Plain {
+    mcf::FactorialOut out;
+    uint32_t kc = 0;  // the CORNER dimensions, as checked
+
+    int check(const Call& c, Request& r) {
+        if (c.n_meas == 0 || c.n_meas > mcf::kMaxMeas) return EZPZ_ERR_INVALID_ARGUMENT;
+        kc = 0;
+        for (const mc::Dist& d : r.dists) {
+            if (d.kind != EZPZ_MC_CORNER && d.kind != EZPZ_MC_FIXED) return EZPZ_ERR_INVALID_ARGUMENT;
+            if (d.kind == EZPZ_MC_CORNER) ++kc;
+        }
+        if (kc == 0 || kc > mcf::kMaxCorners) return EZPZ_ERR_INVALID_ARGUMENT;
+        if (c.samples && c.samples != 1ull << kc) return EZPZ_ERR_INVALID_ARGUMENT;
+        return output_missing(*this, c) ? EZPZ_ERR_INVALID_ARGUMENT : EZPZ_OK;
+    }
+    template <class F>
+    void outputs(size_t, size_t m, F&& f) {
+        f(out.info, m), f(out.main, m * kc), f(out.pair, m * kc * kc), f(out.ss_order, m * (kc + 1)), f(out.ss_total, m * kc);
+        f(out.first, m * kc), f(out.total, m * kc), f(out.coef, out.coef ? m << kc : 0);
+    }
+    template <class W>
+    void needs(McPlan& P, const Needs& n, W& work) const {
+        work(P.factorial_work, (uint32_t)n.n_meas, kc);
+    }
+    bool keeps_rows() const { return true; }
+    int behind_run(McPlan& P, const Call& c, const Rows& rows) const {
+        return mcf::enqueue_factorial(P.factorial_work, rows.m, rows.flags, rows.ok, P.nominal.p, kc, (uint32_t)c.n_meas, out, c.sys->lim.cus, c.stream);
+    }
+};
+
+// Sobol indices (ezpz_system_tolerance_sobol[_device]): the tail of run_sobol(), which enqueues mc_sobol.hip's sums
+// and closing kernel itself.
+struct SobolOut {
+    const EzpzSobolConfig* sc = nullptr;
+    double* sums = nullptr;
+    uint64_t* n_complete = nullptr;
+    double *var = nullptr, *first = nullptr, *total = nullptr, *first_var = nullptr, *total_var = nullptr;
+    uint64_t seed_b = 0;      // as checked
+    uint32_t fixed_mask = 0;  // the FIXED dimensions
+
+    // ... and the run's chunk
+    int check(const Call& c, Request& r) {
+        const size_t n_param = c.n_param, n_meas = c.n_meas;
+        if (int rc = sobol::check_shape(n_param, n_meas)) return rc;
+        EzpzSobolConfig s;
+        sobol::default_config(&s);
+        if (sc) s = *sc;
+        if (s.seed_b == r.seed) return EZPZ_ERR_INVALID_ARGUMENT;
+        seed_b = s.seed_b;
+        fixed_mask = 0;
+        for (size_t j = 0; j < n_param; ++j) {
+            if (r.dists[j].kind == EZPZ_MC_CORNER) return EZPZ_ERR_INVALID_ARGUMENT;
+            // (a flagged dimension's matrix B would be matrix A XOR a constant: the two are not independent, and pick-freeze needs that)
+            if (r.dists[j].sequence) return EZPZ_ERR_INVALID_ARGUMENT;
+            if (r.dists[j].kind == EZPZ_MC_FIXED) fixed_mask |= 1u << j;
+        }
+        if (output_missing(*this, c)) return EZPZ_ERR_INVALID_ARGUMENT;
+        if (!(c.mc_cfg && c.mc_cfg->chunk)) {  // the library's choice: the rows and the copies of x0 each below the round's bound
+            const uint64_t per_sample = std::max<uint64_t>({(uint64_t)c.sys->counts.n_vars, (uint64_t)(n_param + 2) * n_meas, 1}) * sizeof(double);
+            const uint64_t chunk = std::max<uint64_t>(std::min<uint64_t>(kChunkValueBytes / per_sample, kDefaultSampleChunk) / kBlock * kBlock, kBlock);
+            r.chunk = std::min<uint64_t>(chunk, whole_blocks(c.samples));
+        }
+        return EZPZ_OK;
+    }
+    template <class F>
+    void outputs(size_t k, size_t m, F&& f) {
+        f(sums, m * sobol::width_of((uint32_t)k)), f(n_complete, m), f(var, m), f(first, k * m), f(total, k * m), f(first_var, k * m), f(total_var, k * m);
+    }
+    template <class W>
+    void needs(McPlan& P, const Needs& n, W& work) const {
+        const uint64_t blocks = n.chunk / kBlock;
+        work(P.sobol_work, blocks * n.n_meas * sobol::width_of((uint32_t)n.n_param), blocks * n.n_meas);
+    }
+    bool keeps_rows() const { return false; }
+};
+
 // What the host writes before a run's launches, behind the last run's, and the nominal: nominal[i] = m(record i, x0), 0 where
 // the guard fires.  `c` holds device pointers.
-int prepare(McPlan& P, const Request& r, const Call& c, const Needs& need) {
+template <class Tail>
+int prepare(McPlan& P, const Request& r, const Call& c, const Needs& need, const Tail& tail) {
     release_thread_kernel(c.sys->device);
     const size_t dist_bytes = r.dists.size() * sizeof(mc::Dist), tab_bytes = r.tab.size() * sizeof(double);
     int rc;
     std::vector<unsigned char> tables(dist_bytes + tab_bytes);
     if (dist_bytes) std::memcpy(tables.data(), r.dists.data(), dist_bytes);
     if (tab_bytes) std::memcpy(tables.data() + dist_bytes, r.tab.data(), tab_bytes);
-    if (tables != P.tables_kept || !P.ticket.p || need.visit(P, false)) {
+    if (tables != P.tables_kept || !P.ticket.p || need.visit(P, tail, false)) {
         if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
         P.tables_kept.clear();
         if ((rc = P.dist.ensure(r.dists.size())) != EZPZ_OK || (rc = P.tab.ensure(r.tab.size())) != EZPZ_OK) return rc;
         if (dist_bytes) HIP_TRY(hipMemcpy(P.dist.p, r.dists.data(), dist_bytes, hipMemcpyHostToDevice));
         if (tab_bytes) HIP_TRY(hipMemcpy(P.tab.p, r.tab.data(), tab_bytes, hipMemcpyHostToDevice));
-        if ((rc = need.visit(P, true)) != EZPZ_OK) return rc;
+        if ((rc = need.visit(P, tail, true)) != EZPZ_OK) return rc;
         if (!P.ticket.p) {
             if ((rc = P.ticket.ensure(1)) != EZPZ_OK) return rc;
             HIP_TRY(hipMemset(P.ticket.p, 0, P.ticket.cap * sizeof(unsigned int)));
@@ -374,7 +490,7 @@ int prepare(McPlan& P, const Request& r, const Call& c, const Needs& need) {
         call_stamp(MC_TABLES_UPLOADED);
     }
     if ((rc = P.order.order_behind(c.stream)) != EZPZ_OK) return rc;
-    // (run() measures where there are records; run_sobol() always does: check_sobol has seen to n_meas >= 1)
+    // (run() measures where there are records; run_sobol() always does: SobolOut::check has seen to n_meas >= 1)
     if (need.n_meas || need.rows != 1)
         return ezpz_system_measure_device(c.sys, c.records, need.n_meas, c.x0, 1, P.nominal.p, nullptr, nullptr, c.stream);
     return EZPZ_OK;
@@ -484,83 +600,30 @@ int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t w
     return EZPZ_OK;
 }
 
-// The edges of a run with effects where its kernels read them: others than the buffer holds wait for the last run's launches first.
-int upload_effect_edges(McPlan& P, const Call& c, const Effects& eff) {
-    const size_t count = c.n_param * (eff.bins - 1);
-    if (P.effect_edges.p && P.effect_edges_kept.size() == count && std::equal(eff.edges, eff.edges + count, P.effect_edges_kept.begin(),
-                                                                               [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }))
-        return EZPZ_OK;
-    release_thread_kernel(c.sys->device);
-    int rc;
-    if ((rc = P.order.before_overwrite()) != EZPZ_OK) return rc;
-    P.effect_edges_kept.clear();
-    if ((rc = P.effect_edges.ensure(count)) != EZPZ_OK) return rc;
-    HIP_TRY(hipMemcpy(P.effect_edges.p, eff.edges, count * sizeof(double), hipMemcpyHostToDevice));
-    P.effect_edges_kept.assign(eff.edges, eff.edges + count);
-    call_stamp(MC_TABLES_UPLOADED);
-    return EZPZ_OK;
-}
-
-// The plain run, with contributors, with quantiles, with effects or with factorial effects.  Device pointers throughout (but Keep's, see there): the plan's mutex is
-// held, the system's device current, the request checked and samples > 0.
-int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Contrib& contrib, const Quant& quant, const Effects& eff,
-        const Fact& fact = Fact{}) {
-    const size_t n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords;
+// The run of every kind but Sobol's: a round is one sub-round, the reduction behind it and what the tail enqueues behind that; the
+// tail's closing step goes behind the last round.  Device pointers throughout (but Keep's, see there): the plan's mutex is held, the
+// system's device current, the request checked and samples > 0.
+template <class Tail>
+int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Tail& tail) {
+    const size_t n_param = c.n_param, n_meas = c.n_meas;
     const uint64_t samples = c.samples, chunk = r.chunk;
     const hipStream_t stream = c.stream;
     int rc;
-    // the rows the selection or the transform reads: the caller's device buffers where given, else the plan's
-    const bool select = quant.n_q != 0, transform = fact.out.info != nullptr, rows_kept = select || transform;
-    double* all_m = !keep.host && keep.m ? keep.m : nullptr;
-    uint8_t* all_flags = !keep.host && keep.flags ? keep.flags : nullptr;
-    uint8_t* all_ok = !keep.host && keep.ok ? keep.ok : nullptr;
-    const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, 1, contrib.moments != nullptr, quant.n_q, !all_m, !all_flags, !all_ok,
-                     eff.sums ? eff.bins : 0u, transform ? fact.kc : 0u};
-    if (eff.sums && (rc = upload_effect_edges(P, c, eff)) != EZPZ_OK) return rc;
-    if ((rc = prepare(P, r, c, need)) != EZPZ_OK) return rc;
+    Rows rows;  // (a caller's device buffer is filled by the round's copies into it)
+    if (!keep.host) rows.m = keep.m, rows.flags = keep.flags, rows.ok = keep.ok;
+    const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, 1, rows};
+    if ((rc = tail.upload(P, c)) != EZPZ_OK || (rc = prepare(P, r, c, need, tail)) != EZPZ_OK) return rc;
     if (r.hist_bins && n_meas) HIP_TRY(hipMemsetAsync(c.hist, 0, n_meas * (r.hist_bins + 2) * sizeof(uint64_t), stream));
     mc::ReduceArgs a = reduce_args(P, need, P.m.p, P.flags.p, P.ok.p, r.limits, r.hist_bins, c.stats, c.totals, c.hist);
-    mcm::MomentArgs mo{};
-    mo.params = P.params.p;
-    mo.m = P.m.p;
-    mo.flags = P.flags.p;
-    mo.ok = P.ok.p;
-    mo.nominal_p = P.tab.p + 4 * n_meas;
-    mo.nominal_m = P.nominal.p;
-    mo.samples = samples;
-    mo.k = (uint32_t)n_param;
-    mo.n_meas = (uint32_t)n_meas;
-    mo.moments = contrib.moments;
-    mo.info = contrib.info;
-    mce::EffectArgs ef{};
-    ef.params = P.params.p;
-    ef.m = P.m.p;
-    ef.flags = P.flags.p;
-    ef.ok = P.ok.p;
-    ef.nominal_m = P.nominal.p;
-    ef.edges = P.effect_edges.p;
-    ef.k = (uint32_t)n_param, ef.n_meas = (uint32_t)n_meas, ef.bins = eff.bins;
-    ef.sums = eff.sums;
-    ef.counts = eff.counts;
     for (uint64_t first = 0; first < samples; first += chunk) {
         const uint64_t count = std::min<uint64_t>(chunk, samples - first);
-        if ((rc = sub_round(P, r, c, nullptr, first, count, P.m.p, P.flags.p)) != EZPZ_OK || (rc = enqueue_reduce(a, first, count, stream)) != EZPZ_OK)
+        if ((rc = sub_round(P, r, c, nullptr, first, count, P.m.p, P.flags.p)) != EZPZ_OK || (rc = enqueue_reduce(a, first, count, stream)) != EZPZ_OK ||
+            (rc = tail.behind_round(P, c, first, count)) != EZPZ_OK)
             return rc;
-        if (contrib.moments) {
-            mo.first = first;
-            mo.count = count;
-            mo.first_round = first == 0;
-            if ((rc = mcm::enqueue_moments(P.moment_work, mo, stream)) != EZPZ_OK) return rc;
-        }
-        if (eff.sums) {
-            ef.count = count;
-            ef.first_round = first == 0;
-            if ((rc = mce::enqueue_effects(P.effect_work, ef, stream)) != EZPZ_OK) return rc;
-        }
-        if (rows_kept) {  // (a caller's device buffer is filled by the copies below)
-            if ((rc = copy_out(all_m ? nullptr : P.all_m.p + first * n_meas, P.m.p, count * n_meas * sizeof(double), false, stream)) != EZPZ_OK ||
-                (rc = copy_out(all_flags ? nullptr : P.all_flags.p + first * n_meas, P.flags.p, count * n_meas, false, stream)) != EZPZ_OK ||
-                (rc = copy_out(all_ok ? nullptr : P.all_ok.p + first, P.ok.p, count, false, stream)) != EZPZ_OK)
+        if (tail.keeps_rows()) {
+            if ((rc = copy_out(rows.m ? nullptr : P.all_m.p + first * n_meas, P.m.p, count * n_meas * sizeof(double), false, stream)) != EZPZ_OK ||
+                (rc = copy_out(rows.flags ? nullptr : P.all_flags.p + first * n_meas, P.flags.p, count * n_meas, false, stream)) != EZPZ_OK ||
+                (rc = copy_out(rows.ok ? nullptr : P.all_ok.p + first, P.ok.p, count, false, stream)) != EZPZ_OK)
                 return rc;
         }
         if (keep.params || keep.m || keep.flags || keep.ok) {
@@ -572,33 +635,10 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
                 return rc;
         }
     }
-    if (contrib.moments) {
-        mcm::ContribArgs ca{};
-        ca.moments = contrib.moments;
-        ca.info = contrib.info;
-        ca.k = (uint32_t)n_param;
-        ca.m = (uint32_t)n_meas;
-        ca.pivot_rel = contrib.pivot_rel;
-        ca.cov = contrib.cov, ca.beta = contrib.beta, ca.contrib = contrib.contrib, ca.r2 = contrib.r2, ca.dropped = contrib.dropped;
-        if ((rc = mcm::enqueue_contributors(ca, stream)) != EZPZ_OK) return rc;
-    }
-    if (eff.sums) {
-        mce::CloseArgs cl{};
-        cl.sums = eff.sums;
-        cl.counts = eff.counts;
-        cl.nominal_m = P.nominal.p;
-        cl.k = (uint32_t)n_param, cl.m = (uint32_t)n_meas, cl.bins = eff.bins;
-        cl.cond_mean = eff.cond_mean, cl.cond_var = eff.cond_var, cl.eta2 = eff.eta2, cl.first = eff.first, cl.bins_used = eff.bins_used;
-        if ((rc = mce::enqueue_close(cl, stream)) != EZPZ_OK) return rc;
-    }
-    if (select && (rc = mcq::enqueue_select(P.select_work, all_m ? all_m : P.all_m.p, all_flags ? all_flags : P.all_flags.p,
-                                            all_ok ? all_ok : P.all_ok.p, samples, (uint32_t)n_meas, quant.probs, (uint32_t)quant.n_q, quant.z,
-                                            quant.out, c.sys->lim.cus, stream)) != EZPZ_OK)
-        return rc;
-    if (transform && (rc = mcf::enqueue_factorial(P.factorial_work, all_m ? all_m : P.all_m.p, all_flags ? all_flags : P.all_flags.p,
-                                                  all_ok ? all_ok : P.all_ok.p, P.nominal.p, fact.kc, (uint32_t)n_meas, fact.out, c.sys->lim.cus,
-                                                  stream)) != EZPZ_OK)
-        return rc;
+    if (!rows.m) rows.m = P.all_m.p;
+    if (!rows.flags) rows.flags = P.all_flags.p;
+    if (!rows.ok) rows.ok = P.all_ok.p;
+    if ((rc = tail.behind_run(P, c, rows)) != EZPZ_OK) return rc;
     call_stamp(MC_LAUNCHED);
     return P.order.record(stream);
 }
@@ -607,13 +647,13 @@ int run(McPlan& P, const Request& r, const Call& c, const Keep& keep, const Cont
 // with the reduction behind A's, the ok bytes behind every other one, mc_sobol.hip's sums behind the last one and its closing kernel
 // behind the last round.  Device pointers throughout (but Keep's): the plan's mutex is held, the system's device current, the
 // request checked and samples > 0.
-int run_sobol(McPlan& P, const Request& r, const Call& c, const SobolOut& out, const Keep& keep) {
-    const size_t n_param = r.dists.size(), n_meas = r.words.size() / kMeasureRecWords, R = n_param + 2;
+int run_sobol(McPlan& P, const Request& r, const Call& c, const Keep& keep, const SobolOut& out) {
+    const size_t n_param = c.n_param, n_meas = c.n_meas, R = n_param + 2;
     const uint64_t samples = c.samples, chunk = r.chunk;
     const hipStream_t stream = c.stream;
     int rc;
-    const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, R, false, 0, false, false, false};
-    if ((rc = prepare(P, r, c, need)) != EZPZ_OK) return rc;
+    const Needs need{chunk, samples, c.sys->counts.n_vars, n_param, n_meas, R, Rows{}};
+    if ((rc = prepare(P, r, c, need, out)) != EZPZ_OK) return rc;
     // A's rows through the plain run's reduction: no limits, no histogram
     mc::ReduceArgs a = reduce_args(P, need, P.rows_f.p, P.rows_flags.p, P.rows_ok.p, false, 0, c.stats, c.totals, nullptr);
     sobol::SumArgs su{};
@@ -663,7 +703,8 @@ int run_sobol(McPlan& P, const Request& r, const Call& c, const SobolOut& out, c
 }
 
 // A host form's outputs.  add() gives each a place, in order, in one device buffer; reserve() makes the buffer hold them and hands
-// out the places; copy_back() brings every output home.  An entry of no elements takes no room and is not copied.
+// out the places; copy_back() brings every output home.  An entry of no elements takes no room, has no place (NULL) and is not
+// copied.
 struct Staged {
     struct Entry {
         void* host;
@@ -686,7 +727,7 @@ struct Staged {
         }
         // (the buffer of an earlier host call is idle: it waited for its launches)
         if (int rc = buf.ensure(bytes)) return rc;
-        for (Entry& e : entries) e.set(e.dev, buf.p + e.offset);
+        for (Entry& e : entries) e.set(e.dev, e.count ? buf.p + e.offset : nullptr);
         return EZPZ_OK;
     }
     int copy_back(const DevBuf<unsigned char>& buf) const {
@@ -696,135 +737,42 @@ struct Staged {
     }
 };
 
-// A host form between its entry and its run: `c`'s x0 on the device, its stats and totals staged behind whatever `out` already
-// holds; `run_on(d)` runs on the device pointers; the copies back once the stream has drained.
-template <class Run>
-int host_form(McPlan& P, const Call& c, Staged& out, Run&& run_on) {
+// Every entry, in the order the argument errors take precedence: the run's checks, the tail's, nothing to do for no samples -- up to
+// here no output and nothing of the plan is touched -- then the run on the plan with its mutex held and the system's device current
+// (SobolOut's run is run_sobol()).  A host form (`c`, `keep` and `tail` hold host pointers) is that run between the upload of x0
+// and the copies back, once the stream has drained, of its outputs: the histogram, the tail's list, stats and totals, staged side
+// by side on the device.
+template <class Tail>
+int entry(const Call& c, const Keep& keep, Tail& tail, bool host) {
+    Request r;
+    if (int rc = check_run(c, r)) return rc;
+    if (int rc = tail.check(c, r)) return rc;
+    if (c.samples == 0) return EZPZ_OK;
+    McPlan& P = plan_of(c.sys);
+    std::lock_guard<std::mutex> lock(P.mu);
+    EZPZ_ON_DEVICE(c.sys->device);
+    auto run_on = [&](const Call& on, const Tail& t) {
+        if constexpr (std::is_same_v<Tail, SobolOut>)
+            return run_sobol(P, r, on, keep, t);
+        else
+            return run(P, r, on, keep, t);
+    };
+    if (!host) return run_on(c, tail);
     const size_t n = c.sys->counts.n_vars;
     Call d = c;
+    Tail dev = tail;
+    Staged out;
+    out.add(c.hist, c.n_meas * (r.hist_bins ? r.hist_bins + 2 : 0), d.hist);
+    dev.outputs(c.n_param, c.n_meas, [&](auto*& p, size_t count) { out.add(p, count, p); });
     out.add(c.stats, c.n_meas, d.stats);
     out.add(c.totals, 1, d.totals);
     int rc;
     if ((rc = P.x0_in.ensure(n)) != EZPZ_OK || (rc = out.reserve(P.host_out)) != EZPZ_OK) return rc;
     if (n) HIP_TRY(hipMemcpy(P.x0_in.p, c.x0, n * sizeof(double), hipMemcpyHostToDevice));
     d.x0 = P.x0_in.p;
-    if ((rc = run_on(d)) != EZPZ_OK) return rc;
+    if ((rc = run_on(d, dev)) != EZPZ_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c.stream));
     return out.copy_back(P.host_out);
-}
-
-// ---- the entries: plain, with contributors, with quantiles, with effects ----------------------------------------------------------
-int check_kinds(const Call& c, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant,
-                const EzpzMcEffectConfig* ec = nullptr, Effects* effects = nullptr) {
-    if (effects)
-        if (int rc = check_effects(c.n_param, c.n_meas, c.samples, ec, *effects)) return rc;
-    if (contrib)
-        if (int rc = check_contrib(c.n_param, c.n_meas, c.samples, cc, *contrib)) return rc;
-    if (quant)
-        if (int rc = mcq::check(c.samples, c.n_meas, quant->probs, quant->n_q, qc, c.sys, quant->out, quant->z)) return rc;  // (the rows are the run's own)
-    return EZPZ_OK;
-}
-
-int run_device(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant,
-               const EzpzMcEffectConfig* ec = nullptr, Effects* effects = nullptr) {
-    return enter(c, [&](Request&) { return check_kinds(c, cc, contrib, qc, quant, ec, effects); }, [&](McPlan& P, Request& r) {
-        return run(P, r, c, keep, contrib ? *contrib : Contrib{}, quant ? *quant : Quant{}, effects ? *effects : Effects{});
-    });
-}
-
-// `contrib`, `quant` and `effects` hold host pointers here.
-int run_host(const Call& c, const Keep& keep, const EzpzMcContribConfig* cc, Contrib* contrib, const EzpzMcQuantileConfig* qc, Quant* quant,
-             const EzpzMcEffectConfig* ec = nullptr, Effects* effects = nullptr) {
-    return enter(c, [&](Request&) { return check_kinds(c, cc, contrib, qc, quant, ec, effects); }, [&](McPlan& P, Request& r) {
-        const size_t n_param = c.n_param, n_meas = c.n_meas, K = n_param + n_meas, km = n_param * n_meas;
-        Staged out;
-        uint64_t* hist_dev = nullptr;
-        out.add(c.hist, n_meas * (r.hist_bins ? r.hist_bins + 2 : 0), hist_dev);
-        Contrib dev;
-        if (contrib) {
-            dev.pivot_rel = contrib->pivot_rel;
-            out.add(contrib->moments, mcm::entries_of((uint32_t)K), dev.moments);
-            out.add(contrib->cov, K * K, dev.cov);
-            out.add(contrib->beta, km, dev.beta);
-            out.add(contrib->contrib, km, dev.contrib);
-            out.add(contrib->r2, n_meas, dev.r2);
-            out.add(contrib->info, 1, dev.info);
-            out.add(contrib->dropped, 1, dev.dropped);
-        }
-        Quant qdev;
-        if (quant && quant->n_q) {
-            qdev = *quant;
-            out.add(quant->out, n_meas * quant->n_q, qdev.out);
-        }
-        Effects edev;
-        if (effects) {
-            edev = *effects;  // (the edges stay the caller's host array; bins as checked)
-            const size_t cells = n_param * effects->bins * n_meas;
-            out.add(effects->sums, 2 * cells, edev.sums);
-            out.add(effects->counts, cells, edev.counts);
-            out.add(effects->cond_mean, cells, edev.cond_mean);
-            out.add(effects->cond_var, cells, edev.cond_var);
-            out.add(effects->eta2, km, edev.eta2);
-            out.add(effects->first, km, edev.first);
-            out.add(effects->bins_used, km, edev.bins_used);
-        }
-        return host_form(P, c, out, [&](Call& d) {
-            d.hist = hist_dev;
-            return run(P, r, d, keep, dev, qdev, edev);
-        });
-    });
-}
-
-// ---- the entries: factorial effects ------------------------------------------------------------------------------------------------
-int factorial_device(const Call& c, const Keep& keep, Fact& fact) {
-    return enter(c, [&](Request& r) { return check_factorial(c, r, fact); },
-                 [&](McPlan& P, Request& r) { return run(P, r, c, keep, Contrib{}, Quant{}, Effects{}, fact); });
-}
-
-// `fact` holds host pointers here.
-int factorial_host(const Call& c, const Keep& keep, Fact& fact) {
-    return enter(c, [&](Request& r) { return check_factorial(c, r, fact); }, [&](McPlan& P, Request& r) {
-        const size_t n_meas = c.n_meas, kc = fact.kc, N = (size_t)1 << kc;
-        Staged out;
-        uint64_t* hist_dev = nullptr;
-        out.add(c.hist, n_meas * (r.hist_bins ? r.hist_bins + 2 : 0), hist_dev);
-        Fact dev;
-        dev.kc = fact.kc;
-        out.add(fact.out.info, n_meas, dev.out.info);
-        out.add(fact.out.main, n_meas * kc, dev.out.main);
-        out.add(fact.out.pair, n_meas * kc * kc, dev.out.pair);
-        out.add(fact.out.ss_order, n_meas * (kc + 1), dev.out.ss_order);
-        out.add(fact.out.ss_total, n_meas * kc, dev.out.ss_total);
-        out.add(fact.out.first, n_meas * kc, dev.out.first);
-        out.add(fact.out.total, n_meas * kc, dev.out.total);
-        if (fact.out.coef) out.add(fact.out.coef, n_meas * N, dev.out.coef);
-        return host_form(P, c, out, [&](Call& d) {
-            d.hist = hist_dev;
-            return run(P, r, d, keep, Contrib{}, Quant{}, Effects{}, dev);
-        });
-    });
-}
-
-// ---- the entries: Sobol indices ----------------------------------------------------------------------------------------------------
-int sobol_device(const Call& c, const EzpzSobolConfig* sc, SobolOut& out, const Keep& keep) {
-    return enter(c, [&](Request& r) { return check_sobol(c, sc, r, out); }, [&](McPlan& P, Request& r) { return run_sobol(P, r, c, out, keep); });
-}
-
-// `out` holds host pointers here.
-int sobol_host(const Call& c, const EzpzSobolConfig* sc, SobolOut& out, const Keep& keep) {
-    return enter(c, [&](Request& r) { return check_sobol(c, sc, r, out); }, [&](McPlan& P, Request& r) {
-        const size_t n_meas = c.n_meas, km = c.n_param * n_meas;
-        Staged staged;
-        SobolOut dev = out;
-        staged.add(out.sums, n_meas * sobol::width_of((uint32_t)c.n_param), dev.sums);
-        staged.add(out.n_complete, n_meas, dev.n_complete);
-        staged.add(out.var, n_meas, dev.var);
-        staged.add(out.first, km, dev.first);
-        staged.add(out.total, km, dev.total);
-        staged.add(out.first_var, km, dev.first_var);
-        staged.add(out.total_var, km, dev.total_var);
-        return host_form(P, c, staged, [&](Call& d) { return run_sobol(P, r, d, dev, keep); });
-    });
 }
 
 }  // namespace
@@ -851,7 +799,8 @@ int ezpz_system_tolerance_mc_device(EzpzSystem* sys, const double* x0_dev, const
                                     uint8_t* keep_ok_dev, void* stream) {
     const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
-    return run_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr, nullptr, nullptr);
+    Plain plain;
+    return entry(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, plain, false);
 }
 
 int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -861,7 +810,8 @@ int ezpz_system_tolerance_mc(EzpzSystem* sys, const double* x0, const uint32_t* 
                              uint8_t* keep_flags, uint8_t* keep_ok) {
     const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats, totals, hist, hipStreamPerThread};
-    return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, nullptr, nullptr);
+    Plain plain;
+    return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, plain, true);
 }
 
 int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
@@ -875,8 +825,8 @@ int ezpz_system_tolerance_mc_contrib_device(EzpzSystem* sys, const double* x0_de
     const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
     Contrib o;
-    o.moments = moments_dev, o.info = info_dev, o.cov = cov_dev, o.beta = beta_dev, o.contrib = contrib_dev, o.r2 = r2_dev, o.dropped = dropped_dev;
-    return run_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, cc, &o, nullptr, nullptr);
+    o.cc = cc, o.moments = moments_dev, o.info = info_dev, o.cov = cov_dev, o.beta = beta_dev, o.contrib = contrib_dev, o.r2 = r2_dev, o.dropped = dropped_dev;
+    return entry(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, o, false);
 }
 
 int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -889,8 +839,8 @@ int ezpz_system_tolerance_mc_contrib(EzpzSystem* sys, const double* x0, const ui
     const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats, totals, hist, hipStreamPerThread};
     Contrib o;
-    o.moments = moments, o.info = info, o.cov = cov, o.beta = beta, o.contrib = contrib, o.r2 = r2, o.dropped = dropped;
-    return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, cc, &o, nullptr, nullptr);
+    o.cc = cc, o.moments = moments, o.info = info, o.cov = cov, o.beta = beta, o.contrib = contrib, o.r2 = r2, o.dropped = dropped;
+    return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, o, true);
 }
 
 int ezpz_system_tolerance_mc_effects_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
@@ -905,9 +855,9 @@ int ezpz_system_tolerance_mc_effects_device(EzpzSystem* sys, const double* x0_de
     const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
     Effects o;
-    o.edges = edges, o.sums = sums_dev, o.counts = counts_dev, o.cond_mean = cond_mean_dev, o.cond_var = cond_var_dev;
+    o.ec = ec, o.edges = edges, o.sums = sums_dev, o.counts = counts_dev, o.cond_mean = cond_mean_dev, o.cond_var = cond_var_dev;
     o.eta2 = eta2_dev, o.first = first_dev, o.bins_used = bins_used_dev;
-    return run_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr, nullptr, nullptr, ec, &o);
+    return entry(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, o, false);
 }
 
 int ezpz_system_tolerance_mc_effects(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -920,9 +870,9 @@ int ezpz_system_tolerance_mc_effects(EzpzSystem* sys, const double* x0, const ui
     const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats, totals, hist, hipStreamPerThread};
     Effects o;
-    o.edges = edges, o.sums = sums, o.counts = counts, o.cond_mean = cond_mean, o.cond_var = cond_var;
+    o.ec = ec, o.edges = edges, o.sums = sums, o.counts = counts, o.cond_mean = cond_mean, o.cond_var = cond_var;
     o.eta2 = eta2, o.first = first, o.bins_used = bins_used;
-    return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, nullptr, nullptr, ec, &o);
+    return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, o, true);
 }
 
 int ezpz_system_tolerance_mc_quantiles_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
@@ -936,8 +886,8 @@ int ezpz_system_tolerance_mc_quantiles_device(EzpzSystem* sys, const double* x0_
     const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
     Quant q;
-    q.probs = probs, q.n_q = n_q, q.out = out_dev;
-    return run_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, nullptr, nullptr, qc, &q);
+    q.qc = qc, q.probs = probs, q.n_q = n_q, q.out = out_dev;
+    return entry(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, q, false);
 }
 
 int ezpz_system_tolerance_mc_quantiles(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
@@ -950,8 +900,8 @@ int ezpz_system_tolerance_mc_quantiles(EzpzSystem* sys, const double* x0, const 
     const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
                  stats, totals, hist, hipStreamPerThread};
     Quant q;
-    q.probs = probs, q.n_q = n_q, q.out = out;
-    return run_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, nullptr, nullptr, qc, &q);
+    q.qc = qc, q.probs = probs, q.n_q = n_q, q.out = out;
+    return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, q, true);
 }
 
 int ezpz_system_tolerance_mc_factorial_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
@@ -968,7 +918,7 @@ int ezpz_system_tolerance_mc_factorial_device(EzpzSystem* sys, const double* x0_
     Fact f;
     f.out.info = info_dev, f.out.main = main_dev, f.out.pair = pair_dev, f.out.ss_order = ss_order_dev, f.out.ss_total = ss_total_dev;
     f.out.first = first_dev, f.out.total = total_dev, f.out.coef = coef_dev;
-    return factorial_device(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, f);
+    return entry(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, f, false);
 }
 
 int ezpz_system_tolerance_mc_factorial(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param,
@@ -983,7 +933,7 @@ int ezpz_system_tolerance_mc_factorial(EzpzSystem* sys, const double* x0, const 
     Fact f;
     f.out.info = info, f.out.main = main, f.out.pair = pair, f.out.ss_order = ss_order, f.out.ss_total = ss_total;
     f.out.first = first, f.out.total = total, f.out.coef = coef;
-    return factorial_host(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, f);
+    return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, f, true);
 }
 
 int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
@@ -995,9 +945,9 @@ int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, co
     const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, nullptr, nullptr, nullptr, nullptr, samples, mc_cfg, cfg,
                  stats_dev, totals_dev, nullptr, (hipStream_t)stream};
     SobolOut o;
-    o.sums = sums_dev, o.n_complete = n_complete_dev, o.var = var_dev, o.first = first_dev, o.total = total_dev;
+    o.sc = sc, o.sums = sums_dev, o.n_complete = n_complete_dev, o.var = var_dev, o.first = first_dev, o.total = total_dev;
     o.first_var = first_var_dev, o.total_var = total_var_dev;
-    return sobol_device(c, sc, o, Keep{nullptr, keep_f_dev, keep_flags_dev, keep_ok_dev, false});
+    return entry(c, Keep{nullptr, keep_f_dev, keep_flags_dev, keep_ok_dev, false}, o, false);
 }
 
 int ezpz_system_tolerance_sobol(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
@@ -1008,8 +958,8 @@ int ezpz_system_tolerance_sobol(EzpzSystem* sys, const double* x0, const uint32_
     const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, nullptr, nullptr, nullptr, nullptr, samples, mc_cfg, cfg,
                  stats, totals, nullptr, hipStreamPerThread};
     SobolOut o;
-    o.sums = sums, o.n_complete = n_complete, o.var = var, o.first = first, o.total = total, o.first_var = first_var, o.total_var = total_var;
-    return sobol_host(c, sc, o, Keep{nullptr, keep_f, keep_flags, keep_ok, true});
+    o.sc = sc, o.sums = sums, o.n_complete = n_complete, o.var = var, o.first = first, o.total = total, o.first_var = first_var, o.total_var = total_var;
+    return entry(c, Keep{nullptr, keep_f, keep_flags, keep_ok, true}, o, true);
 }
 
 }  // extern "C"

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void mc_sample_pick_kernel(const Dist* __restr
     for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += stride) {
         const uint64_t s = idx / n_param;
         const uint32_t j = (uint32_t)(idx - s * n_param);
-        params[idx] = draw_plain(pick == kPickAll || j == pick ? seed_b : seed_a, first + s, j, dist[j]);  // (no flagged dimension: check_sobol)
+        params[idx] = draw_plain(pick == kPickAll || j == pick ? seed_b : seed_a, first + s, j, dist[j]);  // (no flagged dimension: SobolOut::check)
     }
 }
 
@@ -208,7 +208,9 @@ __global__ __launch_bounds__(256) void mc_reduce_kernel(ReduceArgs a) {
     if (t == 0) {
         a.part_ok[q] = s_valid[0] + s_valid[1] + s_valid[2] + s_valid[3];
         a.part_all_in[q] = s_in[0] + s_in[1] + s_in[2] + s_in[3];
-        // the partials are out before the ticket is drawn; whoever draws the last one sees every block's
+        // the partials are out before the ticket is drawn; whoever draws the last one sees every block's.  (mcb::last_block's
+        // step, with the fence in the one thread that wrote them: with it in all four wavefronts a run measured some 10 us a
+        // round slower; profiles/mc_block_sum_ab.txt, section 2)
         __threadfence();
         s_last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
     }

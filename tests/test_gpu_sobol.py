@@ -72,7 +72,9 @@ def reference_sums(k, m, samples, mask):
 WIDE_MASK = 0b1000_0000_0001_0000_0000_0000_0100_0010  # FIXED dimensions 1, 6, 20 and 31 of 32
 
 
-@pytest.mark.parametrize("k,m,samples,mask", SUM_SHAPES + [(1, 1, 257, 0), (8, 8, 257, 0b100), (32, 32, 257, WIDE_MASK)])
+# (U = m (k + 1) units pick the length of the kernel's sub-trees: 16, 32 and 64 units are the 2, 4 and 8 eights the other shapes miss)
+@pytest.mark.parametrize("k,m,samples,mask", SUM_SHAPES + [(1, 1, 257, 0), (8, 8, 257, 0b100), (32, 32, 257, WIDE_MASK),
+                                                           (3, 4, 257, 0), (7, 4, 257, 0), (7, 8, 257, 0)])
 def test_the_device_sums_are_the_stated_sums(E, k, m, samples, mask):
     a = rows_of(k, m, samples, mask)
     want, want_n = reference_sums(k, m, samples, mask)

@@ -172,6 +172,70 @@ def test_device_form_on_another_stream_equals_the_host_form(E):
     assert got == result_bytes(res)
 
 
+# ---- the kinds of run share a system's plan: what one leaves in it changes no byte of the next ------------------------------------
+RECS6 = ALL46[:6]
+SMOOTH16 = [(R.UNIFORM, -0.2, 0.2) if d[0] == R.CORNER else d for d in DISTS16]  # (the Sobol run takes no CORNER dimension)
+CORNERS16 = [(R.CORNER, -0.1, 0.1)] * 3 + [(R.FIXED, 0.0, 0.0)] * (N16 - 3)
+
+
+def _contrib_on_a_second_stream(E, s):
+    import torch
+
+    K = N16 + 6
+    x0 = torch.from_numpy(X16).cuda()
+    sizes = (6 * 88, 24, (K + K * (K + 1) // 2) * 8, 16, K * K * 8, 6 * N16 * 8, 6 * N16 * 8, 6 * 8, 8)  # stats .. dropped
+    out = [torch.full((n,), 0x5A, dtype=torch.uint8, device="cuda") for n in sizes]
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream):
+        s.tolerance_mc_device(x0.data_ptr(), POS16, dists_of(E, DISTS16), RECS6, 257, out[0].data_ptr(), out[1].data_ptr(), seed=SEED, chunk=256,
+                              stream=stream.cuda_stream, **{name: t.data_ptr() for name, t in zip(
+                                  ("moments_ptr", "info_ptr", "cov_ptr", "beta_ptr", "contrib_ptr", "r2_ptr", "dropped_ptr"), out[2:])})
+    stream.synchronize()
+    return [t.cpu().numpy().tobytes() for t in out]
+
+
+def _kind_calls(E):
+    """name -> call(system) -> every output of the call as bytes."""
+    def run(samples=257, dists=DISTS16, keep=False, also=(), **kind):
+        def call(s):
+            res = s.tolerance_mc(X16, POS16, dists_of(E, dists), RECS6, samples, seed=SEED, chunk=256, keep=keep, **kind)
+            return result_bytes(res, keep) + [np.ascontiguousarray(get(res)).tobytes() for get in also]
+        return call
+
+    def part(owner, *names):
+        return [lambda res, n=n: getattr(getattr(res, owner) if owner else res, n) for n in names]
+
+    def sobol(s):
+        res = s.tolerance_sobol(X16, POS16, dists_of(E, SMOOTH16), RECS6, 257, seed=SEED, chunk=256, keep=True)
+        return [np.ascontiguousarray(a).tobytes() for a in (res.stats, res.totals, res.sums, res.n_complete, res.var, res.first, res.total,
+                                                            res.first_var, res.total_var, res.f, res.flags, res.ok)]
+
+    quantiles = dict(quantiles=[0.0, 0.1, 0.5, 1.0], quantile_z=2.0, also=part("", "quantiles"))
+    return {"plain": run(keep=True),
+            "contributors": lambda s: _contrib_on_a_second_stream(E, s),
+            "quantiles": run(**quantiles),
+            "effects": run(effects=E.EffectsConfig(8), also=part("effects", "sums", "counts", "edges", "cond_mean", "cond_var", "eta2", "first",
+                                                                  "bins_used")),
+            "factorial": run(samples=8, dists=CORNERS16, factorial=True, also=part("factorial", "info", "main", "pair", "ss_order", "ss_total",
+                                                                                   "first", "total")),
+            "sobol": sobol,
+            "quantiles of 600": run(samples=600, **quantiles)}
+
+
+def test_the_kinds_share_a_plan(E):
+    """Two rounds a run, the second of one sample.  Every kind after every other on ONE system -- the six in order, then in reverse
+    order, then the quantiles on rows that have to grow after the factorial run has used them -- gives, output for output and byte
+    for byte, what the same call gives on a system that has run nothing else."""
+    calls = _kind_calls(E)
+    fixed16 = O.stack([O.fixed(v, float(X16[v])) for v in range(N16)])
+    want = {name: call(E.System(fixed16, N16)) for name, call in calls.items()}
+    shared = E.System(fixed16, N16)
+    six = list(calls)[:6]
+    for name in six + six[::-1] + ["quantiles of 600"]:
+        assert calls[name](shared) == want[name], name
+
+
 # ---- variants that do not assemble: a triangle whose third side can outgrow the other two --------------------------------------
 A, B, Cc = (0, 1), (2, 3), (4, 5)
 TRIANGLE = O.stack([O.fixed(0, 0.0), O.fixed(1, 0.0), O.fixed(3, 0.0), O.distance(A, B, 1.0), O.distance(B, Cc, 1.0), O.distance(Cc, A, 1.9)])
