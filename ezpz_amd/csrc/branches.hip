@@ -1,10 +1,10 @@
 // Solution branches (include/ezpz_amd.h: ezpz_branch_cluster, ezpz_system_solve_branches and their _device forms):
 // the host side of branches.hip.hpp's kernels -- the check of a request, the plan (the round's workspace, the compared variables'
-// and the sampler's tables, the host forms' buffers) and the rounds.  A round of the run is the start kernel ->
+// and the sampler's tables, the host forms' staging) and the rounds.  A round of the run is the start kernel ->
 // ezpz_system_solve_batch_device -> assign -> elect, all on the caller's stream: the solve is that entry itself, with its routes,
 // its locks and its ordering.  The leader table lives in the caller's outputs between rounds.
 #include "branches.hip.hpp"
-#include "system.hpp"
+#include "host_stage.hpp"
 
 using namespace ezpz;
 
@@ -30,12 +30,7 @@ struct BranchPlan {
     DevBuf<double> x_in, x_out;
     DevBuf<EzpzStatus> status;
     DevBuf<int32_t> label;
-    // the host forms' buffers
-    DevBuf<double> x_all, x_branch_out;
-    DevBuf<uint8_t> ok_all;
-    DevBuf<EzpzBranchInfo> info_out;
-    DevBuf<EzpzBranch> branches_out;
-    DevBuf<int32_t> label_out;
+    DevBuf<unsigned char> host_stage;  // the host forms' staging (host_stage.hpp)
 };
 
 BranchPlan& plan_of(EzpzSystem* sys) {
@@ -268,24 +263,21 @@ int run(EzpzSystem* sys, BranchPlan& P, const Request& r, const double* x0_dev, 
     return P.order.record(stream);
 }
 
-// The host forms' outputs: the plan's buffers, and the copies back once the stream has drained.
-int host_outputs(BranchPlan& P, const Request& r, uint64_t batch, uint64_t samples, size_t n_vars, bool labels) {
-    int rc;
-    if ((rc = P.info_out.ensure(batch)) != EZPZ_OK || (rc = P.branches_out.ensure(batch * r.max_branches)) != EZPZ_OK ||
-        (rc = P.x_branch_out.ensure(batch * r.max_branches * n_vars)) != EZPZ_OK || (rc = P.label_out.ensure(labels ? batch * samples : 0)) != EZPZ_OK)
-        return rc;
-    return EZPZ_OK;
-}
-
-int copy_back(BranchPlan& P, const Request& r, uint64_t batch, uint64_t samples, size_t n_vars, EzpzBranchInfo* info, EzpzBranch* branches,
-              double* x_branch, int32_t* keep_label) {
-    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
-    HIP_TRY(hipMemcpy(info, P.info_out.p, batch * sizeof(EzpzBranchInfo), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(branches, P.branches_out.p, batch * r.max_branches * sizeof(EzpzBranch), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(x_branch, P.x_branch_out.p, batch * r.max_branches * n_vars * sizeof(double), hipMemcpyDeviceToHost));
-    if (keep_label) HIP_TRY(hipMemcpy(keep_label, P.label_out.p, batch * samples * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return EZPZ_OK;
-}
+// The outputs of both host forms: their places on the list
+struct HostOutputs {
+    EzpzBranchInfo* info;
+    EzpzBranch* branches;
+    double* x_branch;
+    int32_t* label;
+    HostOutputs(Staged& io, const Request& r, uint64_t batch, uint64_t samples, size_t n_vars, EzpzBranchInfo* info_host, EzpzBranch* branches_host,
+                double* x_branch_host, int32_t* keep_label) {
+        io.out(info_host, batch, info);
+        io.out(branches_host, batch * r.max_branches, branches);
+        io.out(x_branch_host, batch * r.max_branches * n_vars, x_branch);
+        io.out(keep_label, batch * samples, label);
+    }
+    HostOutputs(const HostOutputs&) = delete;  // (the list holds the members' addresses)
+};
 
 }  // namespace
 
@@ -324,17 +316,19 @@ int ezpz_branch_cluster(const double* x, const uint8_t* ok, const uint8_t* compa
     int device = -1;
     if (int rc = plan_of_device(P, device)) return rc;
     std::lock_guard<std::mutex> lock(P->mu);
+    const double* x_dev;
+    const uint8_t* ok_dev;
+    Staged io;
+    io.in(x, batch * samples * n_vars, x_dev);
+    io.in(ok, batch * samples, ok_dev);
+    HostOutputs o(io, r, batch, samples, n_vars, info, branches, x_branch, keep_label);
     int rc;
-    // (the buffers of an earlier host call are idle: it waited for its launches)
-    if ((rc = P->x_all.ensure(batch * samples * n_vars)) != EZPZ_OK || (rc = P->ok_all.ensure(ok ? batch * samples : 0)) != EZPZ_OK ||
-        (rc = host_outputs(*P, r, batch, samples, n_vars, keep_label != nullptr)) != EZPZ_OK)
+    if ((rc = io.reserve(P->host_stage)) != EZPZ_OK || (rc = io.upload(P->host_stage)) != EZPZ_OK) return rc;
+    if ((rc = cluster(*P, r, device_limits(device).cus, x_dev, ok_dev, batch, samples, n_vars, o.info, o.branches, o.x_branch, o.label,
+                      hipStreamPerThread)) != EZPZ_OK)
         return rc;
-    HIP_TRY(hipMemcpy(P->x_all.p, x, batch * samples * n_vars * sizeof(double), hipMemcpyHostToDevice));
-    if (ok) HIP_TRY(hipMemcpy(P->ok_all.p, ok, batch * samples, hipMemcpyHostToDevice));
-    if ((rc = cluster(*P, r, device_limits(device).cus, P->x_all.p, ok ? P->ok_all.p : nullptr, batch, samples, n_vars, P->info_out.p,
-                      P->branches_out.p, P->x_branch_out.p, keep_label ? P->label_out.p : nullptr, hipStreamPerThread)) != EZPZ_OK)
-        return rc;
-    return copy_back(*P, r, batch, samples, n_vars, info, branches, x_branch, keep_label);
+    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
+    return io.copy_back(P->host_stage);
 }
 
 int ezpz_system_solve_branches_device(EzpzSystem* sys, const double* x0_dev, const EzpzMcDist* dist, const uint8_t* compare, size_t batch,
@@ -359,14 +353,15 @@ int ezpz_system_solve_branches(EzpzSystem* sys, const double* x0, const EzpzMcDi
     std::lock_guard<std::mutex> lock(P.mu);
     EZPZ_ON_DEVICE(sys->device);
     const size_t n = sys->counts.n_vars;
+    const double* x0_dev;
+    Staged io;
+    io.in(x0, batch * n, x0_dev);
+    HostOutputs o(io, r, batch, samples, n, info, branches, x_branch, keep_label);
     int rc;
-    // (the buffers of an earlier host call are idle: it waited for its launches)
-    if ((rc = P.x_all.ensure(batch * n)) != EZPZ_OK || (rc = host_outputs(P, r, batch, samples, n, keep_label != nullptr)) != EZPZ_OK) return rc;
-    HIP_TRY(hipMemcpy(P.x_all.p, x0, batch * n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = run(sys, P, r, P.x_all.p, batch, samples, cfg, P.info_out.p, P.branches_out.p, P.x_branch_out.p,
-                  keep_label ? P.label_out.p : nullptr, hipStreamPerThread)) != EZPZ_OK)
-        return rc;
-    return copy_back(P, r, batch, samples, n, info, branches, x_branch, keep_label);
+    if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
+    if ((rc = run(sys, P, r, x0_dev, batch, samples, cfg, o.info, o.branches, o.x_branch, o.label, hipStreamPerThread)) != EZPZ_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
+    return io.copy_back(P.host_stage);
 }
 
 }  // extern "C"

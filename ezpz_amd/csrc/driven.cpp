@@ -3,6 +3,7 @@
 // system), the enqueue and the host form.  Host code only: the kernels are launched by the route launchers of params.hip,
 // sweep.hip, guarded_sweep.hip (a sweep with a GuardLaunch: DESIGN.md 3j), front_params.hip and comp.hip, which instantiate them.
 #include "driven_params.hpp"
+#include "host_stage.hpp"
 
 namespace ezpz {
 
@@ -149,14 +150,7 @@ int driven_host_form(EzpzSystem* sys, const double* x0, size_t n_param, const do
             if (status[b].iterations == EZPZ_ITERATIONS_TEAM_TIMEOUT) return EZPZ_ERR_HIP;
     if (n) HIP_TRY(hipMemcpy(x_out, sys->x_dev.p, all * n * sizeof(double), hipMemcpyDeviceToHost));
     if (unsat_mask && C) HIP_TRY(hipMemcpy(unsat_mask, sys->mask_dev.p, all * C, hipMemcpyDeviceToHost));
-    if (want_log) {
-        // only the entries the kernel wrote are meaningful: n_warnings per row, capped
-        std::vector<uint64_t> log(all * (size_t)warn_cap);
-        HIP_TRY(hipMemcpy(log.data(), sys->log_dev.p, log.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        for (size_t b = 0; b < all; ++b)
-            std::memcpy(warn_log + b * warn_cap, log.data() + b * warn_cap, std::min<size_t>(status[b].n_warnings, warn_cap) * sizeof(uint64_t));
-    }
-    return EZPZ_OK;
+    return want_log ? copy_back_warn_log(warn_log, sys->log_dev.p, status, all, warn_cap) : EZPZ_OK;
 }
 
 void debug_params_line(const EzpzSystem& s, uint32_t n_param, bool in_lds, size_t copies, size_t lds_from, size_t lds_to) {

@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "driven_params.hpp"
+#include "host_stage.hpp"
 #include "list_walk_launch.hip.hpp"
 
 using namespace ezpz;
@@ -160,45 +161,36 @@ int ezpz_system_sweep_guarded(EzpzSystem* sys, const double* x0, const uint32_t*
     if (!route_in_kernel(r.sweep_route))
         return guarded_rounds(sys, x0, positions, n_param, params0, params, steps, batch, cfg, g, x_out, status, guard, params_reached,
                               unsat_mask, warn_log, warn_cap);
-    // one launch: staged through buffers of the call's own (x0 apart from x_out: a later step may gather from it again)
+    // one launch: staged through a buffer of the call's own -- this form cannot hold sys->mu across the device form it calls -- with
+    // x0 apart from x_out: a later step may gather from it again
     EZPZ_ON_DEVICE(sys->device);
     const size_t n = sys->counts.n_vars, C = sys->counts.n_cons, all = steps * batch;
     const bool want_log = warn_log && warn_cap;
-    DevBuf<double> x0_dev, p0_dev, par_dev, xo_dev, reached_dev;
-    DevBuf<EzpzStatus> st_dev;
-    DevBuf<EzpzGuardStep> guard_dev;
-    DevBuf<uint8_t> mask_dev;
-    DevBuf<uint64_t> log_dev;
+    DevBuf<unsigned char> stage;
+    const double *x0_dev, *p0_dev, *par_dev;
+    double *xo_dev, *reached_dev;
+    EzpzStatus* st_dev;
+    EzpzGuardStep* guard_dev;
+    uint8_t* mask_dev;
+    uint64_t* log_dev;
+    Staged io;
+    io.in(x0, batch * n, x0_dev);
+    io.in(params0, batch * n_param, p0_dev);
+    io.in(params, all * n_param, par_dev);
+    io.out(x_out, all * n, xo_dev, Staged::kPlaced);  // (the device form wants x_out whatever n is)
+    io.out(status, all, st_dev);
+    io.out(guard, all, guard_dev);
+    io.out(params_reached, all * n_param, reached_dev);
+    io.out(unsat_mask, all * C, mask_dev);
+    io.room(want_log ? all * warn_cap : 0, log_dev);  // (the log goes home by copy_back_warn_log)
     int rc;
-    if ((rc = x0_dev.ensure(batch * std::max<size_t>(n, 1))) != EZPZ_OK) return rc;
-    if ((rc = p0_dev.ensure(batch * n_param)) != EZPZ_OK) return rc;
-    if ((rc = par_dev.ensure(all * n_param)) != EZPZ_OK) return rc;
-    if ((rc = xo_dev.ensure(all * std::max<size_t>(n, 1))) != EZPZ_OK) return rc;
-    if ((rc = reached_dev.ensure(all * n_param)) != EZPZ_OK) return rc;
-    if ((rc = st_dev.ensure(all)) != EZPZ_OK) return rc;
-    if ((rc = guard_dev.ensure(all)) != EZPZ_OK) return rc;
-    if (unsat_mask && (rc = mask_dev.ensure(all * std::max<size_t>(C, 1))) != EZPZ_OK) return rc;
-    if (want_log && (rc = log_dev.ensure(all * warn_cap)) != EZPZ_OK) return rc;
-    if (n) HIP_TRY(hipMemcpy(x0_dev.p, x0, batch * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p0_dev.p, params0, batch * n_param * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(par_dev.p, params, all * n_param * sizeof(double), hipMemcpyHostToDevice));
-    rc = ezpz_system_sweep_guarded_device(sys, x0_dev.p, positions, n_param, p0_dev.p, par_dev.p, steps, batch, cfg, &g, xo_dev.p, st_dev.p,
-                                          guard_dev.p, reached_dev.p, unsat_mask ? mask_dev.p : nullptr, want_log ? log_dev.p : nullptr,
-                                          warn_cap, hipStreamPerThread);
+    if ((rc = io.reserve(stage)) != EZPZ_OK || (rc = io.upload(stage)) != EZPZ_OK) return rc;
+    rc = ezpz_system_sweep_guarded_device(sys, x0_dev, positions, n_param, p0_dev, par_dev, steps, batch, cfg, &g, xo_dev, st_dev, guard_dev,
+                                          reached_dev, mask_dev, log_dev, warn_cap, hipStreamPerThread);
     if (rc != EZPZ_OK) return rc;
     HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
-    HIP_TRY(hipMemcpy(status, st_dev.p, all * sizeof(EzpzStatus), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(guard, guard_dev.p, all * sizeof(EzpzGuardStep), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(params_reached, reached_dev.p, all * n_param * sizeof(double), hipMemcpyDeviceToHost));
-    if (n) HIP_TRY(hipMemcpy(x_out, xo_dev.p, all * n * sizeof(double), hipMemcpyDeviceToHost));
-    if (unsat_mask && C) HIP_TRY(hipMemcpy(unsat_mask, mask_dev.p, all * C, hipMemcpyDeviceToHost));
-    if (want_log) {  // (only the entries the last attempt wrote are meaningful: n_warnings per row, capped)
-        std::vector<uint64_t> log(all * (size_t)warn_cap);
-        HIP_TRY(hipMemcpy(log.data(), log_dev.p, log.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        for (size_t b = 0; b < all; ++b)
-            std::memcpy(warn_log + b * warn_cap, log.data() + b * warn_cap, std::min<size_t>(status[b].n_warnings, warn_cap) * sizeof(uint64_t));
-    }
-    return EZPZ_OK;
+    if ((rc = io.copy_back(stage)) != EZPZ_OK) return rc;
+    return want_log ? copy_back_warn_log(warn_log, log_dev, status, all, warn_cap) : EZPZ_OK;
 }
 
 }  // extern "C"

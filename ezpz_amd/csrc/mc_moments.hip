@@ -3,6 +3,7 @@
 // run, ezpz_system_tolerance_mc_contrib in tolerance_mc.hip) and the reduction alone on a caller's samples, on a workspace the
 // process owns per device.
 #define EZPZ_MCM_KERNELS
+#include "host_stage.hpp"
 #include "mc_moments.hip.hpp"
 
 using namespace ezpz;
@@ -38,12 +39,9 @@ using namespace ezpz::mcm;
 
 constexpr uint64_t kBlock = 256;
 
-// ezpz_mc_moments has no system: its workspace is the process's (mcb::ProcessPlan), with the host form's buffers beside the sums'
+// ezpz_mc_moments has no system: its workspace is the process's (mcb::ProcessPlan), with the host form's staging beside the sums'
 struct MomentWork : mcb::Work {
-    // a round of the samples, the nominals, the outputs
-    DevBuf<double> params, m, nominal, moments_out;
-    DevBuf<uint8_t> flags, ok;
-    DevBuf<EzpzMcMomentsInfo> info_out;
+    DevBuf<unsigned char> host_stage;  // the nominals, the outputs, a round of the samples (host_stage.hpp)
 };
 using MomentPlan = mcb::ProcessPlan<MomentWork>;
 
@@ -128,25 +126,24 @@ int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags,
         if ((rc = P->order.before_overwrite()) != EZPZ_OK || (rc = W.ensure(blocks * entries_of(K), blocks)) != EZPZ_OK) return rc;
         call_stamp(MOMENTS_WORKSPACE_GROWN);
     }
-    if ((rc = W.params.ensure(chunk * n_param)) != EZPZ_OK || (rc = W.m.ensure(chunk * n_meas)) != EZPZ_OK ||
-        (rc = W.flags.ensure(flags ? chunk * n_meas : 0)) != EZPZ_OK || (rc = W.ok.ensure(ok ? chunk : 0)) != EZPZ_OK ||
-        (rc = W.nominal.ensure(K)) != EZPZ_OK || (rc = W.moments_out.ensure(entries_of(K))) != EZPZ_OK || (rc = W.info_out.ensure(1)) != EZPZ_OK)
-        return rc;
-    if (n_param) HIP_TRY(hipMemcpy(W.nominal.p, nominal_p, n_param * sizeof(double), hipMemcpyHostToDevice));
-    if (n_meas) HIP_TRY(hipMemcpy(W.nominal.p + n_param, nominal_m, n_meas * sizeof(double), hipMemcpyHostToDevice));
     if ((rc = P->order.order_behind(stream)) != EZPZ_OK) return rc;
-    MomentArgs a = args_of(W.nominal.p, W.nominal.p + n_param, samples, n_param, n_meas, W.moments_out.p, W.info_out.p);
-    a.params = W.params.p;
-    a.m = W.m.p;
-    a.flags = flags ? W.flags.p : nullptr;
-    a.ok = ok ? W.ok.p : nullptr;
+    MomentArgs a = args_of(nullptr, nullptr, samples, n_param, n_meas, nullptr, nullptr);
+    Staged io;
     for (uint64_t first = 0; first < samples; first += chunk) {
         const uint64_t count = std::min<uint64_t>(chunk, samples - first);
         if (first) HIP_TRY(hipStreamSynchronize(stream));  // (the last round has read the buffers)
-        if (n_param) HIP_TRY(hipMemcpy(W.params.p, params + first * n_param, count * n_param * sizeof(double), hipMemcpyHostToDevice));
-        if (n_meas) HIP_TRY(hipMemcpy(W.m.p, m + first * n_meas, count * n_meas * sizeof(double), hipMemcpyHostToDevice));
-        if (flags && n_meas) HIP_TRY(hipMemcpy(W.flags.p, flags + first * n_meas, count * n_meas, hipMemcpyHostToDevice));
-        if (ok) HIP_TRY(hipMemcpy(W.ok.p, ok + first, count, hipMemcpyHostToDevice));
+        // The round's list.  What the whole call shares -- the nominals, and the outputs the rounds sum into -- stands in front of the
+        // round's samples, so that every round finds it at the same place; round 0 uploads the nominals, the others keep their room.
+        io = Staged{};
+        first ? io.room(n_param, a.nominal_p) : io.in(nominal_p, n_param, a.nominal_p);
+        first ? io.room(n_meas, a.nominal_m) : io.in(nominal_m, n_meas, a.nominal_m);
+        io.out(moments, entries_of(K), a.moments);
+        io.out(info, 1, a.info);
+        io.in(params + first * n_param, count * n_param, a.params);
+        io.in(m + first * n_meas, count * n_meas, a.m);
+        io.in(flags ? flags + first * n_meas : nullptr, count * n_meas, a.flags);
+        io.in(ok ? ok + first : nullptr, count, a.ok);
+        if ((rc = io.reserve(W.host_stage)) != EZPZ_OK || (rc = io.upload(W.host_stage)) != EZPZ_OK) return rc;
         a.first = first;
         a.count = count;
         a.first_round = first == 0;
@@ -155,9 +152,7 @@ int ezpz_mc_moments(const double* params, const double* m, const uint8_t* flags,
     call_stamp(MOMENTS_LAUNCHED);
     if ((rc = P->order.record(stream)) != EZPZ_OK) return rc;
     HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipMemcpy(moments, W.moments_out.p, entries_of(K) * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(info, W.info_out.p, sizeof(EzpzMcMomentsInfo), hipMemcpyDeviceToHost));
-    return EZPZ_OK;
+    return io.copy_back(W.host_stage);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // Reference dimensions (include/ezpz_amd.h: ezpz_constraint_measure, ezpz_system_measure, _measure_response, _measure_vjp and
 // their _device forms): the host side of measure.hip.hpp's kernels -- the plan a system keeps for the last call's
-// record list (a KeptRecords, its packed table and CSR on the device, the gradient workspace, the host entries' buffers), the
+// record list (a KeptRecords, its packed table and CSR on the device, the gradient workspace, the host entries' staging), the
 // ROW / DIRECT launch, and the entry points of the C ABI.  The check of a list and its tables are in measure_tables.hpp.
-#include "system.hpp"
+#include "host_stage.hpp"
 
 #include "measure.hip.hpp"
 #include "measure_tables.hpp"
@@ -19,9 +19,7 @@ struct MeasurePlan {
     DevBuf<uint32_t> table, csr;
     bool csr_valid = false;  // `csr` is the kept list's (built when a vjp first asks for it)
     DevBuf<double> gws;      // [batch][n_meas][8]: the gradients of a response's or a vjp's first launch
-    // the host entries' buffers
-    DevBuf<double> x_in, s_in, tol_in, gm_in, m_out, grad_out, d_out, worst_out, rss_out, gx_out;
-    DevBuf<uint8_t> flags_out;
+    DevBuf<unsigned char> host_stage;  // the host entries' staging (host_stage.hpp)
 };
 
 MeasurePlan& plan_of(EzpzSystem* sys) {
@@ -207,13 +205,6 @@ int vjp_device(EzpzSystem* sys, std::vector<uint32_t>&& words, const double* x_d
     return P.list.record(stream);
 }
 
-template <class T>
-int stage_in(DevBuf<T>& buf, const T* host, size_t count) {
-    if (int rc = buf.ensure(count)) return rc;
-    HIP_TRY(hipMemcpy(buf.p, host, count * sizeof(T), hipMemcpyHostToDevice));
-    return EZPZ_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -241,19 +232,18 @@ int ezpz_system_measure(EzpzSystem* sys, const EzpzConstraint* records, size_t n
     EZPZ_ON_DEVICE(sys->device);
     MeasurePlan& P = plan_of(sys);
     const size_t n = sys->counts.n_vars, out = batch * n_meas;
+    const double* x_dev;
+    double *m_dev, *grad_dev;
+    uint8_t* flags_dev;
+    Staged io;
+    io.in(x, batch * n, x_dev);
+    io.out(m_out, out, m_dev);
+    io.out(flags_out, out, flags_dev);
+    io.out(grad_out, out * 8, grad_dev);
     int rc;
-    // (the buffers of an earlier host call are idle: it waited for its launches)
-    if ((rc = stage_in(P.x_in, x, batch * n)) != EZPZ_OK) return rc;
-    if ((rc = P.m_out.ensure(out)) != EZPZ_OK) return rc;
-    if (flags_out && (rc = P.flags_out.ensure(out)) != EZPZ_OK) return rc;
-    if (grad_out && (rc = P.grad_out.ensure(out * 8)) != EZPZ_OK) return rc;
-    if ((rc = measure_device(sys, std::move(words), P.x_in.p, batch, P.m_out.p, flags_out ? P.flags_out.p : nullptr,
-                             grad_out ? P.grad_out.p : nullptr, nullptr)) != EZPZ_OK)
-        return rc;
-    HIP_TRY(hipMemcpy(m_out, P.m_out.p, out * sizeof(double), hipMemcpyDeviceToHost));
-    if (flags_out) HIP_TRY(hipMemcpy(flags_out, P.flags_out.p, out, hipMemcpyDeviceToHost));
-    if (grad_out) HIP_TRY(hipMemcpy(grad_out, P.grad_out.p, out * 8 * sizeof(double), hipMemcpyDeviceToHost));
-    return EZPZ_OK;
+    if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
+    if ((rc = measure_device(sys, std::move(words), x_dev, batch, m_dev, flags_dev, grad_dev, nullptr)) != EZPZ_OK) return rc;
+    return io.copy_back(P.host_stage);  // (blocking copies on the null stream: they wait for its launches)
 }
 
 int ezpz_system_measure_response_device(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x_dev,
@@ -283,21 +273,20 @@ int ezpz_system_measure_response(EzpzSystem* sys, const EzpzConstraint* records,
     EZPZ_ON_DEVICE(sys->device);
     MeasurePlan& P = plan_of(sys);
     const size_t n = sys->counts.n_vars, out = batch * n_meas;
+    const double *x_dev, *S_dev, *tol_dev;
+    double *D_dev, *worst_dev, *rss_dev;
+    Staged io;
+    io.in(x, batch * n, x_dev);
+    io.in(S, batch * n_param * n, S_dev);
+    io.in(tol, n_param, tol_dev);
+    io.out(D_out, out * n_param, D_dev);
+    io.out(worst_out, out, worst_dev);  // (both or neither: check_response)
+    io.out(rss_out, out, rss_dev);
     int rc;
-    if ((rc = stage_in(P.x_in, x, batch * n)) != EZPZ_OK) return rc;
-    if ((rc = stage_in(P.s_in, S, batch * n_param * n)) != EZPZ_OK) return rc;
-    if (tol && (rc = stage_in(P.tol_in, tol, n_param)) != EZPZ_OK) return rc;
-    if ((rc = P.d_out.ensure(out * n_param)) != EZPZ_OK) return rc;
-    if (worst_out && ((rc = P.worst_out.ensure(out)) != EZPZ_OK || (rc = P.rss_out.ensure(out)) != EZPZ_OK)) return rc;
-    if ((rc = response_device(sys, std::move(words), P.x_in.p, P.s_in.p, n_param, batch, tol ? P.tol_in.p : nullptr, P.d_out.p,
-                              worst_out ? P.worst_out.p : nullptr, worst_out ? P.rss_out.p : nullptr, nullptr)) != EZPZ_OK)
+    if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
+    if ((rc = response_device(sys, std::move(words), x_dev, S_dev, n_param, batch, tol_dev, D_dev, worst_dev, rss_dev, nullptr)) != EZPZ_OK)
         return rc;
-    HIP_TRY(hipMemcpy(D_out, P.d_out.p, out * n_param * sizeof(double), hipMemcpyDeviceToHost));
-    if (worst_out) {
-        HIP_TRY(hipMemcpy(worst_out, P.worst_out.p, out * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(rss_out, P.rss_out.p, out * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return EZPZ_OK;
+    return io.copy_back(P.host_stage);
 }
 
 int ezpz_system_measure_vjp_device(EzpzSystem* sys, const EzpzConstraint* records, size_t n_meas, const double* x_dev,
@@ -319,13 +308,16 @@ int ezpz_system_measure_vjp(EzpzSystem* sys, const EzpzConstraint* records, size
     EZPZ_ON_DEVICE(sys->device);
     MeasurePlan& P = plan_of(sys);
     const size_t n = sys->counts.n_vars;
+    const double *x_dev, *gm_dev;
+    double* gx_dev;
+    Staged io;
+    io.in(x, batch * n, x_dev);
+    io.in(grad_m, batch * n_meas, gm_dev);
+    io.out(grad_x_out, batch * n, gx_dev);
     int rc;
-    if ((rc = stage_in(P.x_in, x, batch * n)) != EZPZ_OK) return rc;
-    if ((rc = stage_in(P.gm_in, grad_m, batch * n_meas)) != EZPZ_OK) return rc;
-    if ((rc = P.gx_out.ensure(batch * n)) != EZPZ_OK) return rc;
-    if ((rc = vjp_device(sys, std::move(words), P.x_in.p, P.gm_in.p, batch, P.gx_out.p, nullptr)) != EZPZ_OK) return rc;
-    HIP_TRY(hipMemcpy(grad_x_out, P.gx_out.p, batch * n * sizeof(double), hipMemcpyDeviceToHost));
-    return EZPZ_OK;
+    if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
+    if ((rc = vjp_device(sys, std::move(words), x_dev, gm_dev, batch, gx_dev, nullptr)) != EZPZ_OK) return rc;
+    return io.copy_back(P.host_stage);
 }
 
 }  // extern "C"

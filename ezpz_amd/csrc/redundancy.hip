@@ -1,6 +1,6 @@
 // Redundancy analysis (include/ezpz_amd.h: ezpz_system_redundancy): the host side of redundancy.hip.hpp's kernel -- the row tables
 // beside FreedomAnalysis' component tables, the LANE / TEAM launch and the two entry points of the C ABI.
-#include "system.hpp"
+#include "host_stage.hpp"
 
 #include "redundancy.hip.hpp"
 
@@ -19,10 +19,7 @@ struct RedundancyPlan {
     KeptList focus;
     DevBuf<double> x_int, jv, r, gws;
     DevBuf<uint8_t> row_status;
-    // the host entry's buffers
-    DevBuf<double> x_in;
-    DevBuf<uint8_t> con_out, row_out, group_out;
-    DevBuf<uint32_t> rank_out;
+    DevBuf<unsigned char> host_stage;  // the host entry's staging (host_stage.hpp)
 };
 
 RedundancyPlan& plan_of(EzpzSystem* sys) {
@@ -250,21 +247,19 @@ int ezpz_system_redundancy(EzpzSystem* sys, const double* x, size_t batch, const
     const size_t n = sys->counts.n_vars, m = sys->counts.n_rows, n_cs = sys->host_cs.size();
     if (n == 0 || m == 0) return EZPZ_ERR_EMPTY_SYSTEM;
     RedundancyPlan& R = plan_of(sys);
+    const double* x_dev;
+    uint8_t *con_dev, *row_dev, *group_dev;
+    uint32_t* rank_dev;
+    Staged io;
+    io.in(x, batch * n, x_dev);
+    io.out(con_status, batch * n_cs, con_dev);
+    io.out(row_status, batch * m, row_dev);
+    io.out(rank, batch, rank_dev);
+    io.out(group, batch * n_focus * n_cs, group_dev);
     int rc;
-    // (the buffers of an earlier call of this entry are idle: it waited for its launch)
-    if ((rc = R.x_in.ensure(batch * n)) != EZPZ_OK) return rc;
-    if ((rc = R.con_out.ensure(batch * n_cs)) != EZPZ_OK) return rc;
-    if ((rc = R.row_out.ensure(batch * m)) != EZPZ_OK) return rc;
-    if ((rc = R.rank_out.ensure(batch)) != EZPZ_OK) return rc;
-    if ((rc = R.group_out.ensure(batch * n_focus * n_cs)) != EZPZ_OK) return rc;
-    HIP_TRY(hipMemcpy(R.x_in.p, x, batch * n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = redundancy_device(sys, R.x_in.p, batch, c, R.con_out.p, R.row_out.p, R.rank_out.p, focus, n_focus, R.group_out.p, nullptr)) != EZPZ_OK)
-        return rc;
-    HIP_TRY(hipMemcpy(con_status, R.con_out.p, batch * n_cs, hipMemcpyDeviceToHost));
-    if (row_status) HIP_TRY(hipMemcpy(row_status, R.row_out.p, batch * m, hipMemcpyDeviceToHost));
-    if (rank) HIP_TRY(hipMemcpy(rank, R.rank_out.p, batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (n_focus) HIP_TRY(hipMemcpy(group, R.group_out.p, batch * n_focus * n_cs, hipMemcpyDeviceToHost));
-    return EZPZ_OK;
+    if ((rc = io.reserve(R.host_stage)) != EZPZ_OK || (rc = io.upload(R.host_stage)) != EZPZ_OK) return rc;
+    if ((rc = redundancy_device(sys, x_dev, batch, c, con_dev, row_dev, rank_dev, focus, n_focus, group_dev, nullptr)) != EZPZ_OK) return rc;
+    return io.copy_back(R.host_stage);  // (blocking copies on the null stream: they wait for its launch)
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // Dimension targets (include/ezpz_amd.h: ezpz_seek_step, ezpz_system_seek_targets and its _device form): the host side
 // of seek.hip.hpp's kernels -- the check of a request, the plan a system keeps (the rounds' workspace, the tables, the host form's
-// buffers) and the rounds.  A round is ezpz_system_solve_batch_params_device -> ezpz_system_param_sensitivity_device ->
+// staging) and the rounds.  A round is ezpz_system_solve_batch_params_device -> ezpz_system_param_sensitivity_device ->
 // ezpz_system_measure_device -> ezpz_system_measure_response_device -> seek_step_kernel -> seek_commit_kernel, all on the caller's
 // stream: the four entries are those entries themselves, with their routes, their locks and their ordering.
 #include "driven_params.hpp"
+#include "host_stage.hpp"
 #include "measure_tables.hpp"
 #include "seek.hip.hpp"
 
@@ -31,9 +32,7 @@ struct SeekPlan {
     DevBuf<uint32_t> sens_status;
     DevBuf<uint8_t> flags, verdict;
     DevBuf<unsigned int> active;
-    // the host form's buffers
-    DevBuf<double> x_io, params0_in, targets_in, params_out, m_out, trace_out;
-    DevBuf<EzpzSeekInfo> info_out;
+    DevBuf<unsigned char> host_stage;  // the host form's staging (host_stage.hpp)
 };
 
 SeekPlan& plan_of(EzpzSystem* sys) {
@@ -283,28 +282,27 @@ int ezpz_system_seek_targets(EzpzSystem* sys, const double* x0, const uint32_t* 
     const size_t n = sys->counts.n_vars, trace_row = (size_t)r.c.max_iterations + 1, chunk = r.chunk;
     int rc;
     if ((rc = prepare(P, r, n, n_param, n_meas)) != EZPZ_OK) return rc;
-    // (the buffers of an earlier host call are idle: it waited for its launches)
-    if ((rc = P.x_io.ensure(chunk * n)) != EZPZ_OK || (rc = P.params0_in.ensure(chunk * n_param)) != EZPZ_OK ||
-        (rc = P.targets_in.ensure(chunk * n_meas)) != EZPZ_OK || (rc = P.params_out.ensure(chunk * n_param)) != EZPZ_OK ||
-        (rc = P.m_out.ensure(chunk * n_meas)) != EZPZ_OK || (rc = P.info_out.ensure(chunk)) != EZPZ_OK ||
-        (cost_trace_out && (rc = P.trace_out.ensure(chunk * trace_row)) != EZPZ_OK))
-        return rc;
     if ((rc = P.order.order_behind(st)) != EZPZ_OK) return rc;
     for (size_t first = 0; first < batch; first += chunk) {
         const size_t count = std::min<size_t>(chunk, batch - first);
-        if (n) HIP_TRY(hipMemcpy(P.x_io.p, x0 + first * n, count * n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(P.params0_in.p, params0 + first * n_param, count * n_param * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(P.targets_in.p, targets + first * n_meas, count * n_meas * sizeof(double), hipMemcpyHostToDevice));
-        if ((rc = run_chunk(sys, P, r, P.x_io.p, positions, n_param, P.params0_in.p, records, n_meas, P.targets_in.p, count, P.params_out.p,
-                            P.x_io.p, P.m_out.p, P.info_out.p, cost_trace_out ? P.trace_out.p : nullptr, true, st)) != EZPZ_OK)
+        // the chunk's list (the first chunk is the largest: only its reserve() allocates); x0 and x_out share a place
+        const double *p0_dev, *targets_dev;
+        double *x_dev, *p_dev, *m_dev, *trace_dev;
+        EzpzSeekInfo* info_dev;
+        Staged io;
+        io.inout(x0 + first * n, count * n, x_out + first * n, count * n, x_dev, Staged::kPlaced);  // (the solve entry wants its x whatever n is)
+        io.in(params0 + first * n_param, count * n_param, p0_dev);
+        io.in(targets + first * n_meas, count * n_meas, targets_dev);
+        io.out(params_out + first * n_param, count * n_param, p_dev);
+        io.out(m_out + first * n_meas, count * n_meas, m_dev);
+        io.out(info_out + first, count, info_dev);
+        io.out(cost_trace_out ? cost_trace_out + first * trace_row : nullptr, count * trace_row, trace_dev);
+        if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
+        if ((rc = run_chunk(sys, P, r, x_dev, positions, n_param, p0_dev, records, n_meas, targets_dev, count, p_dev, x_dev, m_dev, info_dev,
+                            trace_dev, true, st)) != EZPZ_OK)
             return rc;
         HIP_TRY(hipStreamSynchronize(st));
-        if (n) HIP_TRY(hipMemcpy(x_out + first * n, P.x_io.p, count * n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(params_out + first * n_param, P.params_out.p, count * n_param * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(m_out + first * n_meas, P.m_out.p, count * n_meas * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(info_out + first, P.info_out.p, count * sizeof(EzpzSeekInfo), hipMemcpyDeviceToHost));
-        if (cost_trace_out)
-            HIP_TRY(hipMemcpy(cost_trace_out + first * trace_row, P.trace_out.p, count * trace_row * sizeof(double), hipMemcpyDeviceToHost));
+        if ((rc = io.copy_back(P.host_stage)) != EZPZ_OK) return rc;
     }
     call_stamp(SEEK_LAUNCHED);
     return P.order.record(st);

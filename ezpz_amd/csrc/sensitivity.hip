@@ -2,9 +2,10 @@
 // ezpz_constraint_param_derivative (include/ezpz_amd.h).  The kernels are in sensitivity.hip.hpp and are
 // instantiated here only; this file is the host side: the plan of a `positions` list -- connected components by union-find,
 // the shape of every component that holds a listed constraint, its records, elimination order, envelope and product lists --
-// kept on the system (a KeptList, like the params overlay's) with its device tables, workspace and the host entry's buffers.
+// kept on the system (a KeptList, like the params overlay's) with its device tables, workspace and the host entry's staging.
 // The check of a list is the one every driven entry shares (driven_params.hpp: driven_slot_map).
 #include "driven_params.hpp"
+#include "host_stage.hpp"
 #include "sensitivity.hip.hpp"
 
 #include <numeric>
@@ -29,9 +30,7 @@ struct SensPlan {
     DevBuf<SensRec> recs;
     DevBuf<uint32_t> u32;
     DevBuf<double> ws;
-    // the host entry's buffers
-    DevBuf<double> x, par, S;
-    DevBuf<uint32_t> st;
+    DevBuf<unsigned char> host_stage;  // the host entry's staging (host_stage.hpp)
 };
 
 struct Ids {
@@ -486,22 +485,23 @@ int ezpz_system_param_sensitivity(EzpzSystem* sys, const double* x, const uint32
         if (!sys->sens) sys->sens = std::make_shared<SensPlan>();
     }
     SensPlan& P = *static_cast<SensPlan*>(sys->sens.get());
-    const size_t n = sys->counts.n_vars, nb = std::max<size_t>(batch, 1), row = n_param * n;
+    const size_t n = sys->counts.n_vars;
+    const double *x_dev, *par_dev;
+    double* S_dev;
+    uint32_t *st_dev, *deg_dev;
+    Staged io;
+    io.in(x, n_param ? batch * n : 0, x_dev);  // (without dimensions x is not read, and may be absent)
+    io.in(params, batch * n_param, par_dev);
+    io.out(S_out, batch * n_param * n, S_dev, Staged::kPlaced);  // (the device form wants S wherever there are dimensions, whatever n is)
+    io.out(status_out, batch, st_dev);
+    io.out(degenerate_count_out, n_param ? batch : 0, deg_dev);
     int rc;
-    if ((rc = P.x.ensure(nb * std::max<size_t>(n, 1))) != EZPZ_OK) return rc;
-    if ((rc = P.st.ensure(2 * nb)) != EZPZ_OK) return rc;
-    if ((rc = P.S.ensure(nb * std::max<size_t>(row, 1))) != EZPZ_OK) return rc;
-    if (params && (rc = P.par.ensure(nb * std::max<size_t>(n_param, 1))) != EZPZ_OK) return rc;
-    if (batch && n && n_param) HIP_TRY(hipMemcpy(P.x.p, x, batch * n * sizeof(double), hipMemcpyHostToDevice));
-    if (batch && params && n_param) HIP_TRY(hipMemcpy(P.par.p, params, batch * n_param * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
     // (errors of the request are the device form's: nothing has been enqueued then, and no output written)
-    rc = ezpz_system_param_sensitivity_device(sys, P.x.p, positions, n_param, params ? P.par.p : nullptr, batch, lambda, P.S.p, P.st.p,
-                                              P.st.p + nb, hipStreamPerThread);
+    rc = ezpz_system_param_sensitivity_device(sys, x_dev, positions, n_param, par_dev, batch, lambda, S_dev, st_dev, deg_dev, hipStreamPerThread);
     if (rc != EZPZ_OK || batch == 0) return rc;
     HIP_TRY(hipStreamSynchronize(hipStreamPerThread));
-    HIP_TRY(hipMemcpy(status_out, P.st.p, batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (row) HIP_TRY(hipMemcpy(S_out, P.S.p, batch * row * sizeof(double), hipMemcpyDeviceToHost));
-    if (degenerate_count_out && n_param) HIP_TRY(hipMemcpy(degenerate_count_out, P.st.p + nb, batch * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if ((rc = io.copy_back(P.host_stage)) != EZPZ_OK) return rc;
     if (degenerate_count_out && !n_param) std::memset(degenerate_count_out, 0, batch * sizeof(uint32_t));
     return EZPZ_OK;
 }

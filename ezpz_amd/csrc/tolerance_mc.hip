@@ -11,9 +11,10 @@
 //                the tail reads them; the tail's behind_run() behind the last round
 //   run_sobol()  (SobolOut alone) k' + 2 sub-rounds a round into the round's rows, the reduction behind A's, mc_sobol.hip's sums
 //                behind the last one and its closing kernel behind the last round
-// A host form is its run between the upload of x0 and the copies back of its Staged outputs.  A new kind is a tail, its two
+// A host form is its run between the upload of x0 and the copies back of its staged outputs (host_stage.hpp).  A new kind is a tail, its two
 // extern "C" entries and, where it has a workspace, a field of McPlan.
 #include "driven_params.hpp"
+#include "host_stage.hpp"
 #include "mc_effects.hip.hpp"
 #include "mc_factorial.hip.hpp"
 #include "mc_moments.hip.hpp"
@@ -48,9 +49,8 @@ struct McPlan {
     DevBuf<uint8_t> flags, ok;
     DevBuf<EzpzStatus> status;
     DevBuf<unsigned int> ticket;
-    // the host forms' buffers: x0, and every output of the call side by side (Staged below)
-    DevBuf<double> x0_in;
-    DevBuf<unsigned char> host_out;
+    // the host forms' staging (host_stage.hpp): x0 and every output of the call
+    DevBuf<unsigned char> host_stage;
     // the run with contributors: the moments' workspace
     mcb::Work moment_work;
     // the run with Sobol indices: the round's rows -- [k + 2][chunk][n_meas] values and flags, [k + 2][chunk] ok bytes
@@ -702,41 +702,6 @@ int run_sobol(McPlan& P, const Request& r, const Call& c, const Keep& keep, cons
     return P.order.record(stream);
 }
 
-// A host form's outputs.  add() gives each a place, in order, in one device buffer; reserve() makes the buffer hold them and hands
-// out the places; copy_back() brings every output home.  An entry of no elements takes no room, has no place (NULL) and is not
-// copied.
-struct Staged {
-    struct Entry {
-        void* host;
-        size_t count, size;
-        void* dev;                        // the caller's device pointer for this entry: a T**
-        void (*set)(void*, unsigned char*);  // ... and how to set it
-        size_t offset;
-    };
-    std::vector<Entry> entries;
-
-    template <class T>
-    void add(T* host, size_t count, T*& dev) {
-        entries.push_back(Entry{host, count, sizeof(T), &dev, [](void* slot, unsigned char* p) { *static_cast<T**>(slot) = reinterpret_cast<T*>(p); }, 0});
-    }
-    int reserve(DevBuf<unsigned char>& buf) {
-        size_t bytes = 0;
-        for (Entry& e : entries) {
-            e.offset = bytes;
-            bytes += (e.count * e.size + 255) / 256 * 256;  // (every place as aligned as an allocation of its own)
-        }
-        // (the buffer of an earlier host call is idle: it waited for its launches)
-        if (int rc = buf.ensure(bytes)) return rc;
-        for (Entry& e : entries) e.set(e.dev, e.count ? buf.p + e.offset : nullptr);
-        return EZPZ_OK;
-    }
-    int copy_back(const DevBuf<unsigned char>& buf) const {
-        for (const Entry& e : entries)
-            if (e.count) HIP_TRY(hipMemcpy(e.host, buf.p + e.offset, e.count * e.size, hipMemcpyDeviceToHost));
-        return EZPZ_OK;
-    }
-};
-
 // Every entry, in the order the argument errors take precedence: the run's checks, the tail's, nothing to do for no samples -- up to
 // here no output and nothing of the plan is touched -- then the run on the plan with its mutex held and the system's device current
 // (SobolOut's run is run_sobol()).  A host form (`c`, `keep` and `tail` hold host pointers) is that run between the upload of x0
@@ -761,18 +726,17 @@ int entry(const Call& c, const Keep& keep, Tail& tail, bool host) {
     const size_t n = c.sys->counts.n_vars;
     Call d = c;
     Tail dev = tail;
-    Staged out;
-    out.add(c.hist, c.n_meas * (r.hist_bins ? r.hist_bins + 2 : 0), d.hist);
-    dev.outputs(c.n_param, c.n_meas, [&](auto*& p, size_t count) { out.add(p, count, p); });
-    out.add(c.stats, c.n_meas, d.stats);
-    out.add(c.totals, 1, d.totals);
+    Staged io;
+    io.in(c.x0, n, d.x0, Staged::kPlaced);  // (the measure entry wants its x whatever n is)
+    io.out(c.hist, c.n_meas * (r.hist_bins ? r.hist_bins + 2 : 0), d.hist);
+    dev.outputs(c.n_param, c.n_meas, [&](auto*& p, size_t count) { io.out(p, count, p); });
+    io.out(c.stats, c.n_meas, d.stats);
+    io.out(c.totals, 1, d.totals);
     int rc;
-    if ((rc = P.x0_in.ensure(n)) != EZPZ_OK || (rc = out.reserve(P.host_out)) != EZPZ_OK) return rc;
-    if (n) HIP_TRY(hipMemcpy(P.x0_in.p, c.x0, n * sizeof(double), hipMemcpyHostToDevice));
-    d.x0 = P.x0_in.p;
+    if ((rc = io.reserve(P.host_stage)) != EZPZ_OK || (rc = io.upload(P.host_stage)) != EZPZ_OK) return rc;
     if ((rc = run_on(d, dev)) != EZPZ_OK) return rc;
     HIP_TRY(hipStreamSynchronize(c.stream));
-    return out.copy_back(P.host_out);
+    return io.copy_back(P.host_stage);
 }
 
 }  // namespace
