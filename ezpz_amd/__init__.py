@@ -11,7 +11,13 @@ from .api import (BranchConfig, BranchResult, cluster_branches, McDist, McResult
                   MixedBatch, MultiSystem, NonLinearSystemError, RawResult, RedundancyConfig, SolveOutcome, SolveOutcomeFreedomAnalysis, System, TEAM_AUTO_LATENCY, TEAM_AUTO_LISTS, TEAM_BATCH_LANES, TEAM_FRONTS, TEAM_LATENCY_PHASES, TEAM_LATENCY_RECORDS, TEAM_LATENCY_WAVE, Warning, WarningContent, analyze, constraint_has_param, constraint_measure, constraint_param_derivative, device_count, launch_policy, solve,
                   host_register, host_unregister, resolve_sides, solve_analysis, specialized_source, solve_batch, solve_batch_mixed, solve_batch_mixed_multi, solve_batch_multi, solve_records, stack_records)
 
+from .sketch_image import (REFERENCE_LAYERS, ComposeLayer, DrawItem, ImageConfig, ImageInfo, ImageView, SketchImage, compose, fit_view, items_from_problem,
+                           save_sketch_png, sketch_image, sketch_image_device, sketch_image_host)
+from ._lib import DRAW_ITEM_DTYPE, IMAGE_INFO_DTYPE
+
 __all__ = [
+    "REFERENCE_LAYERS", "ComposeLayer", "DrawItem", "ImageConfig", "ImageInfo", "ImageView", "SketchImage", "compose", "fit_view", "items_from_problem",
+    "save_sketch_png", "sketch_image", "sketch_image_device", "sketch_image_host", "DRAW_ITEM_DTYPE", "IMAGE_INFO_DTYPE",
     "Angle", "AngleKind", "CircleSide", "Config", "Constraint", "ConstraintRequest", "DatumCircle", "DatumCircularArc",
     "DatumDistance", "DatumLineSegment", "DatumPoint", "FailureOutcome", "FreedomAnalysis", "GuardConfig", "IdGenerator", "LineSide",
     "MixedBatch", "MultiSystem", "NonLinearSystemError", "RawResult", "RedundancyConfig", "SolveOutcome", "SolveOutcomeFreedomAnalysis", "System", "TEAM_AUTO_LATENCY", "TEAM_AUTO_LISTS", "TEAM_BATCH_LANES", "TEAM_FRONTS", "TEAM_LATENCY_PHASES", "TEAM_LATENCY_RECORDS", "TEAM_LATENCY_WAVE", "Warning", "WarningContent", "analyze", "constraint_has_param", "constraint_measure", "constraint_param_derivative",

@@ -164,6 +164,21 @@ class CViewport(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class CImageView(C.Structure):  # EzpzImageView
+    _fields_ = [("x_min", C.c_double), ("y_min", C.c_double), ("scale", C.c_double), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+DRAW_POINT, DRAW_SEGMENT, DRAW_CIRCLE, DRAW_ARC = 0, 1, 2, 3  # EZPZ_DRAW_*
+DRAW_FILL = 1
+IMAGE_MAX_LAYERS, IMAGE_MAX_SIDE = 8, 16384  # EZPZ_IMAGE_MAX_*
+DRAW_ITEM_DTYPE = np.dtype([("kind", "<u2"), ("layer", "u1"), ("flags", "u1"), ("ids", "<u4", (6,)), ("reserved", "<u4"),
+                            ("half_width", "<f8")])  # EzpzDrawItem
+IMAGE_INFO_DTYPE = np.dtype([("variants", "<u8"), ("masked", "<u8"), ("items_skipped", "<u8"), ("increments", "<u8")])  # EzpzImageInfo
+COMPOSE_LAYER_DTYPE = np.dtype({"names": ["rgb", "opacity", "a_min", "full_at"], "formats": [("u1", (3,)), "u1", "u1", "<u4"],
+                                "offsets": [0, 3, 4, 8], "itemsize": 12})  # EzpzComposeLayer
+assert C.sizeof(CImageView) == 32 and DRAW_ITEM_DTYPE.itemsize == 40 and IMAGE_INFO_DTYPE.itemsize == 32
+
+
 class CRedundancyConfig(C.Structure):
     _fields_ = [("rank_tol", C.c_double), ("conflict_tol", C.c_double), ("group_tol", C.c_double)]
 
@@ -214,6 +229,9 @@ EXPORTS = [
     "ezpz_default_seek_config", "ezpz_seek_step", "ezpz_system_seek_targets", "ezpz_system_seek_targets_device",
     "ezpz_default_branch_config", "ezpz_branch_cluster", "ezpz_branch_cluster_device", "ezpz_system_solve_branches",
     "ezpz_system_solve_branches_device",
+    "ezpz_sketch_image", "ezpz_sketch_image_device", "ezpz_sketch_image_host", "ezpz_sketch_compose",
+    "ezpz_system_tolerance_mc_image", "ezpz_system_tolerance_mc_image_device",
+    "ezpz_problem_num_lines", "ezpz_problem_line",
 ]
 
 _lib = None
@@ -334,6 +352,18 @@ def lib():
     L.ezpz_system_tolerance_mc_factorial.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp] * 8
     L.ezpz_system_tolerance_mc_factorial_device.restype = C.c_int
     L.ezpz_system_tolerance_mc_factorial_device.argtypes = L.ezpz_system_tolerance_mc_factorial.argtypes + [vp]
+    L.ezpz_sketch_image.restype = C.c_int
+    L.ezpz_sketch_image.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(CImageView), u32, C.c_int, vp, vp]
+    L.ezpz_sketch_image_host.restype = C.c_int
+    L.ezpz_sketch_image_host.argtypes = L.ezpz_sketch_image.argtypes
+    L.ezpz_sketch_image_device.restype = C.c_int
+    L.ezpz_sketch_image_device.argtypes = L.ezpz_sketch_image.argtypes + [vp]
+    L.ezpz_sketch_compose.restype = C.c_int
+    L.ezpz_sketch_compose.argtypes = [vp, C.POINTER(CImageView), u32, vp, vp, vp]
+    L.ezpz_system_tolerance_mc_image.restype = C.c_int
+    L.ezpz_system_tolerance_mc_image.argtypes = L.ezpz_system_tolerance_mc.argtypes + [vp, sz, C.POINTER(CImageView), u32, vp, vp]
+    L.ezpz_system_tolerance_mc_image_device.restype = C.c_int
+    L.ezpz_system_tolerance_mc_image_device.argtypes = L.ezpz_system_tolerance_mc_image.argtypes + [vp]
     L.ezpz_default_seek_config.argtypes = [C.POINTER(CSeekConfig)]
     L.ezpz_seek_step.restype = C.c_int
     L.ezpz_seek_step.argtypes = [sz, sz, vp, vp, vp, vp, C.POINTER(CSeekConfig), C.c_double, vp, vp, vp]
@@ -485,5 +515,9 @@ def lib():
     L.ezpz_problem_num_labels.argtypes = [vp, C.c_int]
     L.ezpz_problem_label.restype = C.c_char_p
     L.ezpz_problem_label.argtypes = [vp, C.c_int, sz]
+    L.ezpz_problem_num_lines.restype = sz
+    L.ezpz_problem_num_lines.argtypes = [vp]
+    L.ezpz_problem_line.restype = C.c_int
+    L.ezpz_problem_line.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
     _lib = L
     return L

@@ -17,7 +17,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_SEQUENCE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, MC_FACTORIAL_DTYPE, MC_FACTORIAL_MAX_CORNERS, MC_FACTORIAL_MAX_MEAS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
+from ._lib import PARAMS_ROUTES, SENSITIVITY_ROUTES, SWEEP_ROUTE_NAMES, CONSTRAINT_DTYPE, GUARD_STEP_DTYPE, BRANCH_DTYPE, BRANCH_INFO_DTYPE, MC_DIST_DTYPE, MC_SEQUENCE, MC_MOMENT_MAX, MC_MOMENTS_INFO_DTYPE, MC_STATS_DTYPE, MC_TOTALS_DTYPE, IMAGE_INFO_DTYPE, STATUS_DTYPE, SEEK_INFO_DTYPE, SEEK_STATUS, SEEK_STEP, CBranchConfig, CConfig, CGuardConfig, CMcConfig, CMcContribConfig, CSobolConfig, SOBOL_MAX, SOBOL_SEED_B, CMcQuantileConfig, CMcEffectConfig, MC_EFFECT_MAX_BINS, MC_EFFECT_MAX_CELLS, MC_EFFECT_MAX_DIM, MC_QUANTILE_DTYPE, MC_QUANTILE_MAX_MEAS, MC_QUANTILE_MAX_PROBS, MC_FACTORIAL_DTYPE, MC_FACTORIAL_MAX_CORNERS, MC_FACTORIAL_MAX_MEAS, CSeekConfig, COutcome, CRedundancyConfig, CSensitivityPlan, CSweepPlan, CSystemInfo, CWarning, lib
 
 Id = int
 
@@ -1226,7 +1226,7 @@ class System:
                      chunk: int = 0, keep: bool = False, config: Optional[Config] = None, contributors: bool = False,
                      pivot_rel: Optional[float] = None, quantiles=None, quantile_z: float = 0.0,
                      effects: Optional["EffectsConfig"] = None, factorial: bool = False, keep_coef: bool = False,
-                     sampling: str = "philox") -> "McResult":
+                     sampling: str = "philox", image=None) -> "McResult":
         """`ezpz_system_tolerance_mc`: every driving dimension (`positions`, one `McDist` each) drawn `samples` times, every variant
         solved from x0 [n_vars] -- the nominal solution -- the reference dimensions `records` read off each answer, and their
         statistics reduced on the device.  nominal [n_param]: the values the deviations are added to (None: the system's own);
@@ -1248,10 +1248,13 @@ class System:
         coefficients per record.  Not together with contributors, quantiles or effects.
         sampling: "philox" -- the list as given -- or "sequence": every UNIFORM and NORMAL dimension of this call drawn from the
         low-discrepancy sequence (`McDist.uniform(..., sequence=True)`): for a smooth response mean, std and what is built on them
-        converge nearly as 1 / samples; tail yields gain little.  At most 64 positions up to the last such dimension, 2^32 samples."""
+        converge nearly as 1 / samples; tail yields gain little.  At most 64 positions up to the last such dimension, 2^32 samples.
+        image: a `sketch_image.ImageConfig(items, view, n_layers)` -- the same run through `ezpz_system_tolerance_mc_image`: every
+        round's solved variants drawn on the device into `image` (uint32 [n_layers, height, width]; a variant that did not solve
+        draws nothing), with `image_info`; no value vector leaves the device.  Not together with the other kinds."""
         if sampling != "philox":
             dists = _with_sampling(dists, sampling)
-        kind = _mc_kind(contributors, quantiles, effects, factorial)
+        kind = _mc_kind(contributors, quantiles, effects, factorial, image)
         x0 = self._mc_x0(x0)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
@@ -1263,7 +1266,7 @@ class System:
                 np.zeros(samples, np.uint8)) if keep else (None,) * 4
         cfg = (config or Config())._c()
         kind = kind(self, pos, d, nominal, k, samples, pivot_rel=pivot_rel, quantiles=quantiles, quantile_z=quantile_z, effects=effects,
-                    keep_coef=keep_coef)
+                    keep_coef=keep_coef, image=image)
         args = (self._h, _ptr(x0), _ptr(pos), n_param, _ptr(d), _ptr(nominal), _ptr(recs), k, _ptr(lim_lo), _ptr(lim_hi), _ptr(hist_lo), _ptr(hist_hi),
                 samples, C.byref(mc), C.byref(cfg), stats.ctypes.data, totals.ctypes.data, _ptr(counts), *(_ptr(a) for a in kept))
         outputs = kind.outputs()
@@ -1282,7 +1285,8 @@ class System:
                             eta2_ptr: int = 0, first_ptr: int = 0, bins_used_ptr: int = 0, factorial: bool = False,
                             factorial_info_ptr: int = 0, factorial_main_ptr: int = 0, factorial_pair_ptr: int = 0,
                             factorial_ss_order_ptr: int = 0, factorial_ss_total_ptr: int = 0, factorial_first_ptr: int = 0,
-                            factorial_total_ptr: int = 0, factorial_coef_ptr: int = 0):
+                            factorial_total_ptr: int = 0, factorial_coef_ptr: int = 0, image=None, image_counts_ptr: int = 0,
+                            image_info_ptr: int = 0):
         """Device pointers for x0 and every output (stats: MC_STATS_DTYPE [n_meas], totals: MC_TOTALS_DTYPE [1], hist: uint64
         [n_meas, bins + 2]) and a hipStream_t handle; positions, dists, records, nominal, limits and hist = (lo, hi, bins) stay host
         values.  Enqueues only once the run's tables are the last run's.  With moments_ptr the run goes through
@@ -1296,14 +1300,17 @@ class System:
         returned (None without effects).  With factorial the run goes through `ezpz_system_tolerance_mc_factorial_device` and fills
         factorial_info_ptr (MC_FACTORIAL_DTYPE [n_meas]), factorial_main_ptr, factorial_ss_total_ptr, factorial_first_ptr and
         factorial_total_ptr [n_meas, kc], factorial_pair_ptr [n_meas, kc, kc], factorial_ss_order_ptr [n_meas, kc + 1] and, where
-        given, factorial_coef_ptr [n_meas, 2^kc]; it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given."""
+        given, factorial_coef_ptr [n_meas, 2^kc]; it reads the kept rows from keep_m_ptr, keep_flags_ptr and keep_ok_ptr where given.
+        With image (a `sketch_image.ImageConfig`, host values, n_layers given) the run goes through
+        `ezpz_system_tolerance_mc_image_device` and fills image_counts_ptr (uint32 [n_layers, height, width]) and image_info_ptr
+        (IMAGE_INFO_DTYPE [1])."""
         given = locals()  # (the keywords by name: a kind names the ones that hold its outputs)
-        kind = _mc_kind(bool(moments_ptr), quantiles, effects, factorial)
+        kind = _mc_kind(bool(moments_ptr), quantiles, effects, factorial, image)
         pos, d, recs, nominal, lim_lo, lim_hi, hist_lo, hist_hi, mc = self._mc_request(positions, dists, records, nominal, limits, hist,
                                                                                      seed, chunk)
         cfg = (config or Config())._c()
         kind = kind(self, pos, d, nominal, len(recs), int(samples), pivot_rel=pivot_rel, quantiles=quantiles, quantile_z=quantile_z,
-                    effects=effects)
+                    effects=effects, image=image)
         args = (self._h, x0_ptr or None, _ptr(pos), len(pos), _ptr(d), _ptr(nominal), _ptr(recs), len(recs), _ptr(lim_lo), _ptr(lim_hi), _ptr(hist_lo),
                 _ptr(hist_hi), int(samples), C.byref(mc), C.byref(cfg), stats_ptr or None, totals_ptr or None, hist_ptr or None,
                 keep_params_ptr or None, keep_m_ptr or None, keep_flags_ptr or None, keep_ok_ptr or None)
@@ -1585,8 +1592,12 @@ def mc_sample(seed: int, dists, nominal, first: int, count: int) -> np.ndarray:
     return out
 
 
-def _mc_kind(contributors, quantiles, effects, factorial):
+def _mc_kind(contributors, quantiles, effects, factorial, image=None):
     """The class of the one kind of a `tolerance_mc` run: the kinds exclude one another."""
+    if image is not None:
+        if contributors or quantiles is not None or effects is not None or factorial:
+            raise ValueError("image together with contributors, quantiles, effects or factorial: run them one after the other")
+        return _McImageKind
     if quantiles is not None and contributors:
         raise ValueError("quantiles together with contributors: run them one after the other")
     if effects is not None and (contributors or quantiles is not None):
@@ -1678,6 +1689,27 @@ class _McFactorialKind(_McPlain):
         return dict(factorial=McFactorial(*out, dims=self.dims, stats=stats))
 
 
+class _McImageKind(_McPlain):
+    entry, device_outputs = "ezpz_system_tolerance_mc_image", ("image_counts_ptr", "image_info_ptr")
+
+    def __init__(self, *request, image, **settings):
+        from .sketch_image import ImageInfo, _layers_of, _view, pack_items  # (the package's `sketch_image` is the function)
+
+        super().__init__(*request)
+        self.items, self.view = pack_items(image.items), _view(image.view)
+        self.n_layers = _layers_of(self.items, image.n_layers)
+        self.info_type = ImageInfo
+        self.inputs = (self.items, len(self.items), C.byref(self.view), self.n_layers)
+
+    def outputs(self):
+        if not (1 <= self.view.width <= 16384 and 1 <= self.view.height <= 16384 and 1 <= self.n_layers <= 8):
+            raise NonLinearSystemError(-103)
+        return (np.zeros((self.n_layers, self.view.height, self.view.width), np.uint32), np.zeros(1, dtype=IMAGE_INFO_DTYPE))
+
+    def result(self, stats, counts, info):
+        return dict(image=counts, image_info=self.info_type(*(int(v) for v in info[0])))
+
+
 def _mc_arg(a):
     return _ptr(a) if a is None or isinstance(a, np.ndarray) else a
 
@@ -1689,10 +1721,13 @@ class McResult:
     contributors also has moments, n_complete, cov, beta, contrib, r2, dropped (those of its `contributors`, a `McContributors`) and
     `corr`.  A run with quantiles also has `quantiles` (MC_QUANTILE_DTYPE [n_meas, n_q]) and its fields as q_value, q_lo, q_hi,
     q_band_lo, q_band_hi.  A run with effects also has `effects` (an `McEffects`), a run with factorial effects `factorial` (an
-    `McFactorial`)."""
+    `McFactorial`), a run with an image `image` (uint32 [n_layers, height, width]) and `image_info`."""
 
-    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None, effects=None, factorial=None):
+    def __init__(self, stats, totals, hist, kept, contributors=None, quantiles=None, effects=None, factorial=None, image=None,
+                 image_info=None):
         self.stats, self.totals, self.hist = stats, totals, hist
+        if image is not None:
+            self.image, self.image_info = image, image_info
         if effects is not None:
             self.effects = effects
         if factorial is not None:

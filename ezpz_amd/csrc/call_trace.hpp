@@ -63,6 +63,9 @@ enum CallStage : uint32_t {
     // ezpz_mc_factorial_device (mc_factorial.hip)
     FACTORIAL_WORKSPACE_GROWN = 130,  // a workspace that had to grow: waited for the last call's launches, allocated
     FACTORIAL_LAUNCHED = 131,         // the gather, the strided levels, the walk and the close enqueued
+    // ezpz_sketch_image_device (sketch_image.hip)
+    IMAGE_WORKSPACE_GROWN = 140,  // another item list than the last call's, or a workspace that had to grow: waited, copied
+    IMAGE_LAUNCHED = 141,         // every round's two passes enqueued
 };
 
 struct CallTrace {

@@ -1,7 +1,9 @@
 // `ezpz-amd`: the reference CLI's behaviour (ezpz-cli/src/main.rs) on top of the C ABI.
 //   -f / --filepath <path|->   problem file, '-' for stdin            (main.rs:20-27, :225-238)
 //   --show-points              print the final values                  (main.rs:33-35, :129-155)
-//   -o / --image-path <png>    accepted, but PNG rendering is out of scope here (visualize.rs)
+//   -o / --image-path <png>    the solved sketch as a PNG file          (main.rs:28-32, visualize.rs:19-68): 1600 x 1600 pixels over
+//                              the reference's span and palette, rasterised on the device (ezpz_sketch_image) and composed on the
+//                              host (ezpz_sketch_compose); axes, mesh, caption and labels are not drawn
 //   --cold                     extension: drop the topology cache before every timed solve
 // Protocol (main.rs:81-103): parse, lower, solve once; lower again and solve 100 more times; report the mean
 // over those 100 of the whole elapsed time.  Output lines follow main.rs:106-203.
@@ -15,6 +17,7 @@
 #include <vector>
 
 #include "../../include/ezpz_amd.h"
+#include "png_write.hpp"
 
 static const int NUM_ITERS_BENCHMARK = 100;  // main.rs:18
 
@@ -41,8 +44,84 @@ static void print_problem_size(size_t num_vars, size_t num_eqs) {  // main.rs:19
     std::printf("Problem size: %zu rows, %zu vars\n", num_eqs, num_vars);
 }
 
+// The picture of the solved values x (visualize.rs:19-68; ezpz_amd/sketch_image.py: items_from_problem, fit_view, REFERENCE_LAYERS,
+// restated): false when an entry fails.
+static bool save_sketch_png(const EzpzProblem* parsed, const std::vector<double>& x, const std::string& path) {
+    const uint32_t side = 1600;
+    const double point_radius = 10.0, half_stroke = 1.5, padding = 1.0;
+    const size_t np = ezpz_problem_num_labels(parsed, 0), nc = ezpz_problem_num_labels(parsed, 1), na = ezpz_problem_num_labels(parsed, 2);
+    enum { POINTS, DISCS, CENTRES, ARCS, LINES, LAYERS };
+    std::vector<EzpzDrawItem> items;
+    auto add = [&](uint16_t kind, uint8_t layer, uint8_t flags, std::initializer_list<size_t> ids, double half_width) {
+        EzpzDrawItem it;
+        std::memset(&it, 0, sizeof it);
+        it.kind = kind, it.layer = layer, it.flags = flags, it.half_width = half_width;
+        int k = 0;
+        for (size_t id : ids) it.ids[k++] = (uint32_t)id;
+        items.push_back(it);
+    };
+    auto circle = [&](size_t i) { return 2 * np + 3 * i; };
+    auto arc = [&](size_t i) { return 2 * np + 3 * nc + 6 * i; };  // a, b, centre
+    for (size_t i = 0; i < np; ++i) add(EZPZ_DRAW_POINT, POINTS, 0, {2 * i, 2 * i + 1}, point_radius);
+    for (size_t i = 0; i < nc; ++i) add(EZPZ_DRAW_POINT, CENTRES, 0, {circle(i), circle(i) + 1}, point_radius);
+    for (size_t offset = 0; offset < 6; offset += 2)
+        for (size_t i = 0; i < na; ++i) add(EZPZ_DRAW_POINT, ARCS, 0, {arc(i) + offset, arc(i) + offset + 1}, point_radius);
+    for (size_t i = 0; i < nc; ++i) add(EZPZ_DRAW_CIRCLE, DISCS, EZPZ_DRAW_FILL, {circle(i), circle(i) + 1, circle(i) + 2}, 0.0);
+    for (size_t i = 0; i < na; ++i) add(EZPZ_DRAW_ARC, ARCS, 0, {arc(i) + 4, arc(i) + 5, arc(i), arc(i) + 1, arc(i) + 2, arc(i) + 3}, half_stroke);
+    for (size_t i = 0; i < ezpz_problem_num_lines(parsed); ++i) {
+        size_t a = 0, b = 0;
+        ezpz_problem_line(parsed, i, &a, &b);
+        add(EZPZ_DRAW_SEGMENT, LINES, 0, {2 * a, 2 * a + 1, 2 * b, 2 * b + 1}, half_stroke);
+    }
+    // Bounds::new, visualize.rs:139-171: one span over both axes (a NaN is left out, as fmin and fmax leave it out)
+    double lo_x = 0.0, hi_x = 0.0, lo_y = 0.0, hi_y = 0.0;
+    bool any_x = false, any_y = false;
+    auto take = [](double v, double& lo, double& hi, bool& any) {
+        if (v != v) return;
+        lo = any ? (v < lo ? v : lo) : v;
+        hi = any ? (v > hi ? v : hi) : v;
+        any = true;
+    };
+    for (const EzpzDrawItem& it : items) {
+        if (it.kind == EZPZ_DRAW_CIRCLE) {
+            for (double sign : {1.0, -1.0}) {
+                take(x[it.ids[0]] + sign * x[it.ids[2]], lo_x, hi_x, any_x);
+                take(x[it.ids[1]] + sign * x[it.ids[2]], lo_y, hi_y, any_y);
+            }
+        } else {
+            const int pairs = it.kind == EZPZ_DRAW_POINT ? 1 : it.kind == EZPZ_DRAW_SEGMENT ? 2 : 3;
+            for (int k = 0; k < pairs; ++k) take(x[it.ids[2 * k]], lo_x, hi_x, any_x), take(x[it.ids[2 * k + 1]], lo_y, hi_y, any_y);
+        }
+    }
+    const double lo = lo_x - padding < lo_y - padding ? lo_x - padding : lo_y - padding;
+    const double hi = hi_x + padding > hi_y + padding ? hi_x + padding : hi_y + padding;
+    EzpzImageView view;
+    view.x_min = lo, view.y_min = lo, view.scale = (double)side / (hi - lo), view.width = side, view.height = side;
+    std::vector<uint32_t> counts((size_t)LAYERS * side * side);
+    EzpzImageInfo info;
+    int rc = ezpz_sketch_image(x.data(), nullptr, 1, x.size(), items.data(), items.size(), &view, LAYERS, 0, counts.data(), &info);
+    if (rc != EZPZ_OK) {
+        std::fprintf(stderr, "Error: could not draw the sketch: %s\n", ezpz_error_string(rc));
+        return false;
+    }
+    // visualize.rs:7-10; the discs at the reference's mix(0.3)
+    static const EzpzComposeLayer layers[LAYERS] = {{{0x58, 0x50, 0x8d}, 255, 0, 1}, {{0xbc, 0x50, 0x90}, 77, 0, 1}, {{0xbc, 0x50, 0x90}, 255, 0, 1},
+                                                    {{0xff, 0x63, 0x61}, 255, 0, 1}, {{0xff, 0xa6, 0x00}, 255, 0, 1}};
+    static const uint8_t white[3] = {255, 255, 255};
+    std::vector<uint8_t> rgb((size_t)side * side * 3), flipped(rgb.size());
+    if (ezpz_sketch_compose(counts.data(), &view, LAYERS, layers, white, rgb.data()) != EZPZ_OK) return false;
+    for (uint32_t y = 0; y < side; ++y)  // row 0 is y_min: the bottom of the picture
+        std::memcpy(&flipped[(size_t)y * side * 3], &rgb[(size_t)(side - 1 - y) * side * 3], (size_t)side * 3);
+    if (!ezpz::png::write_file(path.c_str(), flipped.data(), side, side)) {
+        std::fprintf(stderr, "Error: could not write %s\n", path.c_str());
+        return false;
+    }
+    std::printf("Plot saved to %s\n", path.c_str());  // visualize.rs:66
+    return true;
+}
+
 int main(int argc, char** argv) {
-    std::string filepath;
+    std::string filepath, image_path;
     bool show_points = false, cold = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -54,11 +133,13 @@ int main(int argc, char** argv) {
             show_points = true;
         else if (a == "--cold")
             cold = true;
-        else if ((a == "-o" || a == "--image-path") && i + 1 < argc) {
-            ++i;
-            std::fprintf(stderr, "note: PNG output is not part of this build (presentation layer is out of scope)\n");
-        } else if (a == "-h" || a == "--help") {
-            std::printf("Usage: ezpz-amd --filepath <FILEPATH> [--show-points] [--cold]\n");
+        else if ((a == "-o" || a == "--image-path") && i + 1 < argc)
+            image_path = argv[++i];
+        else if (a.rfind("--image-path=", 0) == 0)
+            image_path = a.substr(13);
+        else if (a == "-h" || a == "--help") {
+            std::printf("Usage: ezpz-amd --filepath <FILEPATH> [--show-points] [--image-path <PNG>] [--cold]\n"
+                        "  -o, --image-path <PNG>  write the solved sketch as a 1600 x 1600 PNG file\n");
             return 0;
         } else {
             std::fprintf(stderr, "error: unexpected argument '%s'\n", a.c_str());
@@ -181,7 +262,12 @@ int main(int argc, char** argv) {
             }
         }
     }
+    bool drawn = true;
+    if (!image_path.empty()) {
+        x.resize(n);
+        drawn = save_sketch_png(parsed, x, image_path);
+    }
     ezpz_problem_destroy(parsed);
     ezpz_problem_destroy(again);
-    return 0;
+    return drawn ? 0 : 1;
 }

@@ -403,6 +403,7 @@ struct EzpzProblem {
     std::vector<EzpzConstraint> constraints;
     std::vector<double> guesses;
     std::vector<std::string> labels[3];  // points, circles, arcs
+    std::vector<std::pair<size_t, size_t>> lines;  // the `line` instructions, as indices into the points (parser.rs:46-48)
 };
 
 namespace {
@@ -520,7 +521,12 @@ void lower(const InstrList& instrs, const std::vector<Guess>& guesses, EzpzProbl
     for (const Instr& in : instrs) {
         const std::string& op = in.op;
         const auto& L = in.labels;
-        if (op == "point" || op == "circle" || op == "arc" || op == "line") continue;
+        if (op == "line") {  // no constraint: kept for the picture (the reference looks both labels up among the points)
+            const int a = index_of(pts, L[0]), b = index_of(pts, L[1]);
+            if (a >= 0 && b >= 0) P.lines.emplace_back((size_t)a, (size_t)b);
+            continue;
+        }
+        if (op == "point" || op == "circle" || op == "arc") continue;
         if (op == "radius") {
             Pt c = datum_point(L[0] + ".center");
             uint32_t r = datum_distance(L[0] + ".radius");
@@ -675,6 +681,13 @@ size_t ezpz_problem_num_labels(const EzpzProblem* p, int kind) {
 const char* ezpz_problem_label(const EzpzProblem* p, int kind, size_t index) {
     if (!p || kind < 0 || kind > 2 || index >= p->labels[kind].size()) return nullptr;
     return p->labels[kind][index].c_str();
+}
+size_t ezpz_problem_num_lines(const EzpzProblem* p) { return p ? p->lines.size() : 0; }
+int ezpz_problem_line(const EzpzProblem* p, size_t i, size_t* point_a, size_t* point_b) {
+    if (!p || !point_a || !point_b || i >= p->lines.size()) return EZPZ_ERR_INVALID_ARGUMENT;
+    *point_a = p->lines[i].first;
+    *point_b = p->lines[i].second;
+    return EZPZ_OK;
 }
 
 }  // extern "C"

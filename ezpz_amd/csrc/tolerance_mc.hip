@@ -5,7 +5,7 @@
 // Needs lists every buffer with its count once, and both "does anything grow" and "grow it" are that list -- and measures the
 // nominal; sub_round() is sampler -> copies of x0 -> ezpz_system_solve_batch_params_device -> ezpz_system_measure_device, all on
 // the caller's stream: the driven solve and the measurement are those entries themselves, with their routes, their locks and their
-// ordering.  What a kind adds stands in its tail alone -- Plain, Contrib, Quant, Effects, Fact, SobolOut: its checks, the one list of
+// ordering.  What a kind adds stands in its tail alone -- Plain, Contrib, Quant, Effects, Fact, Image, SobolOut: its checks, the one list of
 // its outputs, its workspaces and what it enqueues -- and the run is a template on the tail that names none of them:
 //   run()        one sub-round a round, the reduction behind it, then the tail's behind_round(); the rows kept on the device where
 //                the tail reads them; the tail's behind_run() behind the last round
@@ -21,6 +21,7 @@
 #include "mc_quantiles.hip.hpp"
 #include "mc_sobol.hip.hpp"
 #include "measure_tables.hpp"
+#include "sketch_image.hip.hpp"
 #include "tolerance_mc.hip.hpp"
 
 using namespace ezpz;
@@ -416,6 +417,32 @@ struct Fact : Plain {
     bool keeps_rows() const { return true; }
     int behind_run(McPlan& P, const Call& c, const Rows& rows) const {
         return mcf::enqueue_factorial(P.factorial_work, rows.m, rows.flags, rows.ok, P.nominal.p, kc, (uint32_t)c.n_meas, out, c.sys->lim.cus, c.stream);
+    }
+};
+
+// The picture (ezpz_system_tolerance_mc_image[_device]): every round's solved variants -- the round's x_out with its ok
+// bytes -- drawn by ezpz_sketch_image_device behind the round's reduction; the first round's call zeroes counts and info, the others
+// add.  items and view: host memory.  The rasteriser's workspace is the process's, not the plan's.
+struct Image : Plain {
+    const EzpzDrawItem* items = nullptr;
+    size_t n_items = 0;
+    const EzpzImageView* view = nullptr;
+    uint32_t n_layers = 0;
+    uint32_t* counts = nullptr;
+    EzpzImageInfo* info = nullptr;
+
+    // (the drawing entry's own check, on a round's variants; without samples nothing is written and no output is asked for)
+    int check(const Call& c, Request& r) {
+        const void* given = this;
+        return skimg::check_request(given, (size_t)std::min<uint64_t>(c.samples, r.chunk), c.sys->counts.n_vars, items, n_items, view, n_layers,
+                                    c.samples ? (const void*)counts : given, c.samples ? (const void*)info : given);
+    }
+    template <class F>
+    void outputs(size_t, size_t, F&& f) {
+        f(counts, view ? (size_t)n_layers * view->width * view->height : 0), f(info, 1);
+    }
+    int behind_round(McPlan& P, const Call& c, uint64_t first, uint64_t count) const {
+        return ezpz_sketch_image_device(P.x_out.p, P.ok.p, count, c.sys->counts.n_vars, items, n_items, view, n_layers, first != 0, counts, info, c.stream);
     }
 };
 
@@ -898,6 +925,35 @@ int ezpz_system_tolerance_mc_factorial(EzpzSystem* sys, const double* x0, const 
     f.out.info = info, f.out.main = main, f.out.pair = pair, f.out.ss_order = ss_order, f.out.ss_total = ss_total;
     f.out.first = first, f.out.total = total, f.out.coef = coef;
     return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, f, true);
+}
+
+int ezpz_system_tolerance_mc_image_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                          const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                          const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                          uint64_t samples, const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                          EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                          uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, const EzpzDrawItem* items, size_t n_items,
+                                          const EzpzImageView* view, uint32_t n_layers, uint32_t* counts_dev, EzpzImageInfo* info_dev,
+                                          void* stream) {
+    const Call c{sys, x0_dev, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                 stats_dev, totals_dev, hist_dev, (hipStream_t)stream};
+    Image o;
+    o.items = items, o.n_items = n_items, o.view = view, o.n_layers = n_layers, o.counts = counts_dev, o.info = info_dev;
+    return entry(c, Keep{keep_params_dev, keep_m_dev, keep_flags_dev, keep_ok_dev, false}, o, false);
+}
+
+int ezpz_system_tolerance_mc_image(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                   const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                   const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                   const EzpzMcConfig* mc_cfg, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals,
+                                   uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok,
+                                   const EzpzDrawItem* items, size_t n_items, const EzpzImageView* view, uint32_t n_layers,
+                                   uint32_t* counts, EzpzImageInfo* info) {
+    const Call c{sys, x0, positions, n_param, dist, nominal, records, n_meas, lim_lo, lim_hi, hist_lo, hist_hi, samples, mc_cfg, cfg,
+                 stats, totals, hist, hipStreamPerThread};
+    Image o;
+    o.items = items, o.n_items = n_items, o.view = view, o.n_layers = n_layers, o.counts = counts, o.info = info;
+    return entry(c, Keep{keep_params, keep_m, keep_flags, keep_ok, true}, o, true);
 }
 
 int ezpz_system_tolerance_sobol_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,

@@ -53,6 +53,7 @@ class ConstraintSystem:
     inner_points: List[str]
     inner_circles: List[str]
     inner_arcs: List[str]
+    inner_lines: List[Tuple[int, int]] = field(default_factory=list)  # the `line` instructions, as indices into inner_points
 
     @property
     def num_vars(self) -> int:
@@ -128,9 +129,14 @@ class Problem:
                 C.memmove(guesses.ctypes.data, L.ezpz_problem_guesses(h), n_vars * 8)
             labels = [[L.ezpz_problem_label(h, k, i).decode() for i in range(L.ezpz_problem_num_labels(h, k))]
                       for k in range(3)]
+            lines = []
+            for i in range(L.ezpz_problem_num_lines(h)):
+                a, b = C.c_size_t(), C.c_size_t()
+                L.ezpz_problem_line(h, i, C.byref(a), C.byref(b))
+                lines.append((a.value, b.value))
         finally:
             lib().ezpz_problem_destroy(h)
-        return Problem(ConstraintSystem(recs, guesses, labels[0], labels[1], labels[2]))
+        return Problem(ConstraintSystem(recs, guesses, labels[0], labels[1], labels[2], lines))
 
     def to_constraint_system(self) -> ConstraintSystem:
         return self._system

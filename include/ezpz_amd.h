@@ -1597,6 +1597,107 @@ const double* ezpz_problem_guesses(const EzpzProblem* p); /* values by id (id ==
 /* label tables, executor.rs:521-566: kind 0 = points, 1 = circles, 2 = arcs */
 size_t ezpz_problem_num_labels(const EzpzProblem* p, int kind);
 const char* ezpz_problem_label(const EzpzProblem* p, int kind, size_t index);
+/* the `line(p, q)` instructions, in the text's order (parser.rs:46-48, inner_lines), as indices into the point labels (kind 0):
+ * what the reference draws as strokes.  A line whose label is no declared point is not kept.  ezpz_problem_line: EZPZ_OK, or
+ * EZPZ_ERR_INVALID_ARGUMENT for a NULL argument or i past the last line. */
+size_t ezpz_problem_num_lines(const EzpzProblem* p);
+int ezpz_problem_line(const EzpzProblem* p, size_t i, size_t* point_a, size_t* point_b);
+
+/* ---- Sketch images: many variants of one drawing list accumulated into an integer image (the counterpart of the
+ * reference's ezpz-cli/src/visualize.rs, without its axes, mesh and text) --------------------------------------------------------
+ * x [batch][n_vars]: the values of `batch` variants of one sketch -- one solution, the steps of a sweep, the branches, the
+ * samples of a tolerance run; ok [batch] or NULL: a variant whose byte is 0 draws nothing.  items [n_items] and view: host memory
+ * in every form.  counts [n_layers][height][width], uint32: the number of (variant, item) pairs of that layer that cover the
+ * pixel -- two items of one variant on one pixel count twice; row 0 is y_min.  accumulate != 0 adds to what counts and info
+ * hold, otherwise both are zeroed first (also with batch == 0 or n_items == 0); a count that wraps over several accumulating calls
+ * is the caller's business.
+ * THE RULE.  Only + - * /, fabs and comparisons, every operation rounded once in the order written (no unit of the library
+ * contracts a product into a fused multiply-add): the host body, the kernel and numpy decide every pixel alike, and the counts
+ * are integers, so the bytes do not depend on the batch, the chunk, the stream or the placement.
+ * A value pair (x, y) is in pixel space u = (x - x_min) * scale, v = (y - y_min) * scale; the centre of pixel (px, py) is
+ * (X, Y) = (px + 0.5, py + 0.5); h = half_width.  ids per kind, unused ones 0:
+ *   POINT    x, y.  dx = X - u; dy = Y - v; covered iff dx*dx + dy*dy <= h*h.
+ *   SEGMENT  ax, ay, bx, by.  ex = bu - au; ey = bv - av; L2 = ex*ex + ey*ey; wx = X - au; wy = Y - av; t = wx*ex + wy*ey.
+ *            L2 == 0 || t <= 0: covered iff wx*wx + wy*wy <= h*h.  Else t >= L2: zx = X - bu; zy = Y - bv; covered iff
+ *            zx*zx + zy*zy <= h*h.  Else cr = wx*ey - wy*ex; covered iff cr*cr <= (h*h)*L2.  (A capsule.)
+ *   CIRCLE   cx, cy, r.  R = fabs(r) * scale; wx = X - u; wy = Y - v; d2 = wx*wx + wy*wy; R2 = R*R.  With EZPZ_DRAW_FILL: hi =
+ *            R + h; covered iff d2 <= hi*hi.  Else the ring: q = (d2 + R2) - h*h; covered iff q <= 0 || q*q <= (4.0*d2)*R2.
+ *   ARC      cx, cy, ax, ay, bx, by: the minor arc from a to b about c with the radius |a - c| (visualize.rs:289-302).  px = au -
+ *            cu; py = av - cv; qx = bu - cu; qy = bv - cv; R2 = px*px + py*py; wx = X - cu; wy = Y - cv; the ring as for the
+ *            circle, and the sector: s = px*qy - py*qx; c1 = px*wy - py*wx; c2 = wx*qy - wy*qx.  s > 0: c1 >= 0 && c2 >= 0.
+ *            s < 0: c1 <= 0 && c2 <= 0.  s == 0 with px*qx + py*qy > 0: nothing.  s == 0 otherwise: c1 >= 0 (the half-turn
+ *            counter-clockwise from a).  The ends are radial cuts, without caps.
+ * An item of a variant is skipped when one of its pixel-space numbers (every u and v, the circle's R) is not finite or above
+ * 2^30 in magnitude; the items of a variant that draws nothing are not looked at.
+ * EzpzImageInfo: variants -- the batch; masked -- variants whose ok byte is 0; items_skipped; increments -- the sum of everything
+ * added to counts, a checksum.
+ * ezpz_sketch_image_device: device pointers for x, ok, counts and info, the current device, a hipStream_t; it takes no system.  It
+ * enqueues only once the item list is the last call's (another list waits for the earlier launches and is copied).
+ * ezpz_sketch_image: the same through host pointers.  ezpz_sketch_image_host: the rule alone, plain loops over every pixel of the
+ * view on the host; it needs no device.
+ * EZPZ_ERR_INVALID_ARGUMENT with nothing enqueued and no output touched: view, counts or info NULL; items NULL with n_items > 0;
+ * x NULL with batch > 0 and n_items > 0; n_layers outside 1 .. 8; width or height outside 1 .. 16384; a scale that is not finite
+ * and > 0; x_min or y_min not finite; a kind above EZPZ_DRAW_ARC; a layer >= n_layers; a flag other than EZPZ_DRAW_FILL, or
+ * EZPZ_DRAW_FILL on another kind than CIRCLE; a used id >= n_vars; a half_width that is not finite and >= 0.  EZPZ_ERR_TOO_LARGE:
+ * batch * n_items >= 2^32. */
+#define EZPZ_DRAW_POINT 0
+#define EZPZ_DRAW_SEGMENT 1
+#define EZPZ_DRAW_CIRCLE 2
+#define EZPZ_DRAW_ARC 3
+#define EZPZ_DRAW_FILL 1u
+#define EZPZ_IMAGE_MAX_LAYERS 8u
+#define EZPZ_IMAGE_MAX_SIDE 16384u
+typedef struct EzpzImageView { /* 32 bytes; isotropic: a circle stays a circle */
+    double x_min, y_min, scale;
+    uint32_t width, height;
+} EzpzImageView;
+typedef struct EzpzDrawItem { /* 40 bytes */
+    uint16_t kind;
+    uint8_t layer;
+    uint8_t flags;
+    uint32_t ids[6];
+    double half_width; /* pixels; POINT: the disc's radius */
+} EzpzDrawItem;
+typedef struct EzpzImageInfo { /* 32 bytes */
+    uint64_t variants, masked, items_skipped, increments;
+} EzpzImageInfo;
+int ezpz_sketch_image_device(const double* x_dev, const uint8_t* ok_dev, size_t batch, size_t n_vars, const EzpzDrawItem* items,
+                             size_t n_items, const EzpzImageView* view, uint32_t n_layers, int accumulate, uint32_t* counts_dev,
+                             EzpzImageInfo* info_dev, void* stream);
+int ezpz_sketch_image(const double* x, const uint8_t* ok, size_t batch, size_t n_vars, const EzpzDrawItem* items, size_t n_items,
+                      const EzpzImageView* view, uint32_t n_layers, int accumulate, uint32_t* counts, EzpzImageInfo* info);
+int ezpz_sketch_image_host(const double* x, const uint8_t* ok, size_t batch, size_t n_vars, const EzpzDrawItem* items, size_t n_items,
+                           const EzpzImageView* view, uint32_t n_layers, int accumulate, uint32_t* counts, EzpzImageInfo* info);
+/* ezpz_system_tolerance_mc_image[_device]: ezpz_system_tolerance_mc[_device] -- the same arguments, the same run, stats, totals,
+ * hist and keep_* byte for byte -- and behind every round's reduction the round's solved variants drawn into counts
+ * [n_layers][height][width] with the round's ok bytes: a variant that did not solve draws nothing.  The run zeroes counts and info
+ * once; items and view are host memory, counts and info device memory in the _device form.  Not combined with the other kinds in
+ * one call.  The argument errors of both entries; with samples == 0: EZPZ_OK after those checks, nothing written. */
+int ezpz_system_tolerance_mc_image(EzpzSystem* sys, const double* x0, const uint32_t* positions, size_t n_param, const EzpzMcDist* dist,
+                                   const double* nominal, const EzpzConstraint* records, size_t n_meas, const double* lim_lo,
+                                   const double* lim_hi, const double* hist_lo, const double* hist_hi, uint64_t samples,
+                                   const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats, EzpzMcTotals* totals,
+                                   uint64_t* hist, double* keep_params, double* keep_m, uint8_t* keep_flags, uint8_t* keep_ok,
+                                   const EzpzDrawItem* items, size_t n_items, const EzpzImageView* view, uint32_t n_layers,
+                                   uint32_t* counts, EzpzImageInfo* info);
+int ezpz_system_tolerance_mc_image_device(EzpzSystem* sys, const double* x0_dev, const uint32_t* positions, size_t n_param,
+                                          const EzpzMcDist* dist, const double* nominal, const EzpzConstraint* records, size_t n_meas,
+                                          const double* lim_lo, const double* lim_hi, const double* hist_lo, const double* hist_hi,
+                                          uint64_t samples, const EzpzMcConfig* mc, const EzpzConfig* cfg, EzpzMcStats* stats_dev,
+                                          EzpzMcTotals* totals_dev, uint64_t* hist_dev, double* keep_params_dev, double* keep_m_dev,
+                                          uint8_t* keep_flags_dev, uint8_t* keep_ok_dev, const EzpzDrawItem* items, size_t n_items,
+                                          const EzpzImageView* view, uint32_t n_layers, uint32_t* counts_dev, EzpzImageInfo* info_dev,
+                                          void* stream);
+/* ezpz_sketch_compose: counts to colours on the host, integer arithmetic only.  rgb_out [height][width][3] starts as
+ * background; per pixel the layers in order: F = full_at, or the layer's largest count where full_at is 0 (1 where that is 0 too);
+ * a = count == 0 ? 0 : max(a_min, min(count, F) * 255 / F); a = a * opacity / 255; out_c = (out_c * (255 - a) + rgb_c * a +
+ * 127) / 255.  EZPZ_ERR_INVALID_ARGUMENT: a NULL argument, a view or n_layers as above. */
+typedef struct EzpzComposeLayer { /* 12 bytes */
+    uint8_t rgb[3], opacity, a_min;
+    uint32_t full_at;
+} EzpzComposeLayer;
+int ezpz_sketch_compose(const uint32_t* counts, const EzpzImageView* view, uint32_t n_layers, const EzpzComposeLayer* layers,
+                        const uint8_t background[3], uint8_t* rgb_out);
 
 #ifdef __cplusplus
 }
